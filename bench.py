@@ -20,8 +20,12 @@ Phases of one run (only the third is timed for `value`):
   warm-up    W untimed steps;
   timed      barrier + synchronize, EXACTLY K steps with the frames already resident in HBM, barrier + synchronize,
              MAX over ranks;
-  extras     (rank 0, N = 1) the same stream through the host-input entry point (`input: host` rate, PCIe inclusive),
-             trajectory error (ATE) against the synthetic ground truth and against the CPU oracle, the CPU baseline.
+  outputs    (--dump-outputs DIR) what the last timed step left for a caller -- poses, ids, surfel counts and maps, the label
+             mask -- as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output;
+  extras     (--full only) the state digest / parity against one GPU, the N > 1 replicas, and on rank 0 at N = 1 the same
+             stream through the host-input entry point (`input: host` rate, PCIe inclusive), the .klg input rate, trajectory error
+             (ATE) against the synthetic ground truth, the CPU oracle and the reference tracker, the static secondary, the CPU
+             baseline.  A plain run stops after the headline line's own figures.
 
 N > 1: one process per GPU, the SAME workload as N = 1 (configs[2] unless --workload says otherwise; the same pre-roll with
 ground-truth masks, so the same models exist at every N).  `--gpus N` without RANK in the environment re-executes itself under
@@ -39,7 +43,7 @@ The JSON line also carries
                 correspondence list that replaces the reference's 16 B DataTerm record is not counted) -- from the
                 dispatches' own begin/end timestamps (hipEvents attached to the launch on the launch stream);
                 `traffic` = HBM-side bytes per launch from the committed rocprofv3 FETCH_SIZE / WRITE_SIZE passes;
-  cpu_baseline  the CPU oracle's odometry path (map preparation + SO3 + 4/5/10 ICP+RGB Gauss-Newton iterations of every
+  cpu_baseline  (--full) the CPU oracle's odometry path (map preparation + SO3 + 4/5/10 ICP+RGB Gauss-Newton iterations of every
                 active model; "port": the reference cannot be built here) compiled -O3 -march=native -fopenmp on this box,
                 timed with 1 thread (`cpu_baseline`) and with all cores (`cpu_baseline_all_cores`) on frames sampled
                 from the same run (inputs = what the GPU tracker read), median per frame.
@@ -61,6 +65,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
+DUMP_SURFEL_ROWS = 1 << 20   # --dump-outputs: surfel rows written in all (48 B each); beyond it a fixed sample of every model's map
+DUMP_MAX_BYTES = 60 * 10 ** 6   # (under 64 MB with the .npy headers)
 
 WORKLOADS = {
     "static": dict(n_obj=0, size=(640, 480), config="configs[1]", desc="single static background model (-static)"),
@@ -90,6 +96,14 @@ def parse(argv=None):
                     help="object workloads: how the object models are spawned during the pre-roll -- 'gt': ground-truth label masks (every "
                          "object gets a model), 'crf': the motion CRF (spawns what it detects); the warm-up and the timed steps always use "
                          "the workload's own segmentation")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: the state digest / N = 1 parity check, the N > 1 replicas, the host-input "
+                         "rate, .klg input, ATE against the ground truth / the oracle / the reference tracker, the static secondary and the CPU "
+                         "baseline (--no-extras / --no-cpu-baseline drop some of them again); without it a run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left for a caller as DIR/<name>.npy (f32 / f64): every model's "
+                         "id, pose, confidence threshold, surfel count and surfels (a fixed sample beyond %d in all; with models over N ranks gathered from "
+                         "their owners, so that the files compare with one GPU's), the label mask" % DUMP_SURFEL_ROWS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip host-input rate / ATE / secondary legs")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work per CPU-baseline leg")
@@ -150,13 +164,57 @@ def parse(argv=None):
     return a
 
 
-def make_stream(width, height, n_frames, n_obj=0, seed=1234):
-    """Seeded synthetic RGB-D stream (co_fusion_amd/synth.py): noisy depth (mm-quantised), RGB, label masks, GT camera poses."""
+def _render_frames(width, height, n_obj, seed, ts):
+    """Frames ts of the seeded scene (a worker of make_stream: every frame is a pure function of (scene seed, t))."""
     warnings.filterwarnings("ignore", category=RuntimeWarning)
     from co_fusion_amd import synth
     cam = synth.Camera.scaled(width, height)
-    # the analytic ray caster needs ~0.7 s per 640x480 frame: rendered frames are kept in a scratch cache between runs
-    cache = os.path.join(os.environ.get("CF_BENCH_CACHE", "/tmp/cf_bench_cache"), f"s{seed}_{width}x{height}_o{n_obj}_n{n_frames}.npz")
+    sc = synth.Scene(n_obj=n_obj, seed=seed)
+    return [sc.render(cam, t, noise=True) for t in ts]
+
+
+def _render_parallel(width, height, n_obj, seed, n_frames):
+    """The stream's frames rendered by up to 16 fresh worker processes per node (spawned, not forked: they hold no GPU state), one BLAS thread
+    each; the frames are bit-identical to a serial render."""
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    workers = max(1, min(16 // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))), cpus, n_frames))   # (the ranks of a node share 16)
+    if workers == 1:
+        return _render_frames(width, height, n_obj, seed, range(n_frames))
+    chunks = [list(range(w, n_frames, workers)) for w in range(workers)]
+    pinned = ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS")
+    saved = {k: os.environ.get(k) for k in pinned}
+    os.environ.update({k: "1" for k in pinned})   # inherited by the workers only: they start inside this block
+    try:
+        with ProcessPoolExecutor(max_workers=workers, mp_context=mp.get_context("spawn")) as ex:
+            parts = list(ex.map(_render_frames, [width] * workers, [height] * workers, [n_obj] * workers, [seed] * workers, chunks))
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    out = [None] * n_frames
+    for ts, fr in zip(chunks, parts):
+        for t, f in zip(ts, fr):
+            out[t] = f
+    return out
+
+
+def make_stream(width, height, n_frames, n_obj=0, seed=1234):
+    """Seeded synthetic RGB-D stream (co_fusion_amd/synth.py): noisy depth (mm-quantised), RGB, label masks, GT camera poses."""
+    import hashlib
+    warnings.filterwarnings("ignore", category=RuntimeWarning)
+    from co_fusion_amd import synth
+    cam = synth.Camera.scaled(width, height)
+    # the analytic ray caster needs ~0.7 s per 640x480 frame: rendered frames are kept in a scratch cache between runs, keyed by the
+    # generator's source so that a changed generator never hands out frames of another
+    src = hashlib.sha256(open(synth.__file__, "rb").read()).hexdigest()[:12]
+    cache = os.path.join(os.environ.get("CF_BENCH_CACHE", "/tmp/cf_bench_cache"), f"s{seed}_{width}x{height}_o{n_obj}_n{n_frames}_{src}.npz")
     if os.path.exists(cache):
         try:
             z = np.load(cache)
@@ -164,11 +222,8 @@ def make_stream(width, height, n_frames, n_obj=0, seed=1234):
                          for t in range(n_frames)]
         except Exception:  # noqa: BLE001 -- a torn cache file is simply regenerated
             pass
-    sc = synth.Scene(n_obj=n_obj, seed=seed)
-    frames = []
-    for t in range(n_frames):
-        d, rgb, lab, T = sc.render(cam, t, noise=True)
-        frames.append(dict(depth=d, rgb=rgb, rgba=synth.rgb_to_rgba(rgb), label=lab, T=T))
+    frames = [dict(depth=d, rgb=rgb, rgba=synth.rgb_to_rgba(rgb), label=lab, T=T)
+              for d, rgb, lab, T in _render_parallel(width, height, n_obj, seed, n_frames)]
     try:
         os.makedirs(os.path.dirname(cache), exist_ok=True)
         tmp = cache + f".{os.getpid()}.tmp.npz"
@@ -384,18 +439,26 @@ def main(argv=None):
     prof = cf.profile_read(reset=True)
     cf.profile_enable(False)
     fps = args.steps * (1 if model_parallel else world) * S / dt
+    if args.dump_outputs:   # (before any other leg plays more frames through this instance)
+        if model_parallel:   # every rank takes part: the maps live with their owners
+            maps = gather_model_maps(cf, dist, rank, world)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, [cf], maps=maps)
+        elif rank == 0:
+            dump_outputs(args.dump_outputs, [st["cf"] for st in streams])
 
     # Parity of the run itself ("make the 8-GPU tier check, not just time"): a digest of the state the timed steps ended in --
     # model ids, poses, confidence thresholds, surfel counts (summed over their owners), the label mask.  With object models spread over
     # the GPUs, rank 0 then plays the SAME frames through a single-GPU instance and compares: the line says whether N GPUs gave the bits
-    # one GPU gives.  (Independent replicas: rank 0's sequence is the N = 1 sequence; its digest is the same at every N.)
+    # one GPU gives.  (Independent replicas: rank 0's sequence is the N = 1 sequence; its digest is the same at every N.)  --full only.
     parity = None
-    try:
-        parity = parity_vs_n1(args, torch, dist, facade, cf, streams[0], rank, world, local_rank, model_parallel, W, H, cam, P, pre_masks, use_gt, gt_mask)
-    except Exception as e:  # noqa: BLE001 -- the headline line must not depend on this leg
-        parity = dict(error=str(e))
+    if args.full:
+        try:
+            parity = parity_vs_n1(args, torch, dist, facade, cf, streams[0], rank, world, local_rank, model_parallel, W, H, cam, P, pre_masks, use_gt, gt_mask)
+        except Exception as e:  # noqa: BLE001 -- the headline line must not depend on this leg
+            parity = dict(error=str(e))
     replicas = None
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         try:
             replicas = replicas_leg(args, torch, facade, local_rank, rank, world, barrier, all_reduce_max)
         except Exception as e:  # noqa: BLE001 -- the headline line must not depend on this leg
@@ -411,7 +474,8 @@ def main(argv=None):
         # planes once (24 B per pixel, shared by the trackers through L2), per tracker 24 B for every pixel of the 64-pixel runs inside its
         # final screen box (the whole image for the background) and 11 B for every pixel of the record slots between its first and last RGB
         # candidate (cf_odom_level0_visited; the last timed frame's tracking call)
-        visited = [cf.model_level0_visited(i) for i in range(n_models)]
+        # (models over ranks: this rank's launch carries its own trackers only; a shadow model has no tracker here and visits nothing)
+        visited = [cf.model_level0_visited(i) if not model_parallel or cf.model_owned(i) else (0, 0) for i in range(n_models)]
         # (the residual pass reads the 1-byte candidate mask over the whole slot range and the other 10 bytes -- next depth, both intensities,
         # gathered last depth -- only where the mask is set; a culled tracker's mask is empty outside its prediction, i.e. outside the pixels
         # its ICP runs cover: 10 B x min(range, ICP pixels).  A tracker that is not culled: 11 B x every pixel, SURVEY 8(d)'s figure.)
@@ -488,9 +552,9 @@ def main(argv=None):
             out["parity_vs_n1"] = parity
         if replicas is not None:
             out["replicas"] = replicas
-        if world == 1 and S == 1 and not args.no_extras:
+        if args.full and world == 1 and S == 1 and not args.no_extras:
             extras(out, args, cf, cam, frames, base + args.steps, use_gt, torch, facade, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 c1, call = cpu_baseline(cf, cam, frames, base + args.steps + 200, step_stream, streams[0], args.cpu_budget)
                 out["cpu_baseline"] = c1
@@ -518,6 +582,57 @@ def state_digest(cf, counts=None):
         h.update(np.int64(info["count"] if counts is None else counts[i]).tobytes())
     h.update(np.ascontiguousarray(cf.mask()).tobytes())
     return h.hexdigest()
+
+
+def gather_model_maps(cf, dist, rank, world):
+    """Model-parallel ranks: every model's surfel map from its first owner in rank order (a replicated background is taken once), on rank 0;
+    None elsewhere.  Collective: every rank calls it."""
+    own = {i: cf.model_download(i) for i in range(cf.num_models) if cf.model_owned(i)}
+    parts = [None] * world if rank == 0 else None
+    dist.gather_object(own, parts, dst=0)
+    if rank != 0:
+        return None
+    maps = {}
+    for part in parts:
+        for i, m in part.items():
+            maps.setdefault(i, m)
+    return maps
+
+
+def dump_outputs(out_dir, instances, maps=None):
+    """--dump-outputs: what the last timed step left for a caller of processFrame, as <out_dir>/<name>.npy -- per model its id, pose, confidence
+    threshold, surfel count (model_ids / model_poses / model_conf_thresholds / model_surfel_counts, in model-list order), its surfel map
+    (model<i>_surfels: [n, 12] f32 rows of cofusion_model_download) and the label mask (label_mask, f32).  Beyond DUMP_SURFEL_ROWS surfels in
+    all (or what DUMP_MAX_BYTES leaves of them), every model keeps its share as a fixed sample (seeded by the model's position, rows in map
+    order).  Several instances (sequences of a lock-step run): names prefixed seq<k>_.  maps (one instance, model-parallel): {model: surfel map}
+    gathered from the owners (gather_model_maps); the surfel counts are then those maps' lengths, as one GPU reports them."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays, given, maps = {}, maps, {}
+    for k, cf in enumerate(instances):
+        pre = f"seq{k}_" if len(instances) > 1 else ""
+        n = cf.num_models
+        infos = [cf.model_info(i) for i in range(n)]
+        arrays[pre + "model_ids"] = np.array([m["id"] for m in infos], np.float64)
+        arrays[pre + "model_poses"] = np.array([m["pose"] for m in infos], np.float32).reshape(n, 4, 4)
+        arrays[pre + "model_conf_thresholds"] = np.array([m["conf_threshold"] for m in infos], np.float32)
+        if given is None:
+            maps.update({(pre, i): cf.model_download(i) for i in range(n)})
+        else:
+            maps.update({(pre, i): m for i, m in given.items()})
+        arrays[pre + "model_surfel_counts"] = np.array([len(maps[(pre, i)]) if (pre, i) in maps else m["count"] for i, m in enumerate(infos)],
+                                                       np.float64)
+        arrays[pre + "label_mask"] = cf.mask().astype(np.float32)
+    total = sum(len(s) for s in maps.values())
+    budget = min(DUMP_SURFEL_ROWS, (DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())) // (12 * 4))
+    for (pre, i), s in maps.items():
+        if total > budget:
+            keep = len(s) * budget // total
+            s = s[np.sort(np.random.default_rng(i).choice(len(s), keep, replace=False))]
+        arrays[f"{pre}model{i}_surfels"] = np.ascontiguousarray(s, np.float32)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, f"--dump-outputs: {nbytes} bytes exceed {DUMP_MAX_BYTES}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def parity_vs_n1(args, torch, dist, facade, cf, st, rank, world, local_rank, model_parallel, W, H, cam, P, pre_masks, use_gt, gt_mask):
@@ -664,6 +779,9 @@ def lockstep_run(args, torch, facade, local_rank, wl, S):
     dt = time.perf_counter() - t0
     prof = cf0.profile_read(reset=True)
     cf0.profile_enable(False)
+    if args.dump_outputs:   # sequence order (group g holds sequences g, g + G, ...)
+        seq = {m: q for gr in groups for m, q in zip(gr["members"], gr["g"].sequences)}
+        dump_outputs(args.dump_outputs, [seq[m] for m in range(S)])
     n_models = [q.num_models for gr in groups for q in gr["g"].sequences]
     trackers = sum(q.num_models for q in groups[0]["g"].sequences)
     avg_us = 1e3 * prof.icp_ms_total / max(1, prof.icp_launches)

@@ -236,7 +236,7 @@ def test_bench_line_checks_itself_against_one_gpu(tmp_path):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--preroll", "40",
-                          "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["rccl_world"] == 2, line["config"]

@@ -1,6 +1,6 @@
 #!/bin/bash
-# diagnostic: the shader clock while the default bench runs (a frame of launch-floor kernels keeps the chip mostly idle), and the
-# headline with the performance level pinned to "high" (rocm-smi) -- what the DVFS governor costs a latency-bound workload
+# diagnostic: the shader clock while the default bench runs (a frame of launch-floor kernels keeps the chip mostly idle); observes only,
+# the performance level is left as the machine has it
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-clocks}
@@ -18,16 +18,9 @@ python bench.py --no-cpu-baseline --no-extras --steps 3000 --warmup 20 > $O/line
 BP=$!
 sleep 12; sample $O/sclk_auto.txt
 wait $BP
-rocm-smi --setperflevel high > $O/set_high.txt 2>&1
-rocm-smi --showperflevel --showclocks > $O/smi_high.txt 2>&1
-python bench.py --no-cpu-baseline --no-extras --steps 3000 --warmup 20 > $O/line_high.json 2> $O/line_high.err &
-BP=$!
-sleep 12; sample $O/sclk_high.txt
-wait $BP
-rocm-smi --setperflevel auto > /dev/null 2>&1
 python - <<PY
 import json
-for n in ("auto", "high"):
+for n in ("auto",):
     try:
         d = json.loads(open("$O/line_%s.json" % n).read().strip().splitlines()[-1])
         print(n, "fps", d["value"], "ms", d["ms_per_step"], "icp us", d["roofline"]["avg_us"], "frac", d["roofline"]["frac"])

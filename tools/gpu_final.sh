@@ -15,4 +15,4 @@ python $R/tools/timed_launches.py $O/prof "icp_reduce_kernel<2, 0, false>" 100 1
 find $O/prof -name "*kernel_trace.csv" -delete
 cd $R
 PMC_SQ=${PMC_SQ:-1} bash tools/gpu_pmc.sh ${1:-final}/pmc > $O/pmc.log 2>&1; tail -12 $O/pmc.log
-timeout 280 python bench.py > $O/bench_default_line.json 2> $O/bench.err; tail -c 600 $O/bench_default_line.json
+timeout 600 python bench.py --full > $O/bench_default_line.json 2> $O/bench.err; tail -c 600 $O/bench_default_line.json

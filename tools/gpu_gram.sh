@@ -13,7 +13,7 @@ try:
 except Exception as e:
     print(json.dumps({'args': '$*', 'error': str(e), 'raw': l[:200]}))" >> $out/lines.jsonl; }
 for A in product gram; do
-  run --icp-arith $A --no-cpu-baseline
+  run --icp-arith $A --full --no-cpu-baseline
   run --icp-arith $A --no-cpu-baseline --no-extras --workload static
   run --icp-arith $A --no-cpu-baseline --no-extras --workload big --steps 40 --warmup 10
   run --icp-arith $A --no-cpu-baseline --no-extras --workload static --streams 12 --lockstep

@@ -15,4 +15,4 @@ python $R/tools/timed_launches.py $O/prof "icp_reduce_kernel<2, 0, false>" 100 1
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/rocprofv3_kernel_stats.csv
 rm -rf $O/prof
 cd $R
-timeout 200 python bench.py > $O/bench_default_line.json 2> $O/bench.err; tail -c 300 $O/bench_default_line.json
+timeout 600 python bench.py --full > $O/bench_default_line.json 2> $O/bench.err; tail -c 300 $O/bench_default_line.json

@@ -12,7 +12,7 @@ shift 3
 cd $R
 export TMPDIR=/tmp
 timeout 600 python -m pytest $T -m gpu -x -q > $O/pytest.log 2>&1; echo "tests rc=$?"; tail -2 $O/pytest.log
-B="python bench.py --no-cpu-baseline --no-extras --steps 150 --warmup 20"
+B="python bench.py --full --no-cpu-baseline --no-extras --steps 150 --warmup 20"
 : > $O/lines.jsonl
 for rep in 1 2 3; do
 for W in ${@:-objects4 static}; do

@@ -13,7 +13,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout ${TEST_TIMEOUT:-1500} python -m pytest tests -m gpu -x -q --durations=12 > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
   tail -4 $O/pytest.log
 fi
-timeout 600 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err; tail -c 600 $O/bench_default_line.json; echo
+timeout 600 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err; tail -c 600 $O/bench_default_line.json; echo
 if [ "${SKIP_LINES:-0}" != "1" ]; then
   : > $O/bench_lines_all_configs.jsonl
   for A in "--workload objects4" "--workload static" "--workload objects8" "--workload big" "--workload big-static" "--workload static --streams 4 --lockstep" "--workload objects4 --streams 3 --lockstep"; do
