@@ -199,6 +199,51 @@ class CoFusion:
         """every segmented frame writes <prefix>Segmentation<tick>.png (labels, rejected superpixels as 0); '' switches it off"""
         self._check(self.lib.cofusion_set_export_segmentation(self.h, str(prefix or "").encode()))
 
+    def render(self, pose=None, intrinsics=None, size=None, near=0.0, far=0.0, background_mode=2, object_mode=4, flags=0,
+               depth=False, labels=False, as_torch=False):
+        """CoFusion::renderScene: every active model drawn into one view (DESIGN.md "Scene rendering").  pose: camera -> world 4x4
+        (None: the current camera), intrinsics (fx, fy, cx, cy) and size (w, h) default to the frame's.  Colour modes and flags as
+        co_fusion_amd.render (GREY .. LABEL; UNSTABLE | WINDOW | PHONG).  Returns rgba u8 [h, w, 4], plus depth f32 [h, w] (0 = empty)
+        and labels u8 [h, w] (255 = empty) when asked for: numpy arrays, or torch tensors on the device with as_torch=True."""
+        from .render import make_view
+        view = None
+        if pose is not None or intrinsics is not None or size is not None or near or far:
+            cur = self.model_info(0)["pose"] if pose is None else pose   # (the background's pose is the camera's)
+            fx, fy, cx, cy = intrinsics if intrinsics is not None else (self.cfg.fx, self.cfg.fy, self.cfg.cx, self.cfg.cy)
+            w, h = size if size is not None else (self.width, self.height)
+            view = make_view(cur, fx, fy, cx, cy, w, h, near, far)
+        w, h = (view.width, view.height) if view is not None else (self.width, self.height)
+        vref = C.byref(view) if view is not None else None
+        if as_torch:
+            r = C.c_void_p(); d = C.c_void_p(); lb = C.c_void_p()
+            self._check(self.lib.cofusion_render_device(self.h, vref, int(background_mode), int(object_mode), int(flags), C.byref(r),
+                                                        C.byref(d), C.byref(lb)))
+            out = [(r, torch.empty((h, w, 4), dtype=torch.uint8, device=self.device))]
+            if depth:
+                out.append((d, torch.empty((h, w), dtype=torch.float32, device=self.device)))
+            if labels:
+                out.append((lb, torch.empty((h, w), dtype=torch.uint8, device=self.device)))
+            ctx = self._ctx()
+            for src, t in out:
+                assert self.abi.cf_memcpy_d2d_async(ctx, C.c_void_p(t.data_ptr()), src, C.c_uint64(t.numel() * t.element_size())) == 0
+            assert self.abi.cf_synchronize(ctx) == 0
+            res = [t for _, t in out]
+        else:
+            rgba = np.empty((h, w, 4), np.uint8)
+            dep = np.empty((h, w), np.float32) if depth else None
+            lab = np.empty((h, w), np.uint8) if labels else None
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+            self._check(self.lib.cofusion_render(self.h, vref, int(background_mode), int(object_mode), int(flags), ptr(rgba), ptr(dep),
+                                                 ptr(lab)))
+            res = [a for a in (rgba, dep, lab) if a is not None]
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def set_export_views(self, prefix, labels=False, normals=False, viewport=False):
+        """after every processed frame write <prefix>Labels<n>.png / Normals<n>.png / Viewport<n>.png (RGBA) from the current camera,
+        <n> as in Segmentation<n>.png (the reference's head-less -el / -en / -ev); all False switches it off"""
+        which = (1 if labels else 0) | (2 if normals else 0) | (4 if viewport else 0)
+        self._check(self.lib.cofusion_set_export_views(self.h, str(prefix or "").encode(), which))
+
     def export_poses(self, prefix):
         """CoFusion::exportPoses: <prefix>poses-<id>.txt per logged model (needs enable_pose_logging=1)"""
         n = self.lib.cofusion_export_poses(self.h, str(prefix).encode())

@@ -837,6 +837,7 @@ CoFusion::CoFusion(const Config& c, cf_ctx* shared, int sequenceIndex)
 CoFusion::~CoFusion()
 {
     pool.reset();
+    releaseRenderer();
     models.clear(); inactiveModels.clear(); newModel.reset(); globalModel.reset();
     cf_free(ctx, depth_dev);
     for (int b = 0; b < 2; b++) { cf_free(ctx, depthFilteredBuf[b]); cf_free(ctx, depthPyr1Buf[b]); cf_free(ctx, depthPyr2Buf[b]); }
@@ -1327,6 +1328,7 @@ void CoFusion::frameEnd()
 
 bool CoFusion::processFrame(const FrameData& frame, const Mat4f* inPose, float weightMultiplier, bool bootstrap)
 {
+    const int frameTick = tick;   // (the number of this frame's Segmentation<n>.png)
     frameBegin(frame, inPose, weightMultiplier, bootstrap);
     if (st.willTrack) { PhaseTimer t(PhaseTimes::Track); trackModels(st.pyr); }
     frameSegment(nullptr);
@@ -1334,6 +1336,7 @@ bool CoFusion::processFrame(const FrameData& frame, const Mat4f* inPose, float w
     frameCollect();
     frameFuse(true, 0);
     frameEnd();
+    if (exportViewsWhich) exportViews(frameTick);   // opt-in (setExportViews): renders after the frame, reads the maps only
     return false;
 }
 

@@ -63,6 +63,8 @@ struct PhaseTimes {
 PhaseTimes& phaseTimes();
 // 8-bit greyscale PNG (zlib), Export.cpp
 bool writePngGray8(const std::string& path, const uint8_t* data, int width, int height);
+// 8-bit RGBA PNG, the same writer (Render.cpp: the exported views)
+bool writePngRGBA8(const std::string& path, const uint8_t* data, int width, int height);
 
 // Model-parallel operation over several GPUs (one process per GPU): every rank runs the same frame loop and takes the
 // same decisions; a model's surfel map and tracker live only on its owner rank, the other ranks keep a data-less
@@ -280,6 +282,21 @@ class CoFusion {
     int exportPoses(const std::string& exportDir);
     // exportSegmentation (CoFusion.cpp:235-240): when set, every segmented frame writes <prefix>Segmentation<tick>.png (8-bit labels)
     void setExportSegmentation(const std::string& prefix) { exportSegmentationPrefix = prefix; }
+    // Scene rendering (Render.cpp over cf_render): every active model drawn into one view, depth-tested against the others, the
+    // background in `backgroundMode`, the objects in `objectMode` (the reference's drawScene(backgroundColor, objectColor)), placed by
+    // Tp = globalPose * modelPose^-1.  view == nullptr: the current camera at the frame intrinsics and size.  The view's flags / tick /
+    // time_delta are replaced by `flags` and this instance's clock.  Outputs are device buffers (cf_render_output); enqueued only.
+    // Single-process operation only (Distributed::active(): throws).
+    void renderScene(const cf_render_view* view, int backgroundMode, int objectMode, int flags, const cf_render_output* outputs, int n);
+    cf_render_view currentView() const;
+    // ... into images this instance owns (valid until the next call): rgba u8x4, depth f32, labels u8 [h*w] of the view's size
+    void renderSceneOwned(const cf_render_view* view, int backgroundMode, int objectMode, int flags, const uint8_t** rgba,
+                          const float** depth, const uint8_t** labels, int* width, int* height);
+    // after every processed frame write <prefix>Labels<n>.png (background in colour, objects in label colour), Normals<n>.png and /
+    // or Viewport<n>.png (colour for all models) from the current camera, <n> the frame's number as in Segmentation<n>.png.
+    // which: 1 labels | 2 normals | 4 viewport; 0 switches it off.  One rasterisation feeds all three.
+    enum { ExportLabels = 1, ExportNormals = 2, ExportViewport = 4 };
+    void setExportViews(const std::string& prefix, int which);
     // the collective of the model-parallel mode (cfg.world > 1); must be set before the first frame
     void setAllreduce(int (*fn)(int64_t*, uint64_t, void*), void* user) { dist.allreduce_i64 = fn; dist.user = user; }
     void setAllreduceDevice(int (*fn)(int64_t*, uint64_t, void*, void*), void* user) { dist.allreduce_dev = fn; dist.user_dev = user; }
@@ -373,6 +390,15 @@ class CoFusion {
     float modelKeepConfThreshold = 0.3f;
     bool enableSmartModelDelete = true;
     std::string exportSegmentationPrefix;
+    // scene rendering: created at first use, grown when a larger view is asked for (Render.cpp)
+    cf_renderer* renderer = nullptr;
+    int renderW = 0, renderH = 0;
+    uint8_t* renderImages = nullptr;   // device: 3 RGBA images | depth f32 | labels u8, each of renderW x renderH
+    std::string exportViewsPrefix;
+    int exportViewsWhich = 0;
+    void ensureRenderer(int w, int h);
+    void releaseRenderer();
+    void exportViews(int frameTick);
     bool useLanes = true;  // per-model auxiliary streams
     std::shared_ptr<EnqueuePool> pool;                      // Config::enqueueThreads helpers
     void modelPasses(Model& model, bool fuse, float weightMultiplier, bool lost);

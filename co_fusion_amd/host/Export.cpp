@@ -18,13 +18,14 @@
 
 namespace cofusion {
 
-// Minimal PNG writer: 8-bit greyscale, one zlib stream, filter type 0 on every row.
-bool writePngGray8(const std::string& path, const uint8_t* data, int width, int height)
+// Minimal PNG writer: 8-bit greyscale (1 channel) or RGBA (4), one zlib stream, filter type 0 on every row.
+static bool writePng8(const std::string& path, const uint8_t* data, int width, int height, int channels)
 {
-    std::vector<uint8_t> raw((size_t)(width + 1) * height);
+    const size_t row = (size_t)width * channels;
+    std::vector<uint8_t> raw((row + 1) * height);
     for (int y = 0; y < height; y++) {
-        raw[(size_t)y * (width + 1)] = 0;
-        memcpy(&raw[(size_t)y * (width + 1) + 1], data + (size_t)y * width, (size_t)width);
+        raw[(size_t)y * (row + 1)] = 0;
+        memcpy(&raw[(size_t)y * (row + 1) + 1], data + (size_t)y * row, row);
     }
     uLongf zlen = compressBound((uLong)raw.size());
     std::vector<uint8_t> z(zlen);
@@ -44,13 +45,15 @@ bool writePngGray8(const std::string& path, const uint8_t* data, int width, int 
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     fwrite(sig, 1, 8, f);
     uint8_t ihdr[13]; be32(ihdr, (uint32_t)width); be32(ihdr + 4, (uint32_t)height);
-    ihdr[8] = 8; ihdr[9] = 0; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8 bit, greyscale, deflate, adaptive filtering, no interlace
+    ihdr[8] = 8; ihdr[9] = channels == 4 ? 6 : 0; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8 bit, greyscale / RGBA, deflate, adaptive filtering, no interlace
     chunk("IHDR", ihdr, 13);
     chunk("IDAT", z.data(), (uint32_t)zlen);
     chunk("IEND", nullptr, 0);
     fclose(f);
     return true;
 }
+bool writePngGray8(const std::string& path, const uint8_t* data, int width, int height) { return writePng8(path, data, width, height, 1); }
+bool writePngRGBA8(const std::string& path, const uint8_t* data, int width, int height) { return writePng8(path, data, width, height, 4); }
 
 static void mul_point(const Mat4f& T, const float p[3], float o[3])
 {

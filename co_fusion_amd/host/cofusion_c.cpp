@@ -265,6 +265,31 @@ int cofusion_set_export_segmentation(cofusion_handle* h, const char* prefix)
     h->cf->setExportSegmentation(prefix ? prefix : "");
     return 0;
 }
+int cofusion_render_device(cofusion_handle* h, const cf_render_view* view, int background_mode, int object_mode, int flags,
+                           const uint8_t** rgba, const float** depth, const uint8_t** labels)
+{
+    if (!h) { g_err = "cofusion_render: no instance"; return -1; }
+    GUARD(h->cf->renderSceneOwned(view, background_mode, object_mode, flags, rgba, depth, labels, nullptr, nullptr));
+    return 0;
+}
+int cofusion_render(cofusion_handle* h, const cf_render_view* view, int background_mode, int object_mode, int flags, uint8_t* rgba,
+                    float* depth, uint8_t* labels)
+{
+    const uint8_t* r = nullptr; const float* d = nullptr; const uint8_t* l = nullptr;
+    if (int rc = cofusion_render_device(h, view, background_mode, object_mode, flags, &r, &d, &l)) return rc;
+    cf_ctx* ctx = h->cf->context();
+    const uint64_t N = view ? (uint64_t)view->width * view->height : (uint64_t)h->cf->cfg.width * h->cf->cfg.height;
+    if (rgba && cf_memcpy_d2h(ctx, rgba, r, N * 4)) { g_err = cf_last_error(ctx); return -1; }
+    if (depth && cf_memcpy_d2h(ctx, depth, d, N * 4)) { g_err = cf_last_error(ctx); return -1; }
+    if (labels && cf_memcpy_d2h(ctx, labels, l, N)) { g_err = cf_last_error(ctx); return -1; }
+    return 0;
+}
+int cofusion_set_export_views(cofusion_handle* h, const char* prefix, int which)
+{
+    if (!h) { g_err = "cofusion_set_export_views: no instance"; return -1; }
+    GUARD(h->cf->setExportViews(prefix ? prefix : "", which));
+    return 0;
+}
 int cofusion_save_ply(cofusion_handle* h, const char* prefix)
 {
     try { const int n = h->cf->savePly(prefix ? prefix : ""); if (n < 0) g_err = "savePly: cannot write"; return n; }

@@ -7,6 +7,7 @@
 #ifndef COFUSION_H_
 #define COFUSION_H_
 #include <stdint.h>
+#include "cofusion_hip.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -138,6 +139,23 @@ int cofusion_save_ply(cofusion_handle *h, const char *export_dir_prefix);
 int cofusion_export_poses(cofusion_handle *h, const char *export_dir_prefix);
 /* exportSegmentation (CoFusion.cpp:235-240): every segmented frame writes <prefix>Segmentation<tick>.png; NULL / "" switches it off */
 int cofusion_set_export_segmentation(cofusion_handle *h, const char *export_dir_prefix);
+
+/* Scene rendering (CoFusion::renderScene over cf_render, include/cofusion_hip.h): every active model drawn into one view as disc
+ * splats, depth-tested against each other; the background in background_mode, the objects in object_mode (CF_RENDER_GREY ..
+ * CF_RENDER_LABEL), objects placed by globalPose * modelPose^-1.  view NULL: the current camera at the frame intrinsics and size;
+ * otherwise its pose (camera -> world), intrinsics, size and near / far are used.  flags: CF_RENDER_UNSTABLE | _WINDOW | _PHONG (the
+ * view's own flags, tick and time_delta are replaced by `flags` and the instance's clock).  Semantics: DESIGN.md "Scene rendering".
+ * Model-parallel / sharded-background operation: an error.
+ * cofusion_render: host outputs, each nullable -- rgba u8x4, depth f32 (0 = empty), labels u8 (model id, 255 = empty), [h*w] each.
+ * cofusion_render_device: the same into images the instance owns (device pointers valid until the next render of this instance). */
+int cofusion_render(cofusion_handle *h, const cf_render_view *view, int background_mode, int object_mode, int flags, uint8_t *rgba,
+                    float *depth, uint8_t *labels);
+int cofusion_render_device(cofusion_handle *h, const cf_render_view *view, int background_mode, int object_mode, int flags,
+                           const uint8_t **rgba, const float **depth, const uint8_t **labels);
+/* the head-less view export (-el / -en / -ev): after every processed frame write <prefix>Labels<n>.png (background in colour, objects
+ * in label colour), <prefix>Normals<n>.png (normals) and / or <prefix>Viewport<n>.png (colour) -- RGBA PNG from the current camera,
+ * <n> the frame's number as in Segmentation<n>.png.  which: 1 labels | 2 normals | 4 viewport; 0 or an empty prefix: off. */
+int cofusion_set_export_views(cofusion_handle *h, const char *export_dir_prefix, int which);
 
 /* .klg RGB-D logs (GUI/Tools/KlgLogReader.cpp:22-87): u16-mm depth raw or zlib, 8-bit x3 colour raw (JPEG frames are
  * rejected: no libjpeg in this build).  depth_m [H*W] metres, rgb [H*W*3]. */

@@ -494,6 +494,65 @@ int cf_set_icp_launch(cf_ctx *ctx, int threads, int pixels_per_thread);
 int cf_set_icp_arith(cf_ctx *ctx, int mode);
 int cf_get_icp_arith(cf_ctx *ctx);
 
+/* ---------------------------------------------------------------- scene rendering ---- */
+/* Draws the surfel maps of several models (background and objects) into one view as disc splats, depth-tested against each
+ * other: what the reference's viewer shows (Model.cpp:274-314, draw_global_surface.*).  Coverage, depth test and colours are
+ * specified exactly in DESIGN.md ("Scene rendering"); in short:
+ *   - a surfel is drawn when conf > conf_threshold, or always with CF_RENDER_UNSTABLE;
+ *   - it covers pixel (px, py) when the ray through (px + 0.5, py + 0.5) meets its plane within `radius` of its centre at view
+ *     depth near < z < far; a surfel with a corner of its quad (half-diagonal radius * sqrt 2) at z <= near is skipped;
+ *   - the nearest z wins; ties go to the earlier item, then to the lower surfel index.
+ * A cf_renderer object owns every buffer of a call (keys, rays, overflow list) for views up to max_w x max_h; nothing is allocated
+ * per call.  cf_render only ENQUEUES, on the context's stream, ordered after every lane of the frame (cf_fork); it reads the
+ * surfel buffers and writes the caller's output images, nothing else. */
+typedef struct cf_renderer cf_renderer;   /* the object; cf_render is the call */
+#define CF_RENDER_MAX_ITEMS 256
+#define CF_RENDER_MAX_COLOUR 8      /* RGBA outputs per call */
+/* view flags */
+#define CF_RENDER_UNSTABLE 1        /* draw surfels at or below their threshold too (in the times colour) */
+#define CF_RENDER_WINDOW 2          /* dim surfels with tick - last_time > time_delta by 0.25 */
+#define CF_RENDER_PHONG 4           /* ambient 0.3 + diffuse + specular (exponent 32), light at the camera centre */
+/* colour modes */
+#define CF_RENDER_GREY 0
+#define CF_RENDER_NORMALS 1         /* world-frame normal */
+#define CF_RENDER_COLOUR 2
+#define CF_RENDER_TIMES 3
+#define CF_RENDER_LABEL 4           /* label palette entry of the item's model id (cf_render_palette) */
+#define CF_RENDER_ITEM_MODE (-1)    /* cf_render_output.mode: each item's own colour_mode */
+/* output kinds */
+#define CF_RENDER_RGBA 0            /* u8x4 [height*width], alpha 255 where covered, all zero where empty */
+#define CF_RENDER_DEPTH 1           /* f32 [height*width] view depth, 0 where empty */
+#define CF_RENDER_LABELS 2          /* u8 [height*width] model id of the winning item, 255 where empty */
+typedef struct {
+    float pose[16];                 /* camera -> world, row-major, rigid (its inverse is taken as [R^T | -R^T t]) */
+    float fx, fy, cx, cy;
+    int width, height;              /* at most the render object's max_w x max_h */
+    float near_z, far_z;            /* 0: the defaults 0.1 / 1000 */
+    int flags;                      /* CF_RENDER_UNSTABLE | CF_RENDER_WINDOW | CF_RENDER_PHONG */
+    int tick, time_delta;           /* the sequence's clock (times colour, window) */
+} cf_render_view;
+typedef struct {
+    const float *surfels;           /* device, `count` surfels of 12 f32 (cf_model_buffer 11) */
+    uint32_t count;
+    float pose[16];                 /* model -> world, row-major: globalPose * modelPose^-1 (identity for the background) */
+    float conf_threshold;
+    int model_id;                   /* 0..254 */
+    int colour_mode;                /* CF_RENDER_GREY .. CF_RENDER_LABEL */
+} cf_render_item;
+typedef struct {
+    void *dst;                      /* device, dense [height*width] elements of the kind */
+    int kind;                       /* CF_RENDER_RGBA / _DEPTH / _LABELS */
+    int mode;                       /* RGBA only: one colour mode for every item, or CF_RENDER_ITEM_MODE */
+} cf_render_output;
+int cf_render_create(cf_ctx *ctx, int max_w, int max_h, cf_renderer **out);
+void cf_render_destroy(cf_renderer *r);
+/* Items are drawn in list order (draw index = surfel index + the counts of the items before it).  At most CF_RENDER_MAX_ITEMS
+ * items, 2^32 - 1 surfels in all, CF_RENDER_MAX_COLOUR RGBA outputs, one depth and one label output. */
+int cf_render(cf_renderer *r, const cf_render_view *view, const cf_render_item *items, int n_items, const cf_render_output *outputs,
+              int n_outputs);
+/* the label palette: RGB8 [256][3]; entry 255 means "none" (black) */
+int cf_render_palette(uint8_t *rgb768);
+
 /* micro-benchmark of the ICP reduction on the state of the last tracking call (level 0..2) */
 int cf_odom_bench_icp(cf_odom *od, int level, int iters, float *avg_us);
 

@@ -4,8 +4,10 @@ does head-less, GUI/MainController.cpp):
 
     python tools/run_klg.py seq.klg out/ [--static] [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240]
                             [--frames N] [--flip-colors] [--export-segmentation]
+                            [--export-labels] [--export-normals] [--export-viewport]
 
-Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png) and prints frames/s."""
+Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png, out/Labels<tick>.png, out/Normals<tick>.png,
+out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s."""
 import argparse
 import os
 import sys
@@ -25,6 +27,9 @@ def main():
     ap.add_argument("--frames", type=int, default=-1)
     ap.add_argument("--flip-colors", action="store_true")
     ap.add_argument("--export-segmentation", action="store_true")
+    ap.add_argument("--export-labels", action="store_true", help="Labels<n>.png: background in colour, objects in label colour (-el)")
+    ap.add_argument("--export-normals", action="store_true", help="Normals<n>.png (-en)")
+    ap.add_argument("--export-viewport", action="store_true", help="Viewport<n>.png: every model in colour (-ev)")
     ap.add_argument("--max-surfels", type=int, default=3072 * 3072)
     a = ap.parse_args()
     from co_fusion_amd import facade, klg
@@ -35,6 +40,8 @@ def main():
                          enable_pose_logging=1)
     if a.export_segmentation and not a.static:
         cf.set_export_segmentation(prefix)
+    if a.export_labels or a.export_normals or a.export_viewport:
+        cf.set_export_views(prefix, labels=a.export_labels, normals=a.export_normals, viewport=a.export_viewport)
     n, t0 = 0, time.perf_counter()
     for ts, depth, rgb in log:
         cf.process_frame(depth, rgb, timestamp=ts)
