@@ -262,6 +262,19 @@ class Context:
     def set_icp_launch(self, threads, ppt):
         self._check(self.lib.cf_set_icp_launch(self.h, threads, ppt))
 
+    def track_batch(self, odoms, poses, rgb_only=False, icp_weight=10.0, pyramid=True, fast_odom=False, so3=True, err_surfaces=None):
+        """cf_odom_track_batch_async: all trackers advance through the Gauss-Newton schedule inside the same launches; nothing is waited
+        for -- Odometry.fetch() of every tracker afterwards.  poses: one 4x4 per tracker; err_surfaces: None or one (nullable) per tracker"""
+        n = len(odoms)
+        keep = [_f(np.asarray(p, np.float32).reshape(16)) for p in poses]
+        pp = (C.POINTER(C.c_float) * max(n, 1))(*[C.cast(k, C.POINTER(C.c_float)) for k in keep])
+        oo = (C.c_void_p * max(n, 1))(*[o.h for o in odoms])
+        ee = None
+        if err_surfaces is not None:
+            ee = (C.c_void_p * max(n, 1))(*[e.data_ptr() if e is not None else None for e in err_surfaces])
+        opts = TrackOpts(int(rgb_only), int(pyramid), int(fast_odom), int(so3), icp_weight)
+        self._check(self.lib.cf_odom_track_batch_async(self.h, oo, n, pp, C.byref(opts), ee))
+
     def set_icp_arith(self, mode):
         """rounding specification of the ICP sums: 0 / "product" (default), 1 / "gram" or 2 / "reference" (the reference's own f32 trees and host loop; include/cofusion_hip.h: cf_set_icp_arith)"""
         self._check(self.lib.cf_set_icp_arith(self.h, {"product": 0, "gram": 1, "reference": 2}.get(mode, mode)))
@@ -332,6 +345,29 @@ class Odometry:
         self.ctx._check(self.ctx.lib.cf_odom_get_incremental_transformation(self.h, t, r, C.byref(opts),
                                                                             _p(err_surface), C.byref(st)))
         return np.array(t, np.float32), np.array(r, np.float32).reshape(3, 3), st
+
+    def fetch(self):
+        """cf_odom_fetch_result of the tracking call Context.track_batch enqueued for this tracker -> (trans, rot, stats)"""
+        t = (C.c_float * 3)(); r = (C.c_float * 9)()
+        st = TrackStats()
+        self.ctx._check(self.ctx.lib.cf_odom_fetch_result(self.h, t, r, C.byref(st)))
+        return np.array(t, np.float32), np.array(r, np.float32).reshape(3, 3), st
+
+    def level0_visited(self):
+        """cf_odom_level0_visited -> (icp_pixels, residual_pixels) of the last fetched tracking call"""
+        a = C.c_uint64(); b = C.c_uint64()
+        self.ctx._check(self.ctx.lib.cf_odom_level0_visited(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_launch_shape(self):
+        """cf_odom_last_launch_shape -> (icp_blocks[3], residual_blocks[3], icp_blocks_err) of the last tracking call"""
+        a = (C.c_int * 3)(); b = (C.c_int * 3)(); e = C.c_int()
+        self.ctx._check(self.ctx.lib.cf_odom_last_launch_shape(self.h, a, b, C.byref(e)))
+        return list(a), list(b), e.value
+
+    def share_frame_maps(self, owner):
+        """cf_odom_share_frame_maps: track against the current-frame pyramids `owner` computed with init_icp"""
+        self.ctx._check(self.ctx.lib.cf_odom_share_frame_maps(self.h, owner.h))
 
     def bench_icp(self, level, iters=200):
         us = C.c_float()

@@ -935,7 +935,9 @@ static int odom_prepare(cf_odom* od, const float pose[16], const cf_track_opts* 
     // reduction projects with the pose of THIS call: the culling is conservative only if the two are the same pose -- which
     // Model::performTracking guarantees (both are the model's pose) and a C-ABI caller tracking from another initial guess does not.
     const float Rt_call[12] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10], pose[3], pose[7], pose[11]};
-    const bool same_pose = memcmp(Rt_call, od->map_pose, sizeof(Rt_call)) == 0;
+    // (compared as VALUES: a -0.0f in one of the two poses is the same pose, and a bitwise comparison switched the culling off for it)
+    bool same_pose = true;
+    for (int i = 0; i < 12; i++) same_pose = same_pose && Rt_call[i] == od->map_pose[i];
     h->aabb_acc = od->aabb; h->cull = (od->use_occ && od->box_valid && od->band_end == 0 && !no_box && same_pose) ? 1 : 0;
     memcpy(h->box_R, od->map_pose, 36); memcpy(h->box_t, od->map_pose + 9, 12);
     h->res_range = (h->cull && rgb) ? od->res_range : nullptr;
@@ -957,6 +959,7 @@ static int odom_prepare(cf_odom* od, const float pose[16], const cf_track_opts* 
     }
     // the accumulators are zero here: dmalloc clears them and every solve leaves them cleared
     od->pending_so3_swap = opts->so3 != 0;
+    od->launch_shape = LaunchShape{};
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -1098,7 +1101,10 @@ int cf_odom_track_batch_async(cf_ctx* ctx, cf_odom* const* ods, int n, const flo
     const bool solve_trace = solve_trace_call >= 0 && solve_trace_seen++ == solve_trace_call;
     if (solve_trace) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); trace_solve_begin(); }
 #endif
-    if (!launch_gn_track(ctx->stream, ctx->icp_launch, states, ctx->d_so3_sync, any_split ? &hook : nullptr, icp_args, rgb_args, n,
+    LaunchShape* shapes[kMaxBatch];
+    for (int m = 0; m < n; m++) shapes[m] = &ods[m]->launch_shape;
+    IcpLaunch launch_cfg = ctx->icp_launch; launch_cfg.shape = shapes;
+    if (!launch_gn_track(ctx->stream, launch_cfg, states, ctx->d_so3_sync, any_split ? &hook : nullptr, icp_args, rgb_args, n,
                          ctx->cfg.width, ctx->cfg.height, so3_here, opts->pyramid != 0, opts->fast_odom != 0, rgb, icp, ctx->gn_mode, prof, h_states,
                          prep_fused ? &prep : nullptr)) {
         ctx->set_error("tracking: the registered collective failed inside the Gauss-Newton loop");
@@ -1305,6 +1311,18 @@ int cf_odom_level0_visited(cf_odom* od, uint64_t* icp_pixels, uint64_t* residual
         if (h->icp) { const CullRuns cr = cull_runs(h->stats.cull_box, 0, ctx->cfg.width, ctx->cfg.height); *icp_pixels = (uint64_t)cr.total * 64 < N ? (uint64_t)cr.total * 64 : N; }
         if (h->rgb && h->res_range && h->res_seen[0] >= 0) { const uint64_t px = (uint64_t)h->res_seen[0] * (uint64_t)(ctx->icp_launch.threads * 4); *residual_pixels = px < N ? px : N; }
     }
+    return CF_OK;
+}
+
+// Workgroups the launcher (launch_icp_kernel_arith) gave this tracker in its last tracking call: host bookkeeping, no device access.
+int cf_odom_last_launch_shape(cf_odom* od, int icp_blocks[3], int residual_blocks[3], int* icp_blocks_err)
+{
+    if (!od) return CF_EINVAL;
+    for (int l = 0; l < CF_NUM_PYRS; l++) {
+        if (icp_blocks) icp_blocks[l] = od->launch_shape.icp[l];
+        if (residual_blocks) residual_blocks[l] = od->launch_shape.res[l];
+    }
+    if (icp_blocks_err) *icp_blocks_err = od->launch_shape.icp_err;
     return CF_OK;
 }
 

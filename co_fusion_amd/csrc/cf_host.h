@@ -135,4 +135,5 @@ struct cf_odom {
     unsigned gn_epoch_seen = 0;      // cf_ctx::gn_mode_epoch of the last tracking call
     bool result_pending = false;     // a tracking call of this tracker is in flight / not fetched: its pinned host state must not be rewritten yet
     int expected_solves = -1;        // Gauss-Newton iterations the pending tracking call enqueued (-1: not checked), against OdomDev::solves
+    cf::LaunchShape launch_shape{};  // cf_odom_last_launch_shape: workgroup counts the launcher gave this tracker in its last tracking call
 };

@@ -185,7 +185,11 @@ inline IDiv make_idiv(int d)
 }
 // Gram form of the ICP sums (cf_set_icp_arith 1, cf_device.h): fraction bits of the fixed-point grid of row entry i (7 = the inlier flag)
 constexpr int kGramBits[8] = {20, 20, 20, 17, 17, 17, 22, 0};
-struct IcpLaunch { int threads; int ppt; int gram; };  // threads per workgroup, pixels per thread, rounding specification of the sums (cf_set_icp_arith)
+// What the launcher gave one tracker in a tracking call (cf_odom_last_launch_shape), host memory: workgroups of its culled-slot mapping
+// per level (0: the whole-image mapping), of the level-0 error-surface iteration apart, and its residual workgroups per level
+struct LaunchShape { int icp[3]; int res[3]; int icp_err; };
+struct IcpLaunch { int threads; int ppt; int gram;   // threads per workgroup, pixels per thread, rounding specification of the sums (cf_set_icp_arith)
+                   LaunchShape* const* shape = nullptr; };  // nullable, [n]: where launch_icp_kernel_arith records what it decided (a few ints per launch)
 
 // stand-alone steps (C-ABI parity with icpStep / computeRgbResidual / rgbStep / so3Step) run the same
 // kernels on a scratch OdomDev prepared by cabi.cpp.

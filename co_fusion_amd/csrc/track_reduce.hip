@@ -1948,10 +1948,21 @@ static void launch_icp_kernel_arith(hipStream_t s, IcpLaunch cfg, const IcpArgs&
     }
     // residual workgroups: one per record slot of the level, or the caller's RgbModelArgs::res_blocks (culled trackers: the slots between
     // the first and the last candidate the previous call saw, residual_blocks_for)
+    int res_compact[kMaxBatch] = {};   // (cf_odom_last_launch_shape: the caller's count where it was taken, 0 where the tracker got one workgroup per slot)
     for (int m = 0; m < n && n_res_blocks > 0; m++) {
         RgbModelArgs& rm = ra.m[m];
         if (!ra.compact || !rm.res_range || rm.res_blocks <= 0 || rm.res_blocks > n_res_blocks) rm.res_blocks = n_res_blocks;
+        else res_compact[m] = rm.res_blocks;
         if (!ra.compact) rm.res_range = nullptr;
+    }
+    if (cfg.shape) {   // cf_odom_last_launch_shape: what was just decided, per tracker (host ints)
+        const int L = 2 - args.occ_shift;
+        for (int m = 0; m < n; m++) {
+            LaunchShape* sh = cfg.shape[m];
+            if (!sh || L < 0 || L > 2) continue;
+            if (args.flags & 1) sh->icp_err = args.m[m].box_blocks; else sh->icp[L] = args.m[m].box_blocks;
+            sh->res[L] = res_compact[m];
+        }
     }
     // ORDER OF THE SLOTS = order of dispatch: the culled trackers' runs (the longest chain of dependent round trips: box, depth interval,
     // planes, occupancy, gather), the unculled ICP reductions, then the residual passes.  Seven orders were measured in round 5 (longest work

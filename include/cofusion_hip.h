@@ -257,6 +257,17 @@ int cf_odom_get_covariance(const cf_track_stats *stats, double cov[36]);
  * runs inside its final screen box and the record slots between its first and last RGB candidate (the whole image for a tracker
  * that is not culled) -- the physical byte count of a roofline figure, as opposed to SURVEY 8(d)'s every-pixel-to-every-tracker */
 int cf_odom_level0_visited(cf_odom *od, uint64_t *icp_pixels, uint64_t *residual_pixels);
+/* Workgroups the launcher gave this tracker in its LAST tracking call (host bookkeeping, readable as soon as the call returned), per
+ * pyramid level.  icp_blocks[l] > 0: the ICP reduction of level l ran on the culled-slot mapping -- that many workgroups dealt the
+ * 64-pixel runs of the tracker's screen box, sized from the box the previous fetched call ended with --; 0: one workgroup per run of the
+ * whole image (no culling, no hint yet, Gram form, row band, or the level did not run).  The LAST level-0 iteration, which also writes
+ * the error surfaces, is reported apart in *icp_blocks_err: it keeps the culled-slot mapping only when a culled tracker of the batch
+ * has an error surface (written aside then); otherwise every tracker of that one launch runs on the whole-image mapping.
+ * residual_blocks[l] > 0: the tracker's residual pass ran on that many workgroups over the record slots between its first and last
+ * candidate, sized from the slots the previous fetched call needed; 0: one workgroup per slot of the level (no culling, no count from a
+ * previous call, a count as large as the level, or no RGB term).  It is the figure of the level's LAST launch -- at level 0 the
+ * error-surface iteration, whose residual pass is sized like every other's.  Any of the three pointers may be NULL. */
+int cf_odom_last_launch_shape(cf_odom *od, int icp_blocks[3], int residual_blocks[3], int *icp_blocks_err);
 /* test access to internal device pyramids (same `which` numbering as the oracle's orc_odom_buffer) */
 /* share the frame-wide current vertex/normal pyramids between models (all models track the same frame,
  * cudafuncs.cu:119); pass NULL arrays to return to the odom-private maps written by cf_odom_init_icp */
