@@ -299,6 +299,17 @@ class CoFusion:
         """CoFusion::getLost: the camera is lost (option reloc=1)"""
         return bool(self.lib.cofusion_is_lost(self.h))
 
+    def set_relocalisation(self, on=True, n_ferns=500, fern_threshold=0.3095, photo_threshold=115.0, min_age=300, seed=0, capacity=1024):
+        """The recovery half of reloc=1 (cofusion_set_relocalisation): a fern keyframe database built from the tracked frames, asked for
+        a keyframe while the camera is lost.  Defaults are the reference's."""
+        self._check(self.lib.cofusion_set_relocalisation(self.h, int(bool(on)), int(n_ferns), C.c_float(fern_threshold), C.c_float(photo_threshold),
+                                                         int(min_age), C.c_uint64(seed), int(capacity)))
+
+    def reloc_stats(self):
+        k = C.c_int(); c = C.c_int(); r = C.c_int(); f = C.c_int()
+        self._check(self.lib.cofusion_reloc_stats(self.h, C.byref(k), C.byref(c), C.byref(r), C.byref(f)))
+        return dict(keyframes=k.value, last_closest=c.value, recoveries=r.value, database_full=bool(f.value))
+
     def model_info(self, index):
         mid = C.c_uint(); cnt = C.c_uint(); conf = C.c_float(); pose = (C.c_float * 16)()
         self._check(self.lib.cofusion_model_info(self.h, index, C.byref(mid), C.byref(cnt), pose, C.byref(conf)))

@@ -838,6 +838,7 @@ CoFusion::~CoFusion()
 {
     pool.reset();
     releaseRenderer();
+    if (ferns) cf_ferns_destroy(ferns);
     models.clear(); inactiveModels.clear(); newModel.reset(); globalModel.reset();
     cf_free(ctx, depth_dev);
     for (int b = 0; b < 2; b++) { cf_free(ctx, depthFilteredBuf[b]); cf_free(ctx, depthPyr1Buf[b]); cf_free(ctx, depthPyr2Buf[b]); }
@@ -1215,9 +1216,16 @@ void CoFusion::frameCollect()
                 if (!trackingOk) {
                     if (++trackingCount > 10) lost = true;
                 } else trackingCount = 0;
+            } else if (lastFrameRecovery) {  // :321-337: the frame after an accepted keyframe decides whether the camera is back
+                double cov[36];
+                check(ctx, cf_odom_get_covariance(&gs, cov), "cf_odom_get_covariance");
+                for (int i = 0; i < 6; i++)
+                    if (cov[i * 6 + i] > 1e-04) { trackingOk = false; break; }
+                if (trackingOk) { lost = false; trackingCount = 0; recoveries++; }
+                lastFrameRecovery = false;
             }
-            // (lastFrameRecovery, :321-337, is only ever set by the fern database, :365-367 -- closeLoops is off in Co-Fusion and the
-            // database out of scope: a lost camera stays lost)
+            // (lastFrameRecovery is only ever set by the fern database, :365-367: see setRelocalisation / fernsAfterPredict -- without
+            // it a lost camera stays lost)
         }
 
         if (cfg.enableMultipleModels) {
@@ -1335,9 +1343,62 @@ bool CoFusion::processFrame(const FrameData& frame, const Mat4f* inPose, float w
     framePreIndex();
     frameCollect();
     frameFuse(true, 0);
+    if (ferns) fernsAfterPredict();
     frameEnd();
     if (exportViewsWhich) exportViews(frameTick);   // opt-in (setExportViews): renders after the frame, reads the maps only
     return false;
+}
+
+void CoFusion::setRelocalisation(bool on, int nFerns, float fernThresh, float photoThresh, int minAge, uint64_t seed, int capacity)
+{
+    if (on && !cfg.reloc) throw std::runtime_error("setRelocalisation: needs Config::reloc (the failure detection that declares the camera lost)");
+    if (on && dist.world > 1) throw std::runtime_error("setRelocalisation: a single-GPU option, like reloc");
+    if (on && !ownsCtx) throw std::runtime_error("setRelocalisation: not available for a sequence of a lock-step group");
+    if (ferns) { cf_ferns_destroy(ferns); ferns = nullptr; }
+    lastFrameRecovery = false; fernLastClosest = -1; recoveries = 0;   // the statistics belong to the database
+    if (!on) return;
+    cf_ferns_config fc{};
+    fc.n_ferns = nFerns; fc.capacity = capacity; fc.max_depth_mm = (int)(cfg.depthCutoff * 1000.0f); fc.photo_threshold = photoThresh;
+    check(ctx, cf_ferns_create(ctx, &fc, nullptr, seed, &ferns), "cf_ferns_create");
+    fernThreshold = fernThresh; fernMinAge = minAge;
+}
+
+void CoFusion::relocStats(int* keyframes, int* lastClosest, int* recoveriesOut, int* databaseFull)
+{
+    int count = 0, full = 0;
+    if (ferns) check(ctx, cf_ferns_count(ferns, &count, &full), "cf_ferns_count");
+    if (keyframes) *keyframes = count;
+    if (lastClosest) *lastClosest = fernLastClosest;
+    if (recoveriesOut) *recoveriesOut = recoveries;
+    if (databaseFull) *databaseFull = full;
+}
+
+// The seam of CoFusion.cpp:349-367 (and ElasticFusion's processFerns, commented out at CoFusion.cpp:496), after the end-of-frame
+// prediction and fill-in.  Tracked: the background's fill-in maps are offered to the database, three launches, no host wait.  Lost:
+// the maps (the frame's own geometry then: performFillIn passes it through) are encoded and Ferns::findFrame runs; an accepted keyframe
+// overrides the pose, the prediction is redone from it (the reference predicts again at the end of its frame, :533), and the next frame's
+// covariance check (frameCollect) decides.
+void CoFusion::fernsAfterPredict()
+{
+    Model& g = *globalModel;
+    const float* v = static_cast<const float*>(mbuf(ctx, g.handle(), 8));
+    const float* n = static_cast<const float*>(mbuf(ctx, g.handle(), 9));
+    const uint8_t* img = static_cast<const uint8_t*>(mbuf(ctx, g.handle(), 10));
+    if (!lost) {
+        check(ctx, cf_ferns_add_async(ferns, v, n, img, g.getPose().m, tick, fernThreshold), "cf_ferns_add_async");
+        return;
+    }
+    lastFrameRecovery = false;   // :352
+    cf_ferns_result res{};
+    check(ctx, cf_ferns_encode(ferns, v, n, img), "cf_ferns_encode");
+    check(ctx, cf_ferns_relocalise(ferns, g.getPose().m, tick, fernMinAge, 1, &res), "cf_ferns_relocalise");
+    fernLastClosest = res.accepted ? res.keyframe : -1;   // Ferns::lastClosest
+    if (!res.accepted) return;
+    Mat4f p;
+    for (int i = 0; i < 16; i++) p.m[i] = res.pose[i];
+    g.overridePose(p);
+    lastFrameRecovery = true;
+    fuseAndPredict(false, st.weightMultiplier, lost, true, 0);
 }
 
 // The first index maps of the surfel chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) enqueued BEHIND the

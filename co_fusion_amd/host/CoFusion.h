@@ -259,7 +259,7 @@ class CoFusion {
         bool colocateBackground = false;
         // CoFusion's `reloc` constructor argument (CoFusion.h:47, -rl on the command line): the failure detection of the frame loop --
         // a frame whose background ICP error / pose covariance is out of bounds is not fused, and after ten such frames the camera is
-        // `lost`: no fusion, the clock stops (CoFusion.cpp:225, 301-338, 463, 495).  The fern-based recovery is out of scope.
+        // `lost`: no fusion, the clock stops (CoFusion.cpp:225, 301-338, 463, 495).  The fern-based recovery is CoFusion::setRelocalisation.
         bool reloc = false;
         // the index maps of the tracked models rasterised before the frame's host wait, with the poses on the device (framePreIndex)
         bool earlyIndexMaps = true;
@@ -313,6 +313,15 @@ class CoFusion {
     const Mat4f& getCurrPose() const { return globalModel->getPose(); }
     int getTick() const { return tick; }
     bool getLost() const { return lost; }  // CoFusion::getLost (CoFusion.h:183-185): the camera is lost (Config::reloc)
+    // The recovery half of `reloc`: ElasticFusion's fern keyframe database (cf_ferns).  Off by default; with it off the
+    // frame loop is what it was, launch for launch.  On: every tracked frame offers the background's fill-in maps to the database
+    // (Ferns::addFrame, no host wait), a lost camera asks it for a keyframe after the end-of-frame prediction (Ferns::findFrame) and,
+    // on acceptance, continues from the recovered pose (CoFusion.cpp:349-367, 321-337).  Needs Config::reloc; single process, not a
+    // sequence of a lock-step group.  Calling it again replaces the database.
+    void setRelocalisation(bool on, int nFerns = 500, float fernThreshold = 0.3095f, float photoThreshold = 115.0f, int minAge = 300,
+                           uint64_t seed = 0, int capacity = 1024);
+    void relocStats(int* keyframes, int* lastClosest, int* recoveries, int* databaseFull);
+    bool isGroupSequence() const { return !ownsCtx; }
     const uint8_t* maskDevice() const { return mask_dev; }
     Segmentation& segmentation() { return *labelGenerator; }
     cf_ctx* context() { return ctx; }
@@ -375,6 +384,11 @@ class CoFusion {
     bool capReported = false;  // the model cap suppressed a spawn and said so
     bool lost = false;          // CoFusion.h:362 (reloc)
     int trackingCount = 0;      // CoFusion.h:364
+    cf_ferns* ferns = nullptr;  // setRelocalisation
+    float fernThreshold = 0.3095f;
+    int fernMinAge = 300, fernLastClosest = -1, recoveries = 0;
+    bool lastFrameRecovery = false;   // CoFusion.h:363
+    void fernsAfterPredict();
     // device frame buffers (CoFusion::textures)
     // filtered depth + its pyramid are double buffered: the filter of frame t+1 runs on an auxiliary stream while the fusion
     // passes of frame t still read frame t's filtered depth (processFrame)

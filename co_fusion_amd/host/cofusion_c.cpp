@@ -102,6 +102,20 @@ int cofusion_process_frame_device(cofusion_handle* h, int64_t ts, const float* d
 int cofusion_num_models(cofusion_handle* h) { return (int)h->cf->getModels().size(); }
 int cofusion_tick(cofusion_handle* h) { return h->cf->getTick(); }
 int cofusion_is_lost(cofusion_handle* h) { return h && h->cf->getLost() ? 1 : 0; }
+int cofusion_set_relocalisation(cofusion_handle* h, int on, int n_ferns, float fern_threshold, float photo_threshold, int min_age, uint64_t seed, int capacity)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->borrowed) { g_err = "relocalisation is not available for a sequence of a lock-step group"; return -1; }
+    GUARD(h->cf->setRelocalisation(on != 0, n_ferns > 0 ? n_ferns : 500, fern_threshold,
+                                   photo_threshold > 0 ? photo_threshold : 115.0f, min_age >= 0 ? min_age : 300, seed, capacity > 0 ? capacity : 1024));
+    return 0;
+}
+int cofusion_reloc_stats(cofusion_handle* h, int* keyframes, int* last_closest, int* recoveries, int* database_full)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    GUARD(h->cf->relocStats(keyframes, last_closest, recoveries, database_full));
+    return 0;
+}
 
 static Model* model_at(cofusion_handle* h, int index)
 {

@@ -32,6 +32,8 @@ SYMBOLS = [
     "cf_depth_pyramid", "cf_set_icp_launch", "cf_set_icp_arith", "cf_get_icp_arith", "cf_set_gn_mode", "cf_profile_enable", "cf_profile_read", "cf_odom_bench_icp", "cf_odom_level0_visited", "cf_odom_last_launch_shape",
     "cf_rccl_unique_id", "cf_rccl_init", "cf_rccl_allreduce", "cf_rccl_broadcast", "cf_rccl_info", "cf_rccl_destroy",
     "cf_render_create", "cf_render_destroy", "cf_render", "cf_render_palette",
+    "cf_ferns_table", "cf_ferns_create", "cf_ferns_destroy", "cf_ferns_get_table", "cf_ferns_encode", "cf_ferns_search", "cf_ferns_append", "cf_ferns_add_async",
+    "cf_ferns_relocalise", "cf_ferns_count", "cf_ferns_download", "cf_ferns_last_search",
 ]
 
 
@@ -56,7 +58,7 @@ HOST_SYMBOLS = [
     "cofusion_model_download", "cofusion_model_icp_stats", "cofusion_model_cull_box", "cofusion_model_level0_visited", "cofusion_model_tracking_inputs", "cofusion_mask_device", "cofusion_context", "cofusion_set_crf",
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
-    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views",
+    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_relocalisation", "cofusion_reloc_stats",
 ]
 _host = None
 

@@ -44,7 +44,7 @@ typedef struct {
     int reloc;                  /* CoFusion's `reloc` constructor argument (CoFusion.h:47): failure detection of the frame loop -- frames
                                  * with a background ICP error >= 1e-4 or a pose-covariance diagonal entry > 1e-4 are not fused, after
                                  * more than ten in a row the camera is lost (no fusion, the clock stops; CoFusion.cpp:225,301-338).
-                                 * cofusion_is_lost reports it.  Default 0. */
+                                 * cofusion_is_lost reports it; cofusion_set_relocalisation adds the recovery.  Default 0. */
     int early_index_maps;       /* 1 (default): the index maps of the tracked models are rasterised with the poses the trackers left ON THE
                                  * DEVICE, behind the segmentation and before the frame's host wait (cf_models_preindex), so the GPU works
                                  * while the host reads poses and decisions; 0: with the rest of the surfel chain, after the wait.  Results are
@@ -67,6 +67,20 @@ int cofusion_num_models(cofusion_handle *h);
 int cofusion_tick(cofusion_handle *h);
 /* CoFusion::getLost (CoFusion.h:183-185): 1 while the camera is lost (cofusion_config.reloc) */
 int cofusion_is_lost(cofusion_handle *h);
+/* The recovery half of `reloc` (ElasticFusion's fern keyframe relocaliser, CoFusion.cpp:349-367 and 321-337; cf_ferns in
+ * cofusion_hip.h): with on = 1 every tracked frame offers the background's fill-in maps to a device-resident keyframe database (no host
+ * wait), a lost camera asks it for a keyframe and, when one is accepted, continues from the recovered pose; the next frame's covariance
+ * check ends the lost state.  Reference values: 500 ferns, fernThresh 0.3095, photoThresh 115, min age 300 ticks; n_ferns <= 0,
+ * photo_threshold <= 0, min_age < 0 and capacity <= 0 select them (capacity: 1024 keyframes).  fern_threshold is taken as given: a
+ * frame becomes a keyframe when its dissimilarity to every keyframe is greater, so a negative value keeps every frame.  The table is
+ * generated from `seed`.  Calling it again replaces the database and resets the statistics.
+ * Needs cfg.reloc = 1 and world == 1; refused for a sequence handle of a lock-step group.  Off (the default): the frame loop is
+ * unchanged.  The frame width must be a multiple of 128, the height of 32. */
+int cofusion_set_relocalisation(cofusion_handle *h, int on, int n_ferns, float fern_threshold, float photo_threshold, int min_age,
+                                uint64_t seed, int capacity);
+/* keyframes in the database, the keyframe the last relocalisation accepted (-1: none), lost -> tracked transitions so far, 1 when an
+ * append was dropped because the database is full; each nullable.  Waits for the stream. */
+int cofusion_reloc_stats(cofusion_handle *h, int *keyframes, int *last_closest, int *recoveries, int *database_full);
 /* per model (list order, 0 = background): id, surfel count, pose T(model <- camera), confidence threshold */
 int cofusion_model_info(cofusion_handle *h, int index, unsigned *id, unsigned *count, float pose[16], float *conf_threshold);
 int cofusion_model_download(cofusion_handle *h, int index, float *surfels, uint32_t capacity, uint32_t *count);

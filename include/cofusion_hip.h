@@ -564,6 +564,74 @@ int cf_render(cf_renderer *r, const cf_render_view *view, const cf_render_item *
 /* the label palette: RGB8 [256][3]; entry 255 means "none" (black) */
 int cf_render_palette(uint8_t *rgb768);
 
+/* ------------------------------------------------ keyframe relocalisation (Core/Ferns.h) ---- */
+/* ElasticFusion's random-fern keyframe database, device resident.  A cf_ferns object belongs to a context of the FULL
+ * frame size and works on 8x reduced maps (nearest sampling at source texel (8x + 4, 8y + 4)).  Restrictions, CF_EINVAL otherwise:
+ * the frame width is a multiple of 128 and the height a multiple of 32 (the reduced frame must itself be a valid cf_create size:
+ * the object owns a second context and a tracker at (W/8) x (H/8), intrinsics divided by 8, enqueueing on the parent's stream);
+ * n_ferns in 1..CF_FERNS_MAX; capacity >= 1; max_depth_mm >= 400.  Everything is allocated at creation: per keyframe of capacity
+ * round_up(n_ferns, 16) + 27 * (W/8) * (H/8) + 76 bytes. */
+#define CF_FERNS_MAX 2048
+typedef struct cf_ferns cf_ferns;
+typedef struct {
+    int32_t x, y;        /* position in the reduced image: 0..W/8-1, 0..H/8-1 */
+    int32_t r, g, b;     /* colour thresholds 0..255 */
+    int32_t d;           /* depth threshold in millimetres, 400..max_depth_mm */
+} cf_fern;               /* Ferns::Fern (Ferns.h) */
+typedef struct {
+    int n_ferns;            /* reference: 500 */
+    int capacity;           /* keyframes */
+    int max_depth_mm;       /* Ferns::maxDepth: depth cut-off in millimetres */
+    float photo_threshold;  /* Ferns::photoThresh, reference: 115 */
+} cf_ferns_config;
+typedef struct {
+    int accepted;           /* all three acceptance tests of Ferns.cpp:237 passed */
+    int keyframe;           /* the match (lowest dissimilarity among keyframes older than min_age), -1: none */
+    float dissimilarity;    /* of the match; FLT_MAX: none */
+    float overlap;          /* blockHDAware of the current codes and the match's (Ferns.cpp:321-336); the tracker runs when > 0.3 */
+    float pose[16];         /* the tracker's estimate, row-major (identity when the tracker did not run) */
+    float icp_error, icp_count;
+    int icp_ran;            /* 1: the tracker ran (pose, icp_*, photo_* are results) */
+    int photo_count;        /* correspondences of the photometric check */
+    double photo_error;     /* Ferns::photometricCheck in f64; +inf with no correspondence */
+} cf_ferns_result;
+/* host helper: the table cf_ferns_create generates from `seed` when none is given (splitmix64, six draws per fern in the order
+ * x, y, r, g, b, d, each lo + draw % (hi - lo + 1): DESIGN.md 4.8) */
+int cf_ferns_table(uint64_t seed, int n_ferns, int reduced_width, int reduced_height, int max_depth_mm, cf_fern *out);
+/* table: n_ferns entries (host) or NULL to generate one from `seed` */
+int cf_ferns_create(cf_ctx *ctx, const cf_ferns_config *cfg, const cf_fern *table, uint64_t seed, cf_ferns **out);
+void cf_ferns_destroy(cf_ferns *f);
+int cf_ferns_get_table(const cf_ferns *f, cf_fern *out /* n_ferns */);
+/* Fill the CURRENT slot from a model's fill-in maps (device, full size: f32x4, f32x4, rgba8), ONE launch: reduced vertex / normal
+ * maps in the planar layout (z == 0 -> NaN, as cf_copy_maps), reduced rgb, the fern codes of Ferns.cpp:89-109 (255 when the reduced
+ * vertex z is not > 0, else (R>r)<<3 | (G>g)<<2 | (B>b)<<1 | (int(z*1000.0f) > d)) and the count of good codes.  Enqueues only. */
+int cf_ferns_encode(cf_ferns *f, const float *vertex4, const float *normal4, const uint8_t *rgba);
+/* Scan the database for the current slot, ONE launch: co[k] = #{i: q[i] != 255 and q[i] == c[k][i]}, dissimilarity
+ * (min(good_q, good_k) - co[k]) / min(good_q, good_k) in f32, (a) its minimum over all keyframes and (b) over the keyframes with
+ * time - srcTime > min_age, lowest index on ties (Ferns.cpp:111-127, 184-196).  Enqueues only; cf_ferns_last_search reads. */
+int cf_ferns_search(cf_ferns *f, int time, int min_age);
+/* Conditional append of the current slot after a search (Ferns.cpp:127: (minimum > threshold || empty) && good > 0), decided and
+ * done on the device, ONE launch; at count == capacity nothing is appended and the `full` flag is raised.  Enqueues only. */
+int cf_ferns_append(cf_ferns *f, const float pose[16], int src_time, float threshold);
+/* Ferns::addFrame: encode -> search -> append, three launches, no host wait (it runs in every tracked frame) */
+int cf_ferns_add_async(cf_ferns *f, const float *vertex4, const float *normal4, const uint8_t *rgba, const float pose[16], int src_time,
+                       float threshold);
+/* Ferns::findFrame (Ferns.cpp:144-262) for the current slot (cf_ferns_encode first); synchronous.  Search; if a match exists and
+ * its overlap is > 0.3: ICP of the current reduced maps against the keyframe's stored maps on the small tracker (model side
+ * cf_odom_init_icp_model with the keyframe's pose, frame side cf_odom_bind_frame_maps, options rgb_only 0, icp_weight 100, pyramid 0,
+ * fast_odom 0, so3 0, starting from the keyframe's pose), then the photometric check; accepted when icp_error < 3e-4, icp_count >
+ * (lost ? 1400 : 2400) and photo_error < photo_threshold.  curr_pose is unused (it only feeds loop-closure constraints). */
+int cf_ferns_relocalise(cf_ferns *f, const float curr_pose[16], int time, int min_age, int lost, cf_ferns_result *result);
+/* the getters wait for the stream */
+int cf_ferns_count(cf_ferns *f, int *count, int *full);
+/* test access.  id = -1: the current slot (pose identity, time 0).  Host outputs, each nullable: codes u8 [n_ferns], good count,
+ * pose, time, reduced vertex / normal maps planar f32 [3 * H/8 * W/8], reduced rgb u8 [H/8 * W/8 * 3] */
+int cf_ferns_download(cf_ferns *f, int id, uint8_t *codes, int *good, float pose[16], int *time, float *vmap, float *nmap, uint8_t *rgb);
+/* results of the last search: co[0..searched) (co_capacity entries available), the keyframes it scanned, the two minima (FLT_MAX:
+ * none), the match (-1: none) and the decision of the last append; each nullable */
+int cf_ferns_last_search(cf_ferns *f, int32_t *co_host, int co_capacity, int *searched, float *min_all, float *min_match, int *match_id,
+                         int *appended);
+
 /* micro-benchmark of the ICP reduction on the state of the last tracking call (level 0..2) */
 int cf_odom_bench_icp(cf_odom *od, int level, int iters, float *avg_us);
 

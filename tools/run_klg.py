@@ -31,13 +31,20 @@ def main():
     ap.add_argument("--export-normals", action="store_true", help="Normals<n>.png (-en)")
     ap.add_argument("--export-viewport", action="store_true", help="Viewport<n>.png: every model in colour (-ev)")
     ap.add_argument("--max-surfels", type=int, default=3072 * 3072)
+    ap.add_argument("--relocalise", action="store_true", help="failure detection (-rl) with the fern keyframe database: a lost camera recovers")
+    ap.add_argument("--fern-threshold", type=float, default=0.3095, help="a frame becomes a keyframe when it differs more than this from every keyframe")
+    ap.add_argument("--photo-threshold", type=float, default=115.0)
+    ap.add_argument("--fern-min-age", type=int, default=300, help="ticks a keyframe must be old to be matched")
+    ap.add_argument("--fern-seed", type=int, default=0)
     a = ap.parse_args()
     from co_fusion_amd import facade, klg
     os.makedirs(a.outdir, exist_ok=True)
     prefix = a.outdir.rstrip("/") + "/"
     log = klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
     cf = facade.CoFusion(a.width, a.height, a.fx, a.fy, a.cx, a.cy, max_surfels=a.max_surfels, enable_multiple_models=int(not a.static),
-                         enable_pose_logging=1)
+                         enable_pose_logging=1, reloc=int(a.relocalise))
+    if a.relocalise:
+        cf.set_relocalisation(True, fern_threshold=a.fern_threshold, photo_threshold=a.photo_threshold, min_age=a.fern_min_age, seed=a.fern_seed)
     if a.export_segmentation and not a.static:
         cf.set_export_segmentation(prefix)
     if a.export_labels or a.export_normals or a.export_viewport:
@@ -50,6 +57,8 @@ def main():
             break
     dt = time.perf_counter() - t0
     print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s incl. log decoding and upload), {cf.num_models} active models")
+    if a.relocalise:
+        print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
     print(f"exported {cf.export_poses(prefix)} pose file(s), {cf.save_ply(prefix)} PLY cloud(s) to {prefix}")
     cf.close()
 
