@@ -262,6 +262,9 @@ class Context:
     def set_icp_launch(self, threads, ppt):
         self._check(self.lib.cf_set_icp_launch(self.h, threads, ppt))
 
+    def set_gn_mode(self, mode):
+        self._check(self.lib.cf_set_gn_mode(self.h, int(mode)))
+
     def track_batch(self, odoms, poses, rgb_only=False, icp_weight=10.0, pyramid=True, fast_odom=False, so3=True, err_surfaces=None):
         """cf_odom_track_batch_async: all trackers advance through the Gauss-Newton schedule inside the same launches; nothing is waited
         for -- Odometry.fetch() of every tracker afterwards.  poses: one 4x4 per tracker; err_surfaces: None or one (nullable) per tracker"""

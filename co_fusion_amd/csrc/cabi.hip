@@ -925,7 +925,7 @@ static int odom_prepare(cf_odom* od, const float pose[16], const cf_track_opts* 
 #else
     constexpr bool no_box = false;
 #endif
-    // the screen box the previous tracking call ended with sizes this call's launches (launch_icp_kernel_arith); the pinned host state
+    // the screen box the previous tracking call ended with sizes this call's launches (launch_icp_rgbres); the pinned host state
     // holds it once that call's results were fetched
     if (h->cull && !od->result_pending) memcpy(od->box_hint, h->stats.cull_box, sizeof(od->box_hint));
     else od->box_hint[0] = kNoBoxHint;
@@ -1314,7 +1314,7 @@ int cf_odom_level0_visited(cf_odom* od, uint64_t* icp_pixels, uint64_t* residual
     return CF_OK;
 }
 
-// Workgroups the launcher (launch_icp_kernel_arith) gave this tracker in its last tracking call: host bookkeeping, no device access.
+// Workgroups the launcher (launch_icp_rgbres) gave this tracker in its last tracking call: host bookkeeping, no device access.
 int cf_odom_last_launch_shape(cf_odom* od, int icp_blocks[3], int residual_blocks[3], int* icp_blocks_err)
 {
     if (!od) return CF_EINVAL;

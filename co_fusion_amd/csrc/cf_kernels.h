@@ -189,7 +189,7 @@ constexpr int kGramBits[8] = {20, 20, 20, 17, 17, 17, 22, 0};
 // per level (0: the whole-image mapping), of the level-0 error-surface iteration apart, and its residual workgroups per level
 struct LaunchShape { int icp[3]; int res[3]; int icp_err; };
 struct IcpLaunch { int threads; int ppt; int gram;   // threads per workgroup, pixels per thread, rounding specification of the sums (cf_set_icp_arith)
-                   LaunchShape* const* shape = nullptr; };  // nullable, [n]: where launch_icp_kernel_arith records what it decided (a few ints per launch)
+                   LaunchShape* const* shape = nullptr; };  // nullable, [n]: where launch_icp_rgbres records what it decided (a few ints per launch)
 
 // stand-alone steps (C-ABI parity with icpStep / computeRgbResidual / rgbStep / so3Step) run the same
 // kernels on a scratch OdomDev prepared by cabi.cpp.

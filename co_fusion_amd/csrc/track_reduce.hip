@@ -16,142 +16,21 @@
 //    blockIdx -> pixel-range mapping is XCD-aware: workgroup b runs on XCD b%8, and XCD x owns
 //    the x-th horizontal band of the image, so the gathered model-map rows stay in that XCD's
 //    4 MiB L2 across the 19 iterations of a frame.
+//
+// One translation unit, five files (the headers are included by this file only):
+//   track_sums_dev.h      the fixed-point sum primitives: SE(3) products, LDS accumulators, commits, reads of the totals
+//   track_reduce.hip      the {ICP reduction || RGB residual} launch, the error surfaces, the candidate mask, the XCD probe; every launcher
+//   track_so3_dev.h       the SO(3) pre-alignment
+//   track_solve_dev.h     the per-iteration Gauss-Newton solve
+//   track_rgb_step_dev.h  the RGB step in its three variants (cf_set_gn_mode 0 / 1 / 2)
 #include "cf_device.h"
 #include "cf_kernels.h"
 #include "track_prep_dev.h"
+#include "track_sums_dev.h"
 
 namespace cf {
 
-__device__ __forceinline__ cf_cam cam_level(cf_cam c, int level)
-{  // CameraModel::operator(), types.cuh:94-98
-    const int div = 1 << level;
-    return cf_cam{c.fx / div, c.fy / div, c.cx / div, c.cy / div};
-}
-
 __device__ __forceinline__ int idiv(int n, IDiv d) { return (int)(__umulhi((unsigned)n, d.M) >> d.s); }  // n / cols, cf_kernels.h: make_idiv
-
-__device__ __forceinline__ float clamp_row(float v, float lim) { return fminf(fmaxf(v, -lim), lim); }
-
-// acc[k] += RNE(row_i*row_j*2^F) for the 27 upper-triangular SE3 products + residual
-template <int F>
-__device__ __forceinline__ void se3_accumulate(const float (&row)[7], unsigned long long (&acc)[32])
-{
-    constexpr float lim = (float)(1 << ((50 - F) / 2));
-    constexpr float scale = (F == 32) ? 4294967296.0f : (float)(1u << (F & 31));
-    double r[7], rs[6];
-#pragma unroll
-    for (int i = 0; i < 7; i++) r[i] = (double)clamp_row(row[i], lim);
-#pragma unroll
-    for (int i = 0; i < 6; i++) rs[i] = (double)(clamp_row(row[i], lim) * scale);
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-            if (j >= i)  // static index: k(i,j) = 7i - i(i-1)/2 + (j-i)
-                acc[7 * i - (i * (i - 1)) / 2 + (j - i)] += (unsigned long long)__double_as_longlong(fma(rs[i], r[j], kMagic));
-    acc[27] += (unsigned long long)__double_as_longlong(fma(r[6] * (double)scale, r[6], kMagic));
-}
-
-// same with a wave-uniform run-time scale 2^F (RGB step: F follows sigma, rgb_fix_bits)
-__device__ __forceinline__ void se3_accumulate_dyn(const float (&row)[7], unsigned long long (&acc)[32], float lim, float scale)
-{
-    double r[7], rs[6];
-#pragma unroll
-    for (int i = 0; i < 7; i++) r[i] = (double)clamp_row(row[i], lim);
-#pragma unroll
-    for (int i = 0; i < 6; i++) rs[i] = (double)(clamp_row(row[i], lim) * scale);
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-            if (j >= i)
-                acc[7 * i - (i * (i - 1)) / 2 + (j - i)] += (unsigned long long)__double_as_longlong(fma(rs[i], r[j], kMagic));
-    acc[27] += (unsigned long long)__double_as_longlong(fma(r[6] * (double)scale, r[6], kMagic));
-}
-
-// ------------------------------------------------------------------------------------------------
-// Product form of the ICP sums, round 5: the lanes add their products into the WORKGROUP's accumulators in LDS -- word k of lane l at
-// [k][l], 64-bit LDS atomics without return, no bank conflicts -- and the butterfly runs ONCE per workgroup over what all waves (and
-// all runs of a wave) left there, split over four waves (seven or eight words each).  Until then every wave ran the 32 x u64 butterfly
-// on its own registers: 190 of the ~510 VALU instructions of a wave that the launch is bound by, and the 64 accumulator registers
-// that set its occupancy.  Only lanes with a correspondence add; each adds the magic number's bits once per word, so the count of
-// correspondences (word 28: a counter of its own, one LDS add per wave) times those bits comes off behind the butterfly.  Integer
-// sums: who adds what in which order does not change a bit.
-constexpr int kIcpLdsWords = 28;
-__shared__ unsigned long long s_icp_acc[kIcpLdsWords][64];
-__shared__ unsigned s_icp_found;
-__device__ __forceinline__ void lds_add_u64(unsigned long long* p, unsigned long long v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void icp_lds_zero()   // (workgroup-uniform; the barrier behind it is the caller's)
-{
-    for (int i = threadIdx.x; i < kIcpLdsWords * 64; i += blockDim.x) (&s_icp_acc[0][0])[i] = 0;
-    if (threadIdx.x == 0) s_icp_found = 0;
-}
-template <int F>
-__device__ __forceinline__ void se3_accumulate_lds(const float (&row)[7], int lane)
-{
-    constexpr float lim = (float)(1 << ((50 - F) / 2));
-    constexpr float scale = (F == 32) ? 4294967296.0f : (float)(1u << (F & 31));
-    unsigned long long* col = &s_icp_acc[0][lane];
-    double r[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) r[i] = (double)clamp_row(row[i], lim);
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const double rs = (double)(clamp_row(row[i], lim) * scale);
-#pragma unroll
-        for (int j = 0; j < 7; j++)
-            if (j >= i) lds_add_u64(col + 64 * (7 * i - (i * (i - 1)) / 2 + (j - i)), (unsigned long long)__double_as_longlong(fma(rs, r[j], kMagic)));
-    }
-    lds_add_u64(col + 64 * 27, (unsigned long long)__double_as_longlong(fma(r[6] * (double)scale, r[6], kMagic)));
-}
-// ... and the workgroup's totals to its accumulator group in memory (all waves call it: the barrier is inside).  Wave g of the first
-// four reduces words 8 g .. 8 g + 7 (fewer than four waves: they take turns); lanes 8 i of a wave end with word 8 g + i.
-__device__ __forceinline__ void icp_lds_commit(int lane, int wave, int nwaves, unsigned long long* __restrict__ dst /* [32] of this group */)
-{
-    __syncthreads();
-    const unsigned found = s_icp_found;
-    if (found == 0) return;
-    for (int g = wave; g < 4; g += nwaves) {
-        unsigned long long acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc[k] = (g < 3 || k < 4) ? s_icp_acc[(g < 3 || k < 4) ? 8 * g + k : 0][lane] : 0ull;
-        unsigned long long v = wave_reduce8_u64(acc, lane);
-        const int w = 8 * g + (lane >> 3);
-        if (w < 28) v -= (unsigned long long)found * kMagicBits;
-        else v = w == 28 ? (unsigned long long)found : 0ull;
-        if ((lane & 7) == 0 && v != 0) atomicAdd(&dst[w], v);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// cross-wave combine + grouped atomics.  v = wave total of word ((lane>>1)&31) (wave_reduce32_u64).
-// XCD_LOCAL: the atomics are performed in the L2 of THIS XCD (workgroup scope) -- for sums that only workgroups of the same XCD add to and
-// read back (rgb_step_solve_kernel).
-template <int MAXW, bool XCD_LOCAL = false>
-__device__ __forceinline__ void block_commit32(unsigned long long v, int lane, int wave, int nwaves,
-                                               unsigned long long* __restrict__ dst /* [32] of this group */)
-{
-    __shared__ unsigned long long lds[MAXW][32];
-    if ((lane & 1) == 0) lds[wave][lane >> 1] = v;
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        unsigned long long t = 0;
-        for (int w = 0; w < nwaves; w++) t += lds[w][threadIdx.x];
-        if (t != 0) {
-            if constexpr (XCD_LOCAL) __hip_atomic_fetch_add(&dst[threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else atomicAdd(&dst[threadIdx.x], t);
-        }
-    }
-}
-
-// ... the workgroup's 32 totals (4 waves) stored as one row: no atomic, no read-modify-write in the L2 (rgb_step_solve_kernel)
-__device__ __forceinline__ void block_store32(unsigned long long v, int lane, int wave, unsigned long long* __restrict__ row /* [32] */)
-{
-    __shared__ unsigned long long lds[4][32];
-    if ((lane & 1) == 0) lds[wave][lane >> 1] = v;
-    __syncthreads();
-    if (threadIdx.x < 32) row[threadIdx.x] = lds[0][threadIdx.x] + lds[1][threadIdx.x] + lds[2][threadIdx.x] + lds[3][threadIdx.x];
-}
 
 // ================================================================================================
 // ICP:  ICPReduction::search + getProducts, reduce.cu:283-394
@@ -174,53 +53,6 @@ __device__ __forceinline__ IcpProj icp_project(const m33& Rcurr, const f3& tcurr
     o.g = o.inb ? uy * cols + ux : 0;
     o.ux = o.inb ? ux : 0; o.uy = o.inb ? uy : 0;
     return o;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Screen-box culling.  A pixel of the current frame finds a correspondence only if its vertex, taken into the camera the prediction was
-// rendered from (vcurr_cp = Rprev^-1 (Rcurr vcurr + tcurr - tprev)), projects onto a VALID pixel of the prediction -- i.e. lies inside
-// that pixel's pyramid -- and is within distThres of the model vertex there (reduce.cu:321-325), hence at a depth within distThres of it.
-// All such vertices lie in one frustum piece of the prediction camera: the pixel rectangle of the valid predicted vertices (lo / hi [0..1],
-// level-0 pixels; model_maps_tiled_body) between the depths lo[2] - distThres and hi[2] + distThres.  Its eight corners, taken into the
-// current camera and projected, bound the pixels that can contribute (a projective map takes the convex piece into the convex hull of
-// the corners' images): everything outside adds exact zeros and is skipped before it loads anything.
-// Conservative: the rectangle is widened by 3 pixels (a level-l pixel of the model maps is valid only if its 2^l x 2^l level-0 sources
-// are, and its pyramid overhangs them by 2^(l-1) level-0 pixels; + rounding of the per-pixel f32 projection), the depths by 1 % + 1 mm on
-// top of distThres, the projected rectangle by 3 pixels, and a near plane that is not clearly in front of either camera (or anything
-// not finite) gives the whole image.  Called by a whole wave; the result is valid in every lane.
-// Rb / tb: pose of the prediction camera (OdomDev::box_R / box_t).
-__device__ __forceinline__ void screen_box(const float* lo, const float* hi, const float* Rb, const float* tb, const float* Rcurr, const float* tcurr,
-                                           cf_cam intr, float distThres, int W, int H, int lane, int (&out)[4], float (&zout)[2])
-{
-    const float finf = __int_as_float(0x7f800000);
-    zout[0] = -finf; zout[1] = finf;
-    if (!(lo[0] <= hi[0])) { out[0] = 1; out[1] = 1; out[2] = 0; out[3] = 0; return; }  // no predicted vertex: nothing can match
-    const float m = distThres * 1.01f + 1e-3f;
-    const float px = (lane & 1) ? hi[0] + 3.f : lo[0] - 3.f, py = (lane & 2) ? hi[1] + 3.f : lo[1] - 3.f;
-    const float znear = lo[2] - m, pz = (lane & 4) ? hi[2] + m : znear;
-    const float cx_ = (px - intr.cx) / intr.fx * pz, cy_ = (py - intr.cy) / intr.fy * pz;
-    // into the global frame, then into the current camera: Rcurr^T (Rcurr is a rotation up to f32 rounding)
-    const float dx = (Rb[0] * cx_ + Rb[1] * cy_ + Rb[2] * pz + tb[0]) - tcurr[0];
-    const float dy = (Rb[3] * cx_ + Rb[4] * cy_ + Rb[5] * pz + tb[1]) - tcurr[1];
-    const float dz = (Rb[6] * cx_ + Rb[7] * cy_ + Rb[8] * pz + tb[2]) - tcurr[2];
-    const float xc = Rcurr[0] * dx + Rcurr[3] * dy + Rcurr[6] * dz;
-    const float yc = Rcurr[1] * dx + Rcurr[4] * dy + Rcurr[7] * dz;
-    const float zc = Rcurr[2] * dx + Rcurr[5] * dy + Rcurr[8] * dz;
-    const float u = intr.fx * xc / zc + intr.cx, v = intr.fy * yc / zc + intr.cy;
-    const bool bad = !(znear > 0.05f) || !(zc > 0.05f) || !is_finite(u) || !is_finite(v);
-    float u0 = u, u1 = u, v0 = v, v1 = v, z0 = zc, z1 = zc;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        u0 = fminf(u0, __shfl_xor(u0, o, 64)); u1 = fmaxf(u1, __shfl_xor(u1, o, 64));
-        v0 = fminf(v0, __shfl_xor(v0, o, 64)); v1 = fmaxf(v1, __shfl_xor(v1, o, 64));
-        z0 = fminf(z0, __shfl_xor(z0, o, 64)); z1 = fmaxf(z1, __shfl_xor(z1, o, 64));
-    }
-    if (__any(bad)) { out[0] = 0; out[1] = 0; out[2] = W - 1; out[3] = H - 1; return; }
-    // the depth (z in the current camera) of a matching vertex lies between the extreme corners: a linear map of a box
-    zout[0] = z0 - (1e-3f + 1e-3f * fabsf(z0)); zout[1] = z1 + (1e-3f + 1e-3f * fabsf(z1));
-    const float fw = (float)(W + 16), fh = (float)(H + 16);
-    out[0] = (int)floorf(fminf(fmaxf(u0, -16.f), fw)) - 3; out[1] = (int)floorf(fminf(fmaxf(v0, -16.f), fh)) - 3;
-    out[2] = (int)ceilf(fminf(fmaxf(u1, -16.f), fw)) + 3; out[3] = (int)ceilf(fminf(fmaxf(v1, -16.f), fh)) + 3;
 }
 
 template <int PPT> struct VecF;
@@ -479,8 +311,18 @@ __device__ __forceinline__ void icp_error_surface_body(const IcpArgs& args, cons
 
 __global__ void __launch_bounds__(256) icp_error_surface_kernel(const IcpArgs args) { icp_error_surface_body(args, args.m[blockIdx.y], (int)blockIdx.x); }
 
+// Culling tests of a run of consecutive pixels against a tracker's screen box (level-0 pixels, IcpHot::box) at pyramid level L
+struct PixBox { int x0, y0, x1, y1; };
+__device__ __forceinline__ PixBox dilated_box(const int (&box)[4], int L) { return PixBox{(box[0] >> L) - 1, (box[1] >> L) - 1, (box[2] >> L) + 1, (box[3] >> L) + 1}; }
+// does the run [first, last] of flat pixel indices (it may straddle rows) miss the rectangle?  The test of the run's first / last pixel
+__device__ __forceinline__ bool span_misses_box(int first, int last, int cols, IDiv cdiv, int bx0, int by0, int bx1, int by1)
+{
+    const int q0 = idiv(first, cdiv), q1 = idiv(last, cdiv);
+    return q1 < by0 || q0 > by1 || (q0 == q1 && (last - q0 * cols < bx0 || first - q0 * cols > bx1));
+}
+
 // GRID.  One-dimensional, in SLOTS: a slot is the ICP reduction or the RGB residual pass of one model.  IcpArgs::slot_end holds the running
-// totals of the workgroups, IcpArgs::slot_desc what every slot is; the launcher orders them longest work first (launch_icp_kernel_arith).
+// totals of the workgroups, IcpArgs::slot_desc what every slot is; the launcher orders them longest work first (launch_icp_rgbres).
 // Every slot starts at a multiple of 8, so hardware workgroup b and its slot-local index agree on the XCD (b % 8).
 //  * A model that is not culled gets one workgroup per run of T * PPT pixels of its image (or row band), XCD x owning the x-th
 //    horizontal band (xcd_logical_block).
@@ -555,10 +397,8 @@ __device__ __forceinline__ void icp_reduce_body(const IcpArgs& args, const RgbAr
                 start = (cr.y0 + q) * cols + ((cr.x0 + (r - q * cr.nrx)) << 6);
             } else {           // runs of the box's rows; a run may straddle rows: the rectangle test of the run's first / last pixel
                 start = (cr.y0 + r) << 6;
-                const int bx0 = (box[0] >> L) - 1, by0 = (box[1] >> L) - 1, bx1 = (box[2] >> L) + 1, by1 = (box[3] >> L) + 1;
-                const int w1 = min(start + 63, N - 1);
-                const int q0 = idiv(start, args.cdiv), q1 = idiv(w1, args.cdiv);
-                if (q1 < by0 || q0 > by1 || (q0 == q1 && (w1 - q0 * cols < bx0 || start - q0 * cols > bx1))) in_range = false;
+                const PixBox db = dilated_box(box, L);
+                if (span_misses_box(start, min(start + 63, N - 1), cols, args.cdiv, db.x0, db.y0, db.x1, db.y1)) in_range = false;
             }
             // ... and by depth: the run carries the interval of its valid depths (frame_maps_kernel); if it misses the interval the
             // model's dilated box spans in this camera, no pixel of the run can match
@@ -606,15 +446,12 @@ __device__ __forceinline__ void icp_reduce_body(const IcpArgs& args, const RgbAr
     if (cull_here) {
         if (ABL(8)) return;  // timing ablation: culled models do nothing
         const int L = 2 - args.occ_shift;
-        const int bx0 = (hs.box[0] >> L) - 1, by0 = (hs.box[1] >> L) - 1, bx1 = (hs.box[2] >> L) + 1, by1 = (hs.box[3] >> L) + 1;
+        const PixBox db = dilated_box(hs.box, L);
         const int p0 = pix0 + lb * T * PPT, p1 = min(p0 + T * PPT, pix1) - 1;  // first / last pixel of this workgroup
-        const int r0 = idiv(p0, args.cdiv), r1 = idiv(p1, args.cdiv);
-        if (r1 < by0 || r0 > by1) return;
-        if (r0 == r1 && (p1 - r0 * cols < bx0 || p0 - r0 * cols > bx1)) return;
-        const int w0 = p0 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) * 64 * PPT, w1 = min(w0 + 64 * PPT, pix1) - 1;
-        const int q0 = idiv(w0, args.cdiv), q1 = idiv(max(w1, 0), args.cdiv);
+        if (span_misses_box(p0, p1, cols, args.cdiv, db.x0, db.y0, db.x1, db.y1)) return;
+        const int w0 = p0 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) * 64 * PPT, w1 = min(w0 + 64 * PPT, pix1) - 1;   // ... of this wave
         if (ABL(512)) return;  // timing ablation (CF_ICP_REPLAY): the cull test alone
-        if (w0 > w1 || q1 < by0 || q0 > by1 || (q0 == q1 && (w1 - q0 * cols < bx0 || w0 - q0 * cols > bx1))) in_range = false;
+        if (w0 > w1 || span_misses_box(w0, max(w1, 0), cols, args.cdiv, db.x0, db.y0, db.x1, db.y1)) in_range = false;
         // ... and by depth: the run of 64 pixels this wave owns (per pixel of a lane) carries the interval of its valid depths
         // (frame_maps_kernel); if it misses the interval the model's dilated box spans in this camera, no pixel of the run can match
         if (in_range && ma.zr && w0 <= w1) {
@@ -920,1005 +757,14 @@ __device__ void rgb_residual_body(const RgbArgs& ra, int model, int blk, int nbl
 
 __global__ void __launch_bounds__(1024) rgb_residual_kernel(const RgbArgs ra) { rgb_residual_body<false>(ra, blockIdx.y, blockIdx.x, 0); }
 
-// sum of word `w` over the groups (wave 0 only; result valid in all lanes of wave 0)
-__device__ __forceinline__ unsigned long long group_sum(const unsigned long long* acc, int w, int lane)
-{
-    unsigned long long v = acc[(size_t)lane * 32 + w];  // kGroups == 64 == lanes
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += shfl_xor_u64(v, o);
-    return v;
-}
+}  // namespace cf
 
-// wrapping 32-bit sum over the 64 lanes of a wave, the same value in every lane: DPP inside each row of 16 lanes (two quad permutations, the
-// mirrors of the half row and of the row), then the four row totals through scalar registers
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
-{
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);    // quad_perm [1, 0, 3, 2]
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);    // quad_perm [2, 3, 0, 1]
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);   // row_half_mirror
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);   // row_mirror
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned)__builtin_amdgcn_readlane((int)v, 16) + (unsigned)__builtin_amdgcn_readlane((int)v, 32) +
-           (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-}
+// the stages behind the {ICP || residual} launch (see the map at the top); they use what is defined above
+#include "track_so3_dev.h"
+#include "track_solve_dev.h"
+#include "track_rgb_step_dev.h"
 
-// sigma handed to rgbStep (RGBDOdometry.cpp:373-385): (tmpError == 0) ? 1 : count   (sic: the COUNT)
-__device__ __forceinline__ float sigma_val_from(int count, int sigma, int rgbOnly)
-{
-    if (rgbOnly) return -1.f;
-    // tmpError = sqrt(sigma)/count is 0 iff sigma == 0 and count != 0 (0/0 is NaN, NaN != 0)
-    return (sigma == 0 && count != 0) ? 1.f : (float)count;
-}
-
-// ================================================================================================
-// RGB step: RGBReduction::getProducts, reduce.cu:521-604
-// ================================================================================================
-// Jacobian row of one valid correspondence (o = flat index in the next image, g = in the last image / point cloud)
-__device__ __forceinline__ void rgb_step_row(const RgbArgs& ra, const RgbModelArgs& m, float sigma, float diff, int o, int g, float (&row)[7])
-{
-    const cf_cam il = ra.il;
-    float w = sigma + fabsf(diff);
-    w = w > 1.19209290E-07F ? 1.0f / w : 1.0f;
-    if (sigma == -1) w = 1;
-    row[6] = -w * diff;
-    const float* cp = m.cloud + (size_t)g * 3;
-    const float px = cp[0], py = cp[1], pz = cp[2];
-    const float invz = 1.0f / pz;
-    const float dI_dx_val = w * ra.sobelScale * (float)m.dIdx[o];
-    const float dI_dy_val = w * ra.sobelScale * (float)m.dIdy[o];
-    const float v0 = dI_dx_val * il.fx * invz;
-    const float v1 = dI_dy_val * il.fy * invz;
-    const float v2 = -(v0 * px + v1 * py) * invz;
-    row[0] = v0; row[1] = v1; row[2] = v2;
-    row[3] = -pz * v1 + py * v2;
-    row[4] = pz * v0 - px * v2;
-    row[5] = -py * v0 + px * v1;
-}
-
-__global__ void __launch_bounds__(256) rgb_step_kernel(const RgbArgs ra)
-{
-    const RgbModelArgs& m = ra.m[blockIdx.y];
-    const RgbHot hs = rgb_hot((StatePtr)m.st);
-    if (hs.rgb && !hs.level_done) {
-        const int cols = ra.cols, rows = ra.rows, N = cols * rows;
-        __shared__ float s_sigma;
-        if (threadIdx.x < 64) {
-            const long long cnt = (long long)group_sum(m.icp_acc, 29, threadIdx.x);
-            const long long sg = (long long)group_sum(m.icp_acc, 30, threadIdx.x);
-            if (threadIdx.x == 0) s_sigma = sigma_val_from((int)cnt, (int)sg, hs.rgbOnly);
-        }
-        const int i = blockIdx.x * 256 + threadIdx.x;
-        int4 raw = make_int4(0, 0, 0, 0);
-        if (i < N) raw = *reinterpret_cast<const int4*>(&m.corres[i]);
-        __syncthreads();
-        const float sigma = s_sigma;
-        unsigned long long acc[32];
-#pragma unroll
-        for (int k = 0; k < 28; k++) acc[k] = 0ull - kMagicBits;
-        acc[28] = acc[29] = acc[30] = acc[31] = 0;
-        float row[7] = {0, 0, 0, 0, 0, 0, 0};
-        int found = 0;
-        if (i < N) {
-            const cf_dataterm c = *reinterpret_cast<const cf_dataterm*>(&raw);
-            if (c.valid) {
-                found = 1;
-                rgb_step_row(ra, m, sigma, c.diff, c.one_y * cols + c.one_x, c.zero_y * cols + c.zero_x, row);
-            }
-        }
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        unsigned long long v = 0;
-        if (__any(found)) {  // a wave without a valid correspondence adds exact zeros
-            const int F = rgb_fix_bits(sigma);
-            se3_accumulate_dyn(row, acc, ldexpf(1.0f, (50 - F) / 2), ldexpf(1.0f, F));
-            acc[28] = (unsigned long long)found;
-            v = wave_reduce32_u64(acc, lane);
-        }
-        block_commit32<4>(v, lane, wave, 4, m.rgb_acc + (size_t)(blockIdx.x % kGroups) * 32);
-    }
-}
-
-// ================================================================================================
-// SO3: SO3Reduction::getProducts, reduce.cu:1007-1090
-// ================================================================================================
-__device__ __forceinline__ void so3_gradient(const uint8_t* __restrict__ img, int cols, int x, int y, float& gx, float& gy)
-{  // reduce.cu:989-1005
-    const float actu = (float)img[y * cols + x];
-    float back = (float)img[y * cols + x - 1], fore = (float)img[y * cols + x + 1];
-    gx = ((back + actu) / 2.0f) - ((fore + actu) / 2.0f);
-    back = (float)img[(y - 1) * cols + x]; fore = (float)img[(y + 1) * cols + x];
-    gy = ((back + actu) / 2.0f) - ((fore + actu) / 2.0f);
-}
-
-// one (grid-strided over blockIdx.x) pass over the level-2 images; this workgroup's totals[0..10] end up in LDS
-__device__ __forceinline__ void so3_pass(const uint8_t* __restrict__ lastImage, const uint8_t* __restrict__ nextImage,
-                                         const m33& B, const m33& Ki, const float* __restrict__ krlr, int cols, int rows,
-                                         unsigned long long (*lds)[16], unsigned long long* totals, int block, int blocks)
-{
-    constexpr float lim = (float)(1 << ((50 - kFixSO3) / 2));
-    constexpr float scale = (float)(1 << kFixSO3);
-    const int N = cols * rows, T = blockDim.x;
-    unsigned long long acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) acc[k] = 0;
-    const float a = krlr[0], b = krlr[1], c = krlr[2], d = krlr[3], e = krlr[4], f = krlr[5], g = krlr[6], h = krlr[7],
-                ii = krlr[8];
-    // (Measured and dropped, round 6: four pixels of a thread at a time -- their warps first, the 4 x 10 byte loads of the gradient stencils in
-    // flight together, then the rows: so3_prealign_kernel 82.0 against 63.1 us on one box, profiles/r6u_*.  The registers of four stencils
-    // cost the launch's other half, the RGB preparation workgroups, their occupancy; the pass itself is 4-7 us of a 9 us iteration.)
-    for (int k = block * T + threadIdx.x; k < N; k += blocks * T) {
-        const int y = k / cols, x = k - y * cols;
-        const f3 unwarped = {(float)x, (float)y, 1.0f};
-        const f3 warped = mul(B, unwarped);
-        const int wx = f2i_rn(warped.x / warped.z), wy = f2i_rn(warped.y / warped.z);
-        if (!(wx >= 1 && wx < cols - 1 && wy >= 1 && wy < rows - 1 && x >= 1 && x < cols - 1 && y >= 1 && y < rows - 1))
-            continue;
-        float gnx, gny, glx, gly;
-        so3_gradient(nextImage, cols, wx, wy, gnx, gny);
-        so3_gradient(lastImage, cols, x, y, glx, gly);
-        const float gx = (gnx + glx) / 2.0f, gy = (gny + gly) / 2.0f;
-        const f3 point = mul(Ki, unwarped);
-        const float z2 = point.z * point.z;
-        const f3 left = {((point.z * (d * gy + a * gx)) - (gy * g * y) - (gx * g * x)) / z2,
-                         ((point.z * (e * gy + b * gx)) - (gy * h * y) - (gx * h * x)) / z2,
-                         ((point.z * (f * gy + c * gx)) - (gy * ii * y) - (gx * ii * x)) / z2};
-        const f3 jac = cross(left, point);
-        const float row[4] = {jac.x, jac.y, jac.z, -((float)nextImage[wy * cols + wx] - (float)lastImage[y * cols + x])};
-        double r[4], rs[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) { r[q] = (double)clamp_row(row[q], lim); rs[q] = (double)(clamp_row(row[q], lim) * scale); }
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                if (q >= p)  // k(p,q) = 4p - p(p-1)/2 + (q-p)
-                    acc[4 * p - (p * (p - 1)) / 2 + (q - p)] += (unsigned long long)__double_as_longlong(fma(rs[p], r[q], kMagic)) - kMagicBits;
-        acc[9] += (unsigned long long)__double_as_longlong(fma(rs[3], r[3], kMagic)) - kMagicBits;
-        acc[10] += 1;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long v = wave_reduce16_u64(acc, lane);
-    if ((lane & 3) == 0) lds[wave][lane >> 2] = v;
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        unsigned long long t = 0;
-        for (int w = 0; w < (T >> 6); w++) t += lds[w][threadIdx.x];
-        totals[threadIdx.x] = t;
-    }
-    __syncthreads();
-}
-
-// reduce.cu:1158-1175 host unpack, on device
-__device__ inline void so3_unpack(const unsigned long long* t, float A[9], float b[3], float residual[2])
-{
-    int shift = 0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = i; j < 4; ++j) {
-            const float value = fix_to_f32((long long)t[shift++], kFixSO3);
-            if (j == 3) b[i] = value;
-            else A[j * 3 + i] = A[i * 3 + j] = value;
-        }
-    residual[0] = fix_to_f32((long long)t[9], kFixSO3);
-    residual[1] = (float)(long long)t[10];
-}
-
-__device__ inline void k_matrix(cf_cam c, double K[9])
-{
-    for (int i = 0; i < 9; i++) K[i] = 0;
-    K[0] = c.fx; K[4] = c.fy; K[2] = c.cx; K[5] = c.cy; K[8] = 1;
-}
-
-// krkInv / kt for the next iteration (RGBDOdometry.cpp:347-358)
-__device__ inline void prepare_iteration(OdomDev* od, int level)
-{
-    double K[9], Kinv[9], Rt[16];
-    k_matrix(cam_level(od->intr, level), K);
-    inv33<double>(K, Kinv);
-    inv44_affine(od->resultRt, Rt);
-    const double R[9] = {Rt[0], Rt[1], Rt[2], Rt[4], Rt[5], Rt[6], Rt[8], Rt[9], Rt[10]};
-    double tmp[9], KRK[9];
-    mul33<double>(K, R, tmp);
-    mul33<double>(tmp, Kinv, KRK);
-    for (int k = 0; k < 9; k++) od->krkInv[k] = (float)KRK[k];
-    const double tv[3] = {Rt[3], Rt[7], Rt[11]};
-    for (int r = 0; r < 3; r++) od->kt[r] = (float)(K[r * 3 + 0] * tv[0] + K[r * 3 + 1] * tv[1] + K[r * 3 + 2] * tv[2]);
-}
-
-// Stand-alone single SO3 step (C-ABI so3Step): one workgroup, totals to out16
-__global__ void __launch_bounds__(1024) so3_step_kernel(const uint8_t* __restrict__ lastImage,
-                                                        const uint8_t* __restrict__ nextImage, m33 B, m33 Ki, m33 krlr,
-                                                        int cols, int rows, unsigned long long* __restrict__ out16)
-{
-    __shared__ unsigned long long lds[16][16];
-    __shared__ unsigned long long totals[16];
-    so3_pass(lastImage, nextImage, B, Ki, krlr.m, cols, rows, lds, totals, blockIdx.x, gridDim.x);
-    if (threadIdx.x < 16) out16[threadIdx.x] = totals[threadIdx.x];
-}
-
-// Whole SO3 pre-alignment (RGBDOdometry.cpp:239-310) in ONE launch.  The pass over the 160x120 level is VALU-bound
-// on a single CU (10.5 us per iteration, measured), so kSo3Blocks co-resident workgroups per model share it:
-// each reduces its pixels, adds its 11 fixed-point totals to the iteration's slot of a global accumulator and
-// meets the others at an atomic arrival counter; every workgroup then reads the totals and runs the identical 3x3
-// solve + Rodrigues on its own LDS copy of the state, so nothing but integer atomics crosses workgroups and the
-// data-dependent early exits stay uniform.  The last workgroup to leave re-zeroes the sync block for the next frame.
-// Also seeds resultRt and the first iteration's krkInv/kt.
-//
-// ONE XCD PER MODEL (round 4).  Until round 4 the meeting was device-scope: atomics through the fabric, a release fence that writes the
-// XCD's L2 back, polling loads that bypass it -- tools/microbench/xcd_barrier.hip measures 9.1 us for such a barrier of 32 workgroups
-// (11.3 us across the chip) against 1.1 us when the workgroups share an XCD and meet in its L2 (atomics at workgroup scope execute in
-// the L2, and so do the returning atomics the counters and sums are read with; nothing is written back).  The launch therefore has 8 x
-// kSo3Blocks workgroups per model and keeps those whose index is (model mod 8) modulo 8: the dispatcher deals consecutive workgroups
-// round-robin over the XCDs (what xcd_logical_block relies on too), so they share one.  Should that ever not hold, the arrival
-// counters live in different L2s, the bounded wait below expires and raises the fault word -- cf_odom_fetch_result returns CF_ESTATE
-// instead of a pose from partial sums.  The sums are integers: the bits do not depend on any of this.
-// Reads that are answered by the L2 itself: a RETURNING read-modify-write (OR with 0).  A load marked sc0 is a group-scope load, which
-// the CU's vector L1 may serve -- with it the workgroups spun on a stale arrival count (reproduced in tools/microbench/xcd_barrier.hip).
-__device__ __forceinline__ unsigned l2_read_u32(unsigned* p)
-{
-    unsigned v;
-    const unsigned zero = 0;
-    asm volatile("global_atomic_or %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p), "v"(zero) : "memory");
-    return v;
-}
-__device__ __forceinline__ unsigned long long l2_read_u64(unsigned long long* p)
-{
-    unsigned long long v;
-    const unsigned long long zero = 0;
-    asm volatile("global_atomic_or_x2 %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p), "v"(zero) : "memory");
-    return v;
-}
-// The launch is one-dimensional: [gx workgroups per model of the pre-alignment | prep_bx workgroups per model of the RGB preparation
-// (Sobel + candidate mask + cloud: rgb_prep_body)].  The two read the same pyramids and depend on nothing of each other; the
-// pre-alignment is a latency chain on 16 workgroups per model, the preparation fills the rest of the chip meanwhile.
-//
-// The tracker state of the call arrives here as well: the host fills its pinned copy, every pre-alignment workgroup stages that copy into
-// LDS (one coalesced read over PCIe, hidden beside the preparation workgroups) and the lead workgroup of each tracker stores it into the
-// device state the rest of the schedule reads -- no copy command in front of the loop (two of them cost ~10 us on the stream per frame).
-#ifdef CF_ABLATE
-// diagnostics build (CF_SO3_TRACE): stamps of tracker 0's lead workgroup in the pre-alignment loop, [iteration][8]
-__device__ unsigned long long g_so3_trace[12][8];
-#define OSTAMP(it, k) do { if (lead && by == 0 && threadIdx.x == 0) g_so3_trace[it][k] = wall_clock64(); } while (0)
-#else
-#define OSTAMP(it, k) do {} while (0)
-#endif
-__global__ void __launch_bounds__(256) so3_prealign_kernel(const TrackerStates ts, So3Sync* __restrict__ syncs, int do_so3,
-                                                           int first_level, int gx, int so3_blocks, const RgbPrepBatch prep, int prep_bx)
-{
-    if ((int)blockIdx.x >= so3_blocks) {
-        const int r = (int)blockIdx.x - so3_blocks, m = r / prep_bx;
-        rgb_prep_body(prep.m[m], r - m * prep_bx);
-        return;
-    }
-    const int by = (int)blockIdx.x / gx, bxx = (int)blockIdx.x - by * gx;  // gx is 1 or a multiple of 8: bxx mod 8 is the XCD
-    OdomDev* const god = ts.dev[by];
-    So3Sync* sync = syncs + by;
-    __shared__ OdomDev s_od;
-    __shared__ unsigned long long lds[16][16];
-    __shared__ unsigned long long totals[16];
-    __shared__ float s_basis[9], s_kinv[9], s_krlr[9];
-    __shared__ int s_done;
-    __shared__ double s_resultR[9];
-    __shared__ double s_K[9], s_Kinv[9];
-    __shared__ float s_Rlr[9];
-    __shared__ float s_lastError, s_lastCount;
-    __shared__ double s_lastResultR[9];
-    __shared__ float s_jtj[9], s_jtr[3], s_delta[3], s_fws[15];
-    __shared__ int s_iws[3];
-    // with the pre-alignment the launch is 8 x kSo3Blocks wide: this model's workgroups are the ones on XCD (model mod 8)
-    const bool one_xcd = do_so3 && gx > 1;
-    if (one_xcd && (bxx & 7) != (by & 7)) return;
-    const int bx = one_xcd ? (bxx >> 3) : bxx;
-    const bool lead = bx == 0;  // the workgroup that uploads the state, publishes statistics and the final state
-    const unsigned G = one_xcd ? (unsigned)gx >> 3 : (unsigned)gx;
-    {
-        static_assert(sizeof(OdomDev) % 4 == 0, "OdomDev is staged as 32-bit words");
-        constexpr int kWords = (int)(sizeof(OdomDev) / 4);
-        const unsigned* __restrict__ src = reinterpret_cast<const unsigned*>(ts.host[by]);
-        constexpr int kPer = (kWords + 255) / 256;   // (both loads of a thread in flight together: they cross PCIe)
-        unsigned w[kPer];
-#pragma unroll
-        for (int q = 0; q < kPer; q++) w[q] = ((int)threadIdx.x + 256 * q < kWords) ? src[threadIdx.x + 256 * q] : 0u;
-#pragma unroll
-        for (int q = 0; q < kPer; q++) if ((int)threadIdx.x + 256 * q < kWords) reinterpret_cast<unsigned*>(&s_od)[threadIdx.x + 256 * q] = w[q];
-        __syncthreads();
-        if (lead) for (int k = threadIdx.x; k < kWords; k += 256) reinterpret_cast<unsigned*>(god)[k] = reinterpret_cast<const unsigned*>(&s_od)[k];
-        __syncthreads();  // (the lead's later stores into the device state follow the upload)
-    }
-    const OdomDev* const od = &s_od;  // what the host passed; results go to the device state (god)
-    const int L = 2, cols = od->width >> L, rows = od->height >> L;
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < 9; k++) { s_resultR[k] = (k % 4 == 0) ? 1.0 : 0.0; s_lastResultR[k] = s_resultR[k]; s_Rlr[k] = (k % 4 == 0) ? 1.f : 0.f; }
-        k_matrix(cam_level(od->intr, L), s_K);
-        inv33<double>(s_K, s_Kinv);
-        s_lastError = 3.402823466e+38F / 2; s_lastCount = 3.402823466e+38F / 2;
-        s_done = 0;
-        if (lead) { god->stats.so3_iterations = 0; god->stats.last_so3_error = 0; god->stats.last_so3_count = 0; }
-    }
-    __syncthreads();
-    if (do_so3) {
-        const uint8_t* __restrict__ lastNext = od->lastNextImage[L];
-        const uint8_t* __restrict__ next = od->nextImage[L];
-        OSTAMP(11, 0);
-        for (int it = 0; it < 10; it++) {
-            OSTAMP(it, 0);
-            if (threadIdx.x == 0) {
-                double tmp[9], H[9];
-                mul33<double>(s_K, s_resultR, tmp);
-                mul33<double>(tmp, s_Kinv, H);
-                for (int k = 0; k < 9; k++) { s_basis[k] = (float)H[k]; s_kinv[k] = (float)s_Kinv[k]; s_krlr[k] = (float)tmp[k]; }
-            }
-            __syncthreads();
-            m33 B, Ki;
-            for (int k = 0; k < 9; k++) { B.m[k] = s_basis[k]; Ki.m[k] = s_kinv[k]; }
-            OSTAMP(it, 1);
-            so3_pass(lastNext, next, B, Ki, s_krlr, cols, rows, lds, totals, bx, (int)G);  // ends with this workgroup's totals in LDS
-            OSTAMP(it, 2);
-            if (G > 1) {
-                if (threadIdx.x < 64) {  // wave 0: publish, arrive, wait, collect -- everything in this XCD's L2
-                    unsigned long long* slot = sync->acc[it];
-                    if (threadIdx.x < 11 && totals[threadIdx.x] != 0)
-                        __hip_atomic_fetch_add(&slot[threadIdx.x], totals[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the L2 has taken this wave's sums before it arrives
-                    if (threadIdx.x == 0) {
-                        __hip_atomic_fetch_add(&sync->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        const unsigned target = (unsigned)(it + 1) * G;
-                        unsigned spins = 0;
-                        while (l2_read_u32(&sync->arrive) < target) {
-                            if (++spins > (1u << 22)) { god->stats.fault = 1; break; }  // never hang the GPU; the host reports CF_ESTATE
-                            __builtin_amdgcn_s_sleep(1);
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    if (threadIdx.x < 16) totals[threadIdx.x] = l2_read_u64(&slot[threadIdx.x]);
-                }
-                __syncthreads();
-            }
-            OSTAMP(it, 3);
-            if (threadIdx.x == 0) {
-                float jtj[9], jtr[3], residual[2];
-                so3_unpack(totals, jtj, jtr, residual);
-                if (lead) god->stats.so3_iterations = it + 1;
-                float err = sqrtf(residual[0]) / residual[1];
-                float cnt = residual[1];
-                if (err < s_lastError && (double)fabsf(s_lastError - cnt) < 0.001) {
-                    s_done = 1;  // "converged" (compares error with COUNT, RGBDOdometry.cpp:285)
-                } else if ((double)err > (double)s_lastError + 0.001) {
-                    err = s_lastError; cnt = s_lastCount;
-                    for (int k = 0; k < 9; k++) s_resultR[k] = s_lastResultR[k];
-                    s_done = 1;
-                } else {
-                    s_lastError = err; s_lastCount = cnt;
-                    for (int k = 0; k < 9; k++) s_lastResultR[k] = s_resultR[k];
-                    for (int k = 0; k < 9; k++) s_jtj[k] = jtj[k];
-                    for (int k = 0; k < 3; k++) s_jtr[k] = jtr[k];
-                    ldlt_solve<float, 3>(s_jtj, s_jtr, s_delta, 1.17549435e-38f, s_fws, s_iws);
-                    const float delta[3] = {s_delta[0], s_delta[1], s_delta[2]};
-                    const double dd[3] = {delta[0], delta[1], delta[2]};
-                    double rotUpdate[9];
-                    rodrigues(dd, rotUpdate);
-                    float ru[9], nr[9];
-                    for (int k = 0; k < 9; k++) ru[k] = (float)rotUpdate[k];
-                    mul33<float>(ru, s_Rlr, nr);
-                    for (int k = 0; k < 9; k++) { s_Rlr[k] = nr[k]; s_resultR[k] = nr[k]; }
-                }
-                if (lead) { god->stats.last_so3_error = err; god->stats.last_so3_count = cnt; }
-            }
-            __syncthreads();
-            OSTAMP(it, 4);
-            if (s_done) break;
-        }
-        OSTAMP(11, 1);
-        if (G > 1 && threadIdx.x == 0) {  // last one out resets the sync block (all workgroups are past their final read)
-            if (__hip_atomic_fetch_add(&sync->depart, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == G - 1) {
-                for (int it = 0; it < 10; it++)
-                    for (int w = 0; w < 16; w++) sync->acc[it][w] = 0;
-                sync->arrive = 0; sync->depart = 0;
-            }
-        }
-    }
-    if (lead && threadIdx.x < 64) {
-        // latch the bounding box the model-map pass accumulated (and clear the accumulator for the next frame); first screen box
-        const int lane = threadIdx.x;
-        unsigned key = 0;
-        if (od->cull && lane < 6) { key = od->aabb_acc[lane]; od->aabb_acc[lane] = 0; }
-        const float val = lane < 3 ? fkey_inv(~key) : fkey_inv(key);
-        float lo[3], hi[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = __shfl(val, k, 64); hi[k] = __shfl(val, 3 + k, 64); }
-        if (__shfl((int)key, 3, 64) == 0) { lo[0] = 1.f; hi[0] = 0.f; }  // never written: empty
-        int ib[4] = {0, 0, od->width - 1, od->height - 1};
-        float zb[2] = {-__int_as_float(0x7f800000), __int_as_float(0x7f800000)};
-        if (od->cull) screen_box(lo, hi, od->box_R, od->box_t, od->Rcurr, od->tcurr, od->intr, od->distThres, od->width, od->height, lane, ib, zb);
-        if (lane == 0) {
-            for (int k = 0; k < 3; k++) { god->box_lo[k] = lo[k]; god->box_hi[k] = hi[k]; }
-            for (int k = 0; k < 4; k++) god->stats.cull_box[k] = ib[k];
-            god->cull_z[0] = zb[0]; god->cull_z[1] = zb[1];
-        }
-    }
-    if (lead && threadIdx.x == 0) {
-        for (int k = 0; k < 16; k++) god->resultRt[k] = (k % 5 == 0) ? 1.0 : 0.0;
-        if (do_so3)
-            for (int x = 0; x < 3; x++)
-                for (int y = 0; y < 3; y++) god->resultRt[x * 4 + y] = s_resultR[x * 3 + y];
-        god->lastRGBError = 3.402823466e+38F;
-        god->level_done = 0;
-        god->residual[0] = 0; god->residual[1] = 0;
-        prepare_iteration(god, first_level);
-        refresh_hot(god);   // what the workgroups of the per-iteration launches read (cf_kernels.h: GnHot)
-    }
-}
-
-// ================================================================================================
-// per-iteration solve: sums -> A,b (f32) -> f64 combine -> LDL^T -> SE3 update -> next krkInv/kt
-// (RGBDOdometry.cpp:371-461, reduce.cu:481-498, OdometryProvider.h:69-89)
-// ================================================================================================
-__device__ inline void se3_unpack(const unsigned long long* t, int F, float A[36], float b[6], float residual[2])
-{
-    int shift = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 7; ++j) {
-            const float value = fix_to_f32((long long)t[shift++], F);
-            if (j == 6) b[i] = value;
-            else A[j * 6 + i] = A[i * 6 + j] = value;
-        }
-    residual[0] = fix_to_f32((long long)t[27], F);
-    residual[1] = (float)(long long)t[28];
-}
-
-// one word of se3_unpack: t < 27 -> A / b entry, 27 -> sum of squared residuals, 28 -> inlier count
-// F < 0: the Gram form of the ICP sums (cf_device.h: word (i, j) carries kGramBits[i] + kGramBits[j] fraction bits)
-__device__ __forceinline__ void se3_unpack_word(const unsigned long long* sums, int t, int F, float* A, float* b, float* residual)
-{
-    if (t < 27) {
-        int i = 0, rem = t;
-        while (rem >= 7 - i) { rem -= 7 - i; i++; }
-        const int j = i + rem;
-        const int bits = F >= 0 ? F : (i < 3 ? 20 : 17) + (j < 3 ? 20 : j < 6 ? 17 : 22);
-        const float value = fix_to_f32((long long)sums[t], bits);
-        if (j == 6) b[i] = value;
-        else A[j * 6 + i] = A[i * 6 + j] = value;
-    } else if (residual) {
-        if (t == 27) residual[0] = fix_to_f32((long long)sums[27], F >= 0 ? F : 44);
-        else if (t == 28) residual[1] = (float)(long long)sums[28];
-    }
-}
-static_assert(kGramBits[0] == 20 && kGramBits[2] == 20 && kGramBits[3] == 17 && kGramBits[5] == 17 && kGramBits[6] == 22, "se3_unpack_word spells the Gram scales out");
-
-// The solve is latency-bound serial work (f64 LDL^T, Rodrigues, SE3 products) on a nearly idle GPU, so:
-//  * the whole device-resident state is staged through LDS (no dependent global round trips),
-//  * the parallel pieces (group totals, fixed-point -> f32 unpack, f64 combine, 4x4 / 3x3 products) are spread
-//    over lanes with exactly the element expressions of the serial helpers, the 6x6 pivoted LDL^T runs across
-//    one wave (ldlt_solve6_wave), and K^-1 of the next level is formed by another wave meanwhile,
-//  * only Rodrigues and the 3x3 pose composition stay on one lane.
-// Must be called by all 256 threads of a workgroup.
-// RGB_IN_L2: the RGB sums were added by workgroup-scope atomics of this launch (rgb_step_solve_kernel): they are read where they live,
-// in this XCD's L2, with agent-scope loads -- a plain load may be served by the CU's L1.
-#ifdef CF_ABLATE
-// diagnostics build (CF_SOLVE_TRACE): phase stamps of tracker 0's solves of one tracking call, [solve][16] on the 100 MHz constant clock
-__device__ unsigned long long* g_solve_trace = nullptr;
-__device__ unsigned g_solve_iter = 0;
-#define SSTAMP(k) do { if (g_solve_trace && threadIdx.x == 0 && blockIdx.x == 0) g_solve_trace[(size_t)(g_solve_iter & 63u) * 16 + (k)] = wall_clock64(); } while (0)
-#else
-#define SSTAMP(k) do {} while (0)
-#endif
-// same-wave exchange through LDS: a wave's LDS operations execute in program order, so all that is needed between a lane's store and
-// another lane's load is that the compiler keeps them in that order
-__device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-
-// ROUND 6 (9.2 us per solve, the frame's most expensive kernel in total).  The kernel is ONE chain of dependent
-// instructions on wave 0 -- ~2500 of them at 4-8 cycles each (profiles/r6c_solve_phases.txt: 1.4 us in the unpack alone, a divergent
-// search loop per word, executed twice for the ICP and the RGB lanes of the same wave) -- so what counts is the number of instructions on
-// that chain and the barriers that make wave 0 wait for stores:
-//  * every lane of the factorisation forms ITS OWN matrix element straight from the totals (closed-form word index, one pass for both
-//    systems) -- no unpacked f32 matrices in LDS, no search loop, two barriers less;
-//  * everything behind the factorisation is spread over lanes with exactly the element expressions of the serial helpers (Rodrigues'
-//    nine entries, the 4x4 product, the f32 pose composition, the affine inverse, K R K^-1), exchanged through LDS inside wave 0;
-//  * the statistics (two square roots, two divisions) and the screen box run on idle waves beside that chain, refresh_hot is folded into
-//    the write-back, and the accumulators are zeroed by the LAST instructions of the kernel (a barrier waits for outstanding stores
-//    too: 16 stores per thread in front of one cost 0.7 us);
-//  * five barriers instead of eleven.
-// Must be called by all 256 threads of a workgroup.
-// RGB_IN_L2: the RGB sums were added by workgroup-scope atomics of this launch (rgb_step_solve_kernel): they are read where they live,
-// in this XCD's L2, with agent-scope loads -- a plain load may be served by the CU's L1.
-template <bool RGB_IN_L2 = false>
-__device__ __forceinline__ void gn_solve_body(int icp_fix, OdomDev* god, unsigned long long* icp_acc, unsigned long long* rgb_acc, int next_level,
-                                              int last_of_level, OdomDev* god_host, int slot_px, int part_first = 0, int part_last = -1)
-{
-    __shared__ OdomDev s_od;
-    __shared__ unsigned long long s_icp[32], s_rgb[32];
-    __shared__ unsigned long long s_part[2][8][32];
-    __shared__ double s_result[6];
-    __shared__ double s_upd[16], s_K[9], s_Kinv[9], s_Rt[16], s_tmp[9];
-    __shared__ int s_flags[2];   // active, stop (wave 0 decides; the statistics lane on wave 3 reads them behind a barrier)
-    static_assert(sizeof(OdomDev) % 4 == 0, "OdomDev is staged as 32-bit words");
-    constexpr int kWords = (int)(sizeof(OdomDev) / 4);
-    constexpr int kMutableFrom = (int)(offsetof(OdomDev, Rprev) / 4);
-    const int tid = threadIdx.x;
-    SSTAMP(0);
-    OdomDev* const od = &s_od;
-    // the state's words and the accumulator words in ONE flight of loads (a rolled copy loop waits for every load before it stores to
-    // LDS: two dependent round trips in front of the accumulator loads, ~1.5 us of every solve until round 5)
-    constexpr int kPer = (kWords + 255) / 256;
-    unsigned stw[kPer];
-#pragma unroll
-    for (int q = 0; q < kPer; q++) stw[q] = (tid + 256 * q < kWords) ? reinterpret_cast<const unsigned*>(god)[tid + 256 * q] : 0u;
-    {   // 256 threads: word = t & 31, slice = t >> 5 (8 slices of 8 groups)
-        const int w = tid & 31, sl = tid >> 5;
-        unsigned long long a = 0, b = 0;
-        if constexpr (RGB_IN_L2) {   // rgb_acc holds one row of 32 totals per workgroup of the step, rows part_first .. part_last (rgb_step_solve_kernel).
-            // Agent-scope loads: never served by the CU's L1, answered by the L2 the rows were stored to
-            for (int g = sl * (kGroups / 8); g < (sl + 1) * (kGroups / 8); g++) a += icp_acc[(size_t)g * 32 + w];
-            for (int r0 = part_first + sl; r0 <= part_last; r0 += 64) {   // eight rows in flight per lane (a rolled loop waits for every load)
-                unsigned long long t[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int r = r0 + 8 * k;
-                    t[k] = __hip_atomic_load(&rgb_acc[(size_t)(r <= part_last ? r : part_last) * 32 + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (r > part_last) t[k] = 0;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) b += t[k];
-            }
-        } else
-        for (int g = sl * (kGroups / 8); g < (sl + 1) * (kGroups / 8); g++) {
-            a += icp_acc[(size_t)g * 32 + w];
-            b += rgb_acc[(size_t)g * 32 + w];
-        }
-        s_part[0][sl][w] = a; s_part[1][sl][w] = b;
-    }
-#pragma unroll
-    for (int q = 0; q < kPer; q++) if (tid + 256 * q < kWords) reinterpret_cast<unsigned*>(&s_od)[tid + 256 * q] = stw[q];
-    __syncthreads();                                                                       // ---- barrier 1: state + partial sums in LDS
-    SSTAMP(1);
-    const bool cull = od->cull != 0;
-    if (tid < 64) {
-        // ============================== wave 0: the chain ==============================
-        const int lane = tid;
-        if (lane < 32) {
-            unsigned long long a = 0, b = 0;
-            for (int sl = 0; sl < 8; sl++) { a += s_part[0][sl][lane]; b += s_part[1][sl][lane]; }
-            s_icp[lane] = a; s_rgb[lane] = b;
-        }
-        wave_lds_sync();
-        SSTAMP(2);
-        // uniform decisions (RGBDOdometry.cpp:371-392).  The RGB error (an f64 square root and division) only decides anything in the RGB-only
-        // mode; otherwise it is a statistic, computed on another wave beside this chain
-        bool active = od->level_done == 0, stop = false;
-        const bool rgbOnly = od->rgbOnly != 0;
-        const int rgbCount = (int)(long long)s_icp[29], rgbSigma = (int)(long long)s_icp[30];
-        if (active && rgbOnly) {
-            const float tmpError = (float)(sqrt((double)rgbSigma) / (double)rgbCount);
-            if (tmpError > od->lastRGBError) { stop = true; active = false; }
-        }
-        if (lane == 0) { s_flags[0] = active ? 1 : 0; s_flags[1] = stop ? 1 : 0; }
-        const bool useIcp = od->icp != 0, useRgb = od->rgb != 0;
-        if (active) {
-            // lane L < 36: A[L / 6][L % 6] of the combined system from word (min, max) of the two sums (reduce.cu:481-498: the host fills the
-            // matrix symmetrically from the upper triangle); lanes 36..41: b[L - 36] from word (i, 6); lanes 42 / 43: the ICP residual pair
-            double a = 0.0;
-            {
-                const int L = lane;
-                const int i = L < 36 ? L / 6 : L - 36, j = L < 36 ? L - 6 * (L / 6) : 6;
-                const int lo = i < j ? i : j, hi = i < j ? j : i;
-                int t = 7 * lo - ((lo * (lo - 1)) >> 1) + (hi - lo);
-                if (L >= 42) t = L == 42 ? 27 : 28;
-                if (L >= 44) t = 0;
-                const int bits_icp = icp_fix >= 0 ? icp_fix : (L == 42 ? 44 : (lo < 3 ? 20 : 17) + (hi < 3 ? 20 : hi < 6 ? 17 : 22));
-                const int bits_rgb = rgb_fix_bits(sigma_val_from(rgbCount, rgbSigma, od->rgbOnly));
-                const long long qi = (long long)s_icp[t], qr = (long long)s_rgb[t];
-                const float vi = useIcp ? fix_to_f32(qi, bits_icp) : 0.f, vr = useRgb ? fix_to_f32(qr, bits_rgb) : 0.f;
-                if (L < 42) {
-                    const bool isA = L < 36;
-                    if (useIcp && useRgb) {
-                        const double w = od->icpWeight;
-                        a = isA ? (double)vr + w * w * (double)vi : (double)vr + w * (double)vi;
-                    } else a = useIcp ? (double)vi : (double)vr;
-                    if (isA) od->stats.lastA[L] = a;
-                    else od->stats.lastb[L - 36] = a;
-                } else if (useIcp) {
-                    if (L == 42) od->residual[0] = vi;
-                    else if (L == 43) od->residual[1] = (float)qi;
-                }
-            }
-            wave_lds_sync();
-            SSTAMP(3);
-            ldlt_solve6_wave(lane < 42 ? a : 0.0, s_result, 2.2250738585072014e-308, lane);   // (lanes 36..41: b)
-            wave_lds_sync();
-            SSTAMP(4);
-            // computeUpdateSE3 (OdometryProvider.h:69-89).  Rodrigues (:32-67): theta, its sine / cosine and 1 / theta are the same in every
-            // lane; lane q < 16 then forms ITS entry of the update matrix [R | t; 0 0 0 1]
-            {
-                double rx = s_result[3], ry = s_result[4], rz = s_result[5];
-                const double theta = sqrt(rx * rx + ry * ry + rz * rz);
-                const int q = lane & 15, r = q >> 2, c = q & 3;
-                double e = (r == c) ? 1.0 : 0.0;   // identity (theta below epsilon), and the last row
-                if (theta >= 2.2204460492503131e-16 && r < 3 && c < 3) {
-                    double sn, cs;
-                    det_sincos(theta, &sn, &cs);
-                    const double c1 = 1.0 - cs;
-                    const double itheta = 1.0 / theta;
-                    rx *= itheta; ry *= itheta; rz *= itheta;
-                    const double ra = r == 0 ? rx : (r == 1 ? ry : rz), rb = c == 0 ? rx : (c == 1 ? ry : rz);
-                    const double rrt = (r <= c) ? ra * rb : rb * ra;                       // {rx rx, rx ry, rx rz, rx ry, ry ry, ry rz, rx rz, ry rz, rz rz}
-                    // [r]_x = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0}
-                    const int k = r * 3 + c;
-                    const double rxm = k == 1 ? -rz : k == 2 ? ry : k == 3 ? rz : k == 5 ? -rx : k == 6 ? -ry : k == 7 ? rx : 0.0;
-                    const double I = (r == c) ? 1.0 : 0.0;
-                    e = cs * I + c1 * rrt + sn * rxm;
-                }
-                if (r < 3 && c == 3) e = s_result[r];
-                if (lane < 16) s_upd[q] = e;
-            }
-            wave_lds_sync();
-            SSTAMP(5);
-            if (lane < 16) {  // mul44(upd, resultRt) element (i, j)
-                const int i = lane >> 2, j = lane & 3;
-                double sacc = s_upd[i * 4 + 0] * od->resultRt[0 * 4 + j];
-                sacc = sacc + s_upd[i * 4 + 1] * od->resultRt[1 * 4 + j];
-                sacc = sacc + s_upd[i * 4 + 2] * od->resultRt[2 * 4 + j];
-                sacc = sacc + s_upd[i * 4 + 3] * od->resultRt[3 * 4 + j];
-                s_Rt[lane] = sacc;   // (staging: every lane has read the old resultRt before anybody overwrites it)
-            }
-            wave_lds_sync();
-            if (lane < 16) od->resultRt[lane] = s_Rt[lane];
-            wave_lds_sync();
-            // pose composition in f32 (RGBDOdometry.cpp:449-461): Ro / to = (float) resultRt, Rinv = Ro^T, tinv = -(Rinv to),
-            // Rcurr = Rprev Rinv, tcurr = Rprev tinv + tprev -- lane q < 9: Rcurr[q], lanes 9..11: tcurr
-            if (lane < 12) {
-                const double* nrt = od->resultRt;
-                if (lane < 9) {
-                    const int i = lane / 3, j = lane - 3 * (lane / 3);
-                    // Rinv[k * 3 + j] = Ro[j * 3 + k] = (float) nrt[j * 4 + k]
-                    od->Rcurr[lane] = od->Rprev[i * 3 + 0] * (float)nrt[j * 4 + 0] + od->Rprev[i * 3 + 1] * (float)nrt[j * 4 + 1] + od->Rprev[i * 3 + 2] * (float)nrt[j * 4 + 2];
-                } else {
-                    const int r = lane - 9;
-                    const float to0 = (float)nrt[0 * 4 + 3], to1 = (float)nrt[1 * 4 + 3], to2 = (float)nrt[2 * 4 + 3];
-                    float tinv[3];
-#pragma unroll
-                    for (int k = 0; k < 3; k++)   // Rinv[k * 3 + m] = Ro[m * 3 + k]
-                        tinv[k] = -((float)nrt[0 * 4 + k] * to0 + (float)nrt[1 * 4 + k] * to1 + (float)nrt[2 * 4 + k] * to2);
-                    od->tcurr[r] = (od->Rprev[r * 3 + 0] * tinv[0] + od->Rprev[r * 3 + 1] * tinv[1] + od->Rprev[r * 3 + 2] * tinv[2]) + od->tprev[r];
-                }
-            }
-        }
-        SSTAMP(6);
-    } else if (next_level >= 0 && tid == 64) {  // another wave: intrinsics of the next iteration's level
-        double K[9], Kinv[9];
-        k_matrix(cam_level(od->intr, next_level), K);
-        inv33<double>(K, Kinv);
-        for (int k = 0; k < 9; k++) { s_K[k] = K[k]; s_Kinv[k] = Kinv[k]; }
-    }
-    __syncthreads();                                                                       // ---- barrier 2: the new pose; K of the next level
-    if (tid < 64) {
-        const int lane = tid;
-        if (next_level >= 0) {  // prepare_iteration(od, next_level): Rt = inv44_affine(resultRt), krkInv = K R K^-1, kt = K t
-            // inv33 by cofactors (cf_device.h): the determinant in every lane, lane k < 9 its entry (L[p] L[q] - L[r] L[s]) / det
-            const double* a = od->resultRt;
-            const double L0 = a[0], L1 = a[1], L2 = a[2], L3 = a[4], L4 = a[5], L5 = a[6], L6 = a[8], L7 = a[9], L8 = a[10];
-            const double c00 = L4 * L8 - L5 * L7, c01 = L5 * L6 - L3 * L8, c02 = L3 * L7 - L4 * L6;
-            const double det = L0 * c00 + L1 * c01 + L2 * c02;
-            const double id = 1.0 / det;
-            const double Lm[9] = {L0, L1, L2, L3, L4, L5, L6, L7, L8};
-            // o[k] = (L[P] * L[Q] - L[R] * L[S]) * id:  k: 0 (4,8,5,7) 1 (2,7,1,8) 2 (1,5,2,4) 3 (5,6,3,8) 4 (0,8,2,6) 5 (2,3,0,5) 6 (3,7,4,6) 7 (1,6,0,7) 8 (0,4,1,3)
-            const int k9 = lane < 9 ? lane : 0;
-            double p1 = 0, q1 = 0, r1 = 0, s1 = 0;
-#pragma unroll
-            for (int m = 0; m < 9; m++) {
-                constexpr int P[9] = {4, 2, 1, 5, 0, 2, 3, 1, 0}, Q[9] = {8, 7, 5, 6, 8, 3, 7, 6, 4}, Rr[9] = {5, 1, 2, 3, 2, 0, 4, 0, 1}, S[9] = {7, 8, 4, 8, 6, 5, 6, 7, 3};
-                if (k9 == m) { p1 = Lm[P[m]]; q1 = Lm[Q[m]]; r1 = Lm[Rr[m]]; s1 = Lm[S[m]]; }
-            }
-            const double li = (p1 * q1 - r1 * s1) * id;
-            if (lane < 9) s_Rt[(lane / 3) * 4 + (lane - 3 * (lane / 3))] = li;
-            wave_lds_sync();
-            if (lane < 9) {  // tmp = K * R
-                const int i = lane / 3, j = lane - 3 * (lane / 3);
-                s_tmp[lane] = s_K[i * 3 + 0] * s_Rt[0 * 4 + j] + s_K[i * 3 + 1] * s_Rt[1 * 4 + j] + s_K[i * 3 + 2] * s_Rt[2 * 4 + j];
-            } else if (lane >= 16 && lane < 19) {  // translation of the inverse: -(Li row i . t)
-                const int i = lane - 16;
-                s_Rt[i * 4 + 3] = -(s_Rt[i * 4 + 0] * a[3] + s_Rt[i * 4 + 1] * a[7] + s_Rt[i * 4 + 2] * a[11]);
-            }
-            wave_lds_sync();
-            if (lane < 9) {
-                const int i = lane / 3, j = lane - 3 * (lane / 3);
-                od->krkInv[lane] = (float)(s_tmp[i * 3 + 0] * s_Kinv[0 * 3 + j] + s_tmp[i * 3 + 1] * s_Kinv[1 * 3 + j] + s_tmp[i * 3 + 2] * s_Kinv[2 * 3 + j]);
-            } else if (lane >= 16 && lane < 19) {
-                const int r = lane - 16;
-                od->kt[r] = (float)(s_K[r * 3 + 0] * s_Rt[3] + s_K[r * 3 + 1] * s_Rt[7] + s_K[r * 3 + 2] * s_Rt[11]);
-            }
-        } else {
-            if (lane == 0 && od->rgb) {  // end of the schedule: divergence guard (RGBDOdometry.cpp:464-467)
-                const float d0 = od->tcurr[0] - od->tprev[0], d1 = od->tcurr[1] - od->tprev[1], d2 = od->tcurr[2] - od->tprev[2];
-                if ((double)sqrtf(d0 * d0 + d1 * d1 + d2 * d2) > 0.3) {
-                    for (int k = 0; k < 9; k++) od->Rcurr[k] = od->Rprev[k];
-                    for (int k = 0; k < 3; k++) od->tcurr[k] = od->tprev[k];
-                }
-            }
-            if (lane == 0) {  // ... and the inverse of the pose the call ends with, for the index pass that is enqueued before the host sees it
-                float pose[16], inv[16];
-                for (int r = 0; r < 3; r++) { pose[r * 4 + 0] = od->Rcurr[r * 3 + 0]; pose[r * 4 + 1] = od->Rcurr[r * 3 + 1]; pose[r * 4 + 2] = od->Rcurr[r * 3 + 2]; pose[r * 4 + 3] = od->tcurr[r]; }
-                pose[12] = 0; pose[13] = 0; pose[14] = 0; pose[15] = 1;   // (the facade's Model::pose after a tracking call: CoFusion::fetchTracking)
-                inv44f(pose, inv);
-                for (int q = 0; q < 16; q++) od->pose_inv[q] = inv[q];
-            }
-            // ... and the candidate range of a culled tracker: how many record slots each level needed goes back to the host (it sizes the
-            // next call's residual workgroups), the accumulator is cleared for the next call's preparation
-            if (lane >= 32 && lane < 35 && od->res_range) {
-                unsigned* rr = od->res_range + 2 * (lane - 32);
-                const unsigned lo_inv = rr[0], hi_p1 = rr[1];
-                const int sh = __builtin_ctz(slot_px) - 8;
-                od->res_seen[lane - 32] = hi_p1 ? (int)(((hi_p1 - 1u) >> sh) - ((~lo_inv) >> sh)) + 1 : 0;
-                rr[0] = 0; rr[1] = 0;
-            }
-        }
-        SSTAMP(7);
-    } else if (tid >= 128 && tid < 192) {
-        if (next_level >= 0 && cull) {  // an idle wave: the screen box under the new pose
-            int ib[4]; float zb[2];
-            screen_box(od->box_lo, od->box_hi, od->box_R, od->box_t, od->Rcurr, od->tcurr, od->intr, od->distThres, od->width, od->height, tid - 128, ib, zb);
-            if (tid == 128) {
-                od->stats.cull_box[0] = ib[0]; od->stats.cull_box[1] = ib[1]; od->stats.cull_box[2] = ib[2]; od->stats.cull_box[3] = ib[3];
-                od->cull_z[0] = zb[0]; od->cull_z[1] = zb[1];
-            }
-        }
-    } else if (tid == 192) {
-        // another idle wave: the level's flags and the statistics (RGBDOdometry.cpp:371-392, 401-402) -- in the order of the serial code:
-        // stop, statistics, end of level
-        const bool active = s_flags[0] != 0, stop = s_flags[1] != 0;
-        if (stop) od->level_done = 1;
-        if (active) {
-            const int rgbCount = (int)(long long)s_icp[29];
-            const float tmpError = (float)(sqrt((double)(int)(long long)s_icp[30]) / (double)rgbCount);
-            od->lastRGBError = tmpError;
-            od->stats.last_rgb_error = tmpError; od->stats.last_rgb_count = (float)rgbCount;
-            od->stats.last_icp_error = sqrtf(od->residual[0]) / od->residual[1];
-            od->stats.last_icp_count = od->residual[1];
-        }
-        if (last_of_level) { od->level_done = 0; od->lastRGBError = 3.402823466e+38F; }
-        od->solves += 1;   // (whether or not the iteration was active: the host counts launches)
-    }
-    __syncthreads();                                                                       // ---- barrier 3: everything the state will hold
-    {
-        // write-back of the mutable words; the hot block (refresh_hot, cf_kernels.h: GnHot) is derived on the way: hot word w <- its source field
-        constexpr int o_icp = (int)(offsetof(OdomDev, icp) / 4), o_ld = (int)(offsetof(OdomDev, level_done) / 4), o_cz = (int)(offsetof(OdomDev, cull_z) / 4),
-                      o_Rc = (int)(offsetof(OdomDev, Rcurr) / 4), o_tc = (int)(offsetof(OdomDev, tcurr) / 4), o_Ri = (int)(offsetof(OdomDev, Rprev_inv) / 4),
-                      o_tp = (int)(offsetof(OdomDev, tprev) / 4), o_cb = (int)((offsetof(OdomDev, stats) + offsetof(cf_track_stats, cull_box)) / 4),
-                      o_rgb = (int)(offsetof(OdomDev, rgb) / 4), o_ro = (int)(offsetof(OdomDev, rgbOnly) / 4), o_krk = (int)(offsetof(OdomDev, krkInv) / 4),
-                      o_kt = (int)(offsetof(OdomDev, kt) / 4), o_hot = (int)(offsetof(OdomDev, hot) / 4);
-        const unsigned* words = reinterpret_cast<const unsigned*>(&s_od);
-        OdomDev* const twin = god_host ? god_host : s_od.host_twin;
-        const bool to_twin = twin && next_level < 0;   // end of the schedule: the result (pose, statistics, fault word) goes to the tracker's pinned
-                                                       // host copy as well -- the frame's host wait finds it there without a copy command on the stream
-        for (int k = kMutableFrom + tid; k < kWords; k += 256) {
-            unsigned v = words[k];
-            const int w = k - o_hot;
-            if (w >= 0 && w < 48) {
-                const int src = w < 1 ? o_icp : w < 2 ? o_ld : w < 4 ? o_cz + (w - 2) : w < 13 ? o_Rc + (w - 4) : w < 16 ? o_tc + (w - 13) : w < 25 ? o_Ri + (w - 16)
-                              : w < 28 ? o_tp + (w - 25) : w < 32 ? o_cb + (w - 28) : w < 33 ? o_rgb : w < 34 ? o_ro : w < 35 ? o_ld : w < 36 ? -1
-                              : w < 45 ? o_krk + (w - 36) : o_kt + (w - 45);
-                v = src >= 0 ? words[src] : 0u;
-            }
-            reinterpret_cast<unsigned*>(god)[k] = v;
-            if (to_twin) reinterpret_cast<unsigned*>(twin)[k] = v;
-        }
-    }
-    // zero the accumulators for the next iteration, 16 bytes per store (their sums were read in the first flight of loads; stores issued
-    // in front of a barrier would make it wait a memory round trip)
-    {
-        ulonglong2* const zi = reinterpret_cast<ulonglong2*>(icp_acc);
-        ulonglong2* const zr = reinterpret_cast<ulonglong2*>(rgb_acc);
-        for (int k = tid; k < kGroups * 16; k += 256) { zi[k] = make_ulonglong2(0, 0); zr[k] = make_ulonglong2(0, 0); }
-    }
-    SSTAMP(8);
-#ifdef CF_ABLATE
-    if (g_solve_trace && threadIdx.x == 0 && blockIdx.x == 0) g_solve_iter++;
-#endif
-}
-
-__global__ void __launch_bounds__(256) gn_solve_kernel(const GnArgs args, int next_level, int last_of_level)
-{
-    gn_solve_body(args.icp_gram ? -1 : kFixICP, args.od[blockIdx.x], args.icp_acc[blockIdx.x], args.rgb_acc[blockIdx.x], next_level, last_of_level, args.od_host[blockIdx.x], args.slot_px);
-}
-
-// RGB step over the per-workgroup record slots the residual pass left (grid: one workgroup per slot x models).  A slot holds at
-// most 4 x producer-workgroup-size records and typically < 10 % of that; thread r reads record r of its slot speculatively together
-// with the slot's count, so the pass has the same two dependent memory round trips as rgb_step_kernel on a tenth of the bytes.
-//
-// Measured and dropped (round 2, profiles/r02b): running this pass and the solve in ONE launch -- 32 workgroups per model reduce a
-// global list, fence, arrive at a counter, workgroup 0 waits and solves.  22.6 us per launch against 6.3 + 8.4 us for the two
-// separate kernels plus one boundary: the device-scope release fence and the arrival wait cost more than a kernel boundary does.
-__device__ __forceinline__ void rgb_slot_step_body(const RgbArgs& ra, int n_slots)
-{
-    const RgbModelArgs m = ra.m[blockIdx.y];
-    asm volatile("" :: "s"(m.st), "s"(m.icp_acc), "s"(m.rgb_acc), "s"(m.recs), "s"(m.slot_counts), "s"(m.res_range), "s"(m.cloud), "s"(m.dIdx), "s"(m.dIdy),
-                 "s"(ra.cols), "s"(ra.rows), "s"(ra.slot_px), "s"(ra.sobelScale), "s"(ra.il.fx), "s"(ra.il.fy));
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t slot0 = (size_t)blockIdx.x * ra.slot_px;
-    // ONE flight of loads: the slot's count, this thread's record (speculative: valid if tid < n) and -- first wave -- the two words of the
-    // accumulator groups that give sigma, all pinned in front of the uniform `n == 0` exit.  Without the pin the compiler sinks the record
-    // and accumulator loads below that exit: three dependent round trips (count -> records + sums -> gathers) where two will do (round 6,
-    // from the ISA: the `speculative` load of round 2 had not been speculative in the binary).
-    unsigned n = m.slot_counts[blockIdx.x];
-    const size_t Npx = (size_t)ra.cols * ra.rows;
-    uint2 rc = m.recs[slot0 + tid < Npx ? slot0 + tid : Npx - 1];   // (unconditional, address clamped: a load under a branch is waited for at its end)
-    unsigned long long g_cnt = 0, g_sig = 0;
-    if (tid < 64) { g_cnt = m.icp_acc[(size_t)tid * 32 + 29]; g_sig = m.icp_acc[(size_t)tid * 32 + 30]; }   // kGroups == 64 == lanes
-    asm volatile("" ::: "memory");   // (the vector loads are issued in front of the scalar round trip of the tracker's hot state, not behind it)
-    SlotRange sr;
-    const RgbHot hs = rgb_hot_and_range(ra, m, n_slots, sr);
-    asm volatile("" : "+v"(n), "+v"(rc.x), "+v"(rc.y), "+v"(g_cnt), "+v"(g_sig));
-    // (a slot outside a culled tracker's candidate range was not visited by the residual pass: its count is stale, it holds nothing)
-    if ((int)blockIdx.x < sr.first || (int)blockIdx.x > sr.last) n = 0;
-    if (!(hs.rgb && !hs.level_done) || n == 0) return;  // uniform
-    __shared__ float s_sigma;
-    if (tid < 64) {
-        // sigma_val_from takes the LOW 32 bits of the two totals (the reference's `int` count and sigma), and the low word of a sum is the
-        // wrapping sum of the low words: a 32-bit reduction over the 64 groups -- four DPP steps inside the rows of 16 lanes, the four row
-        // totals added on the scalar unit -- instead of twelve dependent LDS shuffles of 64-bit values (0.35 us of this launch)
-        const unsigned c32 = wave_sum_u32((unsigned)g_cnt), s32 = wave_sum_u32((unsigned)g_sig);
-        if (tid == 0) s_sigma = sigma_val_from((int)c32, (int)s32, hs.rgbOnly);
-    }
-    __syncthreads();
-    const float sigma = s_sigma;
-    const int F = rgb_fix_bits(sigma);
-    const float lim = ldexpf(1.0f, (50 - F) / 2), scale = ldexpf(1.0f, F);
-    unsigned long long acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; k++) acc[k] = 0;
-    unsigned long long terms = 0;
-    for (unsigned r = tid; r < n; r += 256) {
-        if (r >= 256) rc = m.recs[slot0 + r];
-        float row[7];
-        rgb_step_row(ra, m, sigma, (float)((int)(rc.y >> 22) - 256), (int)rc.x, (int)(rc.y & 0x3fffffu), row);
-        se3_accumulate_dyn(row, acc, lim, scale);
-        terms++;
-    }
-    unsigned long long v = 0;
-    if (__any(terms != 0)) {
-#pragma unroll
-        for (int k = 0; k < 28; k++) acc[k] -= terms * kMagicBits;
-        acc[28] = terms;
-        v = wave_reduce32_u64(acc, lane);
-    }
-    block_commit32<4>(v, lane, wave, 4, m.rgb_acc + (size_t)(blockIdx.x % kGroups) * 32);
-}
-__global__ void __launch_bounds__(256) rgb_slot_step_kernel(const RgbArgs ra, int n_slots) { rgb_slot_step_body(ra, n_slots); }
-// ... and, on the last level-0 iteration, the error surfaces of the culled trackers in the SAME launch (workgroups behind the record
-// slots; until late in round 6 icp_error_surface_kernel ran as a launch of its own between the {ICP || residual} launch and this one:
-// 6.5 us + a launch boundary on the Gauss-Newton chain of every frame).  Both read the tracker state the solve has not touched yet.
-__global__ void __launch_bounds__(256) rgb_slot_step_err_kernel(const RgbArgs ra, int n_slots, const IcpArgs e)
-{
-    if ((int)blockIdx.x >= n_slots) { icp_error_surface_body(e, e.m[blockIdx.y], (int)blockIdx.x - n_slots); return; }
-    rgb_slot_step_body(ra, n_slots);
-}
-
-// MODE 2 (round 5): the RGB step and the solve in ONE launch.  Rounds 2-3 measured this twice with device-scope synchronisation and lost
-// both times (a release fence per workgroup writes the XCD's L2 back; returning device-scope atomics cost a memory round trip each).
-// What round 4's SO(3) kernel showed is that workgroups of ONE XCD can meet in its L2 for ~1.5 us: so the step workgroups of tracker m
-// are placed on XCD m mod 8 (hardware workgroup b runs on XCD b mod 8: tools/microbench/xcc_map.hip), add their sums with
-// workgroup-scope atomics -- performed in that L2 --, wait for them, and take a ticket there.  Nobody waits for anybody: the workgroup
-// that draws the last ticket runs the solve (gn_solve_body reads the RGB sums back from the L2 with agent-scope loads), the others
-// leave.  What the solve writes (state, cleared accumulators, the ticket counter) is written back at the end of the kernel like any
-// other store.  One launch boundary (~2.5 us) and the solve kernel's own ramp less per Gauss-Newton iteration: 57 -> 38 launches per
-// frame.  The sums are integers: which workgroup adds what, and who solves, does not change a bit.
-// Grid: 8 x n_quads x ceil(n / 8) workgroups, n_quads = ceil(n_slots / 2) (two record slots per workgroup), b = 8 * (quad + n_quads * (m / 8)) + m % 8.
-__global__ void __launch_bounds__(256) rgb_step_solve_kernel(const RgbArgs ra, So3Sync* __restrict__ syncs, int n_slots, int n_quads, IDiv quad_div,
-                                                             int n, int icp_fix, int next_level, int last_of_level)
-{
-    const int b = (int)blockIdx.x;
-#ifdef CF_ABLATE
-    unsigned long long* const tr = g_icp_trace ? g_icp_trace + (size_t)b * 8 : nullptr;
-    if (tr && threadIdx.x == 0) { tr[0] = wall_clock64(); tr[1] = tr[2] = tr[3] = tr[4] = 0; tr[5] = 0xffff; }
-#define STAMP(k) do { if (tr && threadIdx.x == 0) tr[k] = wall_clock64(); } while (0)
-#else
-#define STAMP(k) do {} while (0)
-#endif
-    const int q = b >> 3, hi = n_quads > 1 ? idiv(q, quad_div) : q;
-    const int model = (b & 7) + 8 * hi, quad = q - hi * n_quads;
-    if (model >= n) return;
-    const RgbModelArgs& m = ra.m[model];
-    const RgbHot hs = rgb_hot((StatePtr)m.st);
-    SlotRange sr = residual_slot_range(ra, m, n_slots);
-    const bool no_slot = sr.last < sr.first;   // a culled tracker without a single candidate: its first workgroup stands in (and solves)
-    if (no_slot) { sr.first = 0; sr.last = 0; }
-    const int qf = sr.first >> 1, ql = sr.last >> 1;
-    if (quad < qf || quad > ql) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Two record slots per workgroup, two waves per slot (`quad`: the pair's index).  The tracker's workgroups share ONE XCD: a workgroup
-    // per slot (round 4's shape) makes the background's 300 slots two rounds of residency there (measured: +4 us), a WAVE per slot leaves a
-    // slot with 700 records to eleven dependent passes of one wave (measured: +8 us).  150 workgroups x 4 waves fit the XCD in one round.
-    const int slot = quad * 2 + (wave >> 1), half = tid & 127;
-    const bool slot_ok = !no_slot && slot >= sr.first && slot <= sr.last;
-    const size_t slot0 = (size_t)slot * ra.slot_px;
-    const unsigned nrec = slot_ok ? m.slot_counts[slot] : 0u;
-    uint2 rc = make_uint2(0, 0);
-    if (slot_ok && slot0 + half < (size_t)ra.cols * ra.rows) rc = m.recs[slot0 + half];   // speculative: valid if half < nrec
-    if (hs.rgb && !hs.level_done) {  // uniform
-        unsigned long long v = 0;
-        if (nrec != 0) {   // (wave-uniform)
-            const long long cnt = (long long)group_sum(m.icp_acc, 29, lane);
-            const long long sg = (long long)group_sum(m.icp_acc, 30, lane);
-            const float sigma = sigma_val_from((int)cnt, (int)sg, hs.rgbOnly);
-            const int F = rgb_fix_bits(sigma);
-            const float lim = ldexpf(1.0f, (50 - F) / 2), scale = ldexpf(1.0f, F);
-            unsigned long long acc[32];
-#pragma unroll
-            for (int k = 0; k < 32; k++) acc[k] = 0;
-            unsigned long long terms = 0;
-            for (unsigned r = half; r < nrec; r += 128) {
-                if (r >= 128) rc = m.recs[slot0 + r];
-                float row[7];
-                rgb_step_row(ra, m, sigma, (float)((int)(rc.y >> 22) - 256), (int)rc.x, (int)(rc.y & 0x3fffffu), row);
-                se3_accumulate_dyn(row, acc, lim, scale);
-                terms++;
-            }
-            if (__any(terms != 0)) {
-#pragma unroll
-                for (int k = 0; k < 28; k++) acc[k] -= terms * kMagicBits;
-                acc[28] = terms;
-                v = wave_reduce32_u64(acc, lane);
-            }
-        }
-        STAMP(1);
-        block_store32(v, lane, wave, m.rgb_acc + (size_t)quad * 32);
-    } else if (tid < 32) m.rgb_acc[(size_t)quad * 32 + tid] = 0;
-#ifdef CF_ABLATE
-    if (tr && threadIdx.x == 0) tr[5] = (unsigned long long)model;
-#endif
-    // The tickets, drawn by the wave that issued the atomics, once the L2 has taken them.  Two levels: returning atomics on ONE address
-    // take the L2 ~17 ns each, so a workgroup draws from the counter of its quad's residue class mod kStepSubs (each in a cache line of
-    // its own), and the last of a class draws from the tracker's top counter.
-    __shared__ int s_last;
-    So3Sync* const sync = syncs + model;
-    if (tid < 64) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(2);
-        if (tid == 0) {
-            static_assert(kStepSubs == 16, "the class arithmetic below shifts by 4");
-            const int j = quad & (kStepSubs - 1);
-            // quads = j (mod kStepSubs) inside [qf, ql]; classes that have any
-            const unsigned in_class = (unsigned)(((ql - j) >> 4) - ((qf - 1 - j) >> 4));
-            const int span = ql - qf + 1;
-            const unsigned classes = (unsigned)(span < kStepSubs ? span : kStepSubs);
-            int last = 0;
-            if (__hip_atomic_fetch_add(&sync->step_sub[j][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == in_class - 1u) {
-                sync->step_sub[j][0] = 0;   // (every ticket of this class is drawn; the next launch finds the counter cleared)
-                if (__hip_atomic_fetch_add(&sync->step_top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == classes - 1u) { sync->step_top = 0; last = 1; }
-            }
-            s_last = last;
-        }
-    }
-    STAMP(3);
-    __syncthreads();
-    if (!s_last) return;
-    OdomDev* const god = m.st;
-    gn_solve_body<true>(icp_fix, god, m.icp_acc, m.rgb_acc, next_level, last_of_level, nullptr, ra.slot_px, qf, ql);
-    STAMP(4);
-#undef STAMP
-}
-
-// total of the grouped accumulator -> out[32] (stand-alone steps)
-__global__ void __launch_bounds__(64) acc_total_kernel(const unsigned long long* __restrict__ acc, unsigned long long* __restrict__ out)
-{
-    for (int w = 0; w < 32; w++) {
-        const unsigned long long v = group_sum(acc, w, threadIdx.x);
-        if (threadIdx.x == 0) out[w] = v;
-    }
-}
-
-// Split reductions (one tracker's image rows over several GPUs): a rank's partial sums are FOLDED before they travel -- the 64 accumulator
-// groups of every split tracker summed into group 0, the other groups cleared -- so that the all-reduce of the Gauss-Newton loop carries
-// the 32 words of the 6x6 system (256 bytes: north_star's "RCCL all-reduce of the 6x6 system") instead of the 16 KB of grouped partial
-// sums it carried until round 5.  Everybody downstream (the RGB step's sigma, the solve) sums the groups as before
-// and finds the totals in group 0 and zeros elsewhere: integer sums, the same bits.
-struct FoldArgs { unsigned long long* acc[kMaxBatch]; };
-__global__ void __launch_bounds__(64) acc_fold_kernel(const FoldArgs a)
-{
-    unsigned long long* __restrict__ acc = a.acc[blockIdx.x];
-    const int lane = threadIdx.x;
-    unsigned long long tot = 0;
-#pragma unroll 4
-    for (int w = 0; w < 32; w++) { const unsigned long long v = group_sum(acc, w, lane); if (lane == w) tot = v; }
-    for (int w = 0; w < 32; w++) acc[(size_t)lane * 32 + w] = 0;   // (every load above has been consumed by a shuffle: the wave is past them)
-    if (lane < 32) acc[lane] = tot;                                  // (same wave, program order: behind the zeroes of group 0)
-}
+namespace cf {
 
 // ------------------------------------------------------------------------------ launchers ----
 // ev0/ev1 (nullable) receive the dispatch's own begin/end timestamps (the figures rocprofv3 reports), not the
@@ -1926,11 +772,32 @@ __global__ void __launch_bounds__(64) acc_fold_kernel(const FoldArgs a)
 #ifdef CF_ABLATE
 static IcpArgs g_last_icp_args; static int g_last_n_icp_blocks = 0, g_last_grid = 0;
 #endif
-template <int TAG, bool GRAM>
-static void launch_icp_kernel_arith(hipStream_t s, IcpLaunch cfg, const IcpArgs& args_in, const RgbArgs& ra_in, bool icp, int n_res_blocks, int n,
-                                    hipEvent_t ev0, hipEvent_t ev1)
+static IcpArgs with_cdiv(IcpArgs a) { a.cdiv = make_idiv(a.cols); return a; }
+// the instantiations of icp_reduce_kernel, [tag][pixels per lane 1 / 2 / 4][gram]: distinct symbols per pyramid level so that
+// rocprofv3 --stats separates them (tag = level for one model, level + 4 for lock-step batches of several models; no tag 3)
+typedef void (*IcpKernel)(const IcpArgs, const RgbArgs, int);
+#define ICP_TAG(T) {{icp_reduce_kernel<1, T, false>, icp_reduce_kernel<1, T, true>}, {icp_reduce_kernel<2, T, false>, icp_reduce_kernel<2, T, true>}, \
+                    {icp_reduce_kernel<4, T, false>, icp_reduce_kernel<4, T, true>}}
+static constexpr IcpKernel kIcpKernels[7][3][2] = {ICP_TAG(0), ICP_TAG(1), ICP_TAG(2), {}, ICP_TAG(4), ICP_TAG(5), ICP_TAG(6)};
+#undef ICP_TAG
+// plain launch when both events are null (also what a stream capture records), hipExtLaunchKernelGGL with the events otherwise
+static void launch_plain_or_timed(IcpKernel kernel, dim3 grid, dim3 block, unsigned lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const IcpArgs& args,
+                              const RgbArgs& ra, int n_icp_blocks)
 {
-    IcpArgs args = args_in; args.cdiv = make_idiv(args.cols);
+    if (!ev0 && !ev1) kernel<<<grid, block, lds, s>>>(args, ra, n_icp_blocks);
+    else hipExtLaunchKernelGGL(kernel, grid, block, lds, s, ev0, ev1, 0, args, ra, n_icp_blocks);
+}
+
+static void launch_icp_rgbres(hipStream_t s, IcpLaunch cfg, const IcpArgs& args_in, const RgbArgs& ra_in, bool icp, bool rgb, int n, int level,
+                              hipEvent_t ev0, hipEvent_t ev1)
+{
+    // pixels per lane of unculled trackers, 0 = the library's choice: two at level 0 in the product form -- half the waves of the launch's
+    // largest slot for the same loads in flight, 12.4 against 13.0 us with five trackers since the accumulators live in LDS (round 5; with
+    // them in registers two pixels cost a wave of occupancy and lost) --, one on the small levels and in the Gram form
+    if (cfg.ppt == 0) cfg.ppt = (level == 0 && !cfg.gram) ? 2 : 1;
+    const int res_per_block = cfg.threads * (ra_in.compact ? 4 : 1);  // compact list pass: four pixels per thread
+    const int n_res_blocks = rgb ? ((icp ? args_in.cols * args_in.rows : ra_in.cols * ra_in.rows) + res_per_block - 1) / res_per_block : 0;
+    IcpArgs args = with_cdiv(args_in);
     RgbArgs ra = ra_in; ra.cdiv = make_idiv(ra.cols);
     const int N = ((args.row_end > 0 ? args.row_end : args.rows) - args.row_begin) * args.cols;
     const int per_block = cfg.threads * cfg.ppt;
@@ -1942,7 +809,7 @@ static void launch_icp_kernel_arith(hipStream_t s, IcpLaunch cfg, const IcpArgs&
     int blocks[kMaxBatch];
     for (int m = 0; m < n; m++) {
         IcpModelArgs& ma = args.m[m];
-        const bool ok = icp && ma.cull && ma.box_blocks > 0 && !GRAM && (!(args.flags & 1) || (args.flags & 2)) && args.row_end == 0 && ma.row_end == 0;
+        const bool ok = icp && ma.cull && ma.box_blocks > 0 && !cfg.gram && (!(args.flags & 1) || (args.flags & 2)) && args.row_end == 0 && ma.row_end == 0;
         ma.box_blocks = ok ? (ma.box_blocks < full ? ((ma.box_blocks + 7) / 8) * 8 : full) : 0;
         blocks[m] = ok ? ma.box_blocks : full;
     }
@@ -1966,7 +833,7 @@ static void launch_icp_kernel_arith(hipStream_t s, IcpLaunch cfg, const IcpArgs&
     }
     // ORDER OF THE SLOTS = order of dispatch: the culled trackers' runs (the longest chain of dependent round trips: box, depth interval,
     // planes, occupancy, gather), the unculled ICP reductions, then the residual passes.  Seven orders were measured in round 5 (longest work
-    // first, residual passes first, ...; a diagnostics build reads CF_ICP_ORDER): 13.8-14.0 us for this one, 14.0-14.5 us for the others --
+    // first, residual passes first, ...; profiles/r5v_bench_icp_slot_orders.txt): 13.8-14.0 us for this one, 14.0-14.5 us for the others --
     // the launch is a little over one round of resident workgroups and its length is the sum of everybody's residency, not its tail
     // (tools/icp_trace_summary.py).  Every slot is padded to a multiple of 8 workgroups so that the hardware workgroup id and the
     // slot-local index agree on the XCD; the padding leaves at once.
@@ -1976,92 +843,18 @@ static void launch_icp_kernel_arith(hipStream_t s, IcpLaunch cfg, const IcpArgs&
         args.slot_end[slot] = total; args.slot_desc[slot] = (unsigned char)(m | (residual ? kResidualSlot : 0)); slot++;
         if (!residual) n_icp_blocks += count;
     };
-#ifdef CF_ABLATE
-    static const int order = getenv("CF_ICP_ORDER") ? atoi(getenv("CF_ICP_ORDER")) : 0;
-#else
-    constexpr int order = 0;
-#endif
-    const bool res = n_res_blocks > 0;
-    auto culled = [&](int m) { return args.m[m].box_blocks > 0 || (args.m[m].cull && ra.m[m].res_range); };
-    if (order == 0) {          // rounds 3-4: culled ICP, unculled ICP, residual passes
-        for (int pass = 0; pass < 2 && icp; pass++) for (int m = 0; m < n; m++) if ((args.m[m].box_blocks > 0) == (pass == 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) add(m, true, ra.m[m].res_blocks);
-    } else if (order == 4) {   // culled ICP, unculled residual, unculled ICP, culled residual
-        for (int m = 0; m < n && icp; m++) if (args.m[m].box_blocks > 0) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (!culled(m)) add(m, true, ra.m[m].res_blocks);
-        for (int m = 0; m < n && icp; m++) if (!(args.m[m].box_blocks > 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (culled(m)) add(m, true, ra.m[m].res_blocks);
-    } else if (order == 5) {   // culled ICP, unculled ICP, culled residual, unculled residual
-        for (int pass = 0; pass < 2 && icp; pass++) for (int m = 0; m < n; m++) if ((args.m[m].box_blocks > 0) == (pass == 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (culled(m)) add(m, true, ra.m[m].res_blocks);
-        for (int m = 0; m < n && res; m++) if (!culled(m)) add(m, true, ra.m[m].res_blocks);
-    } else if (order == 6) {   // unculled ICP, culled ICP, residual passes
-        for (int pass = 0; pass < 2 && icp; pass++) for (int m = 0; m < n; m++) if ((args.m[m].box_blocks > 0) == (pass == 1)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) add(m, true, ra.m[m].res_blocks);
-    } else if (order == 2) {   // unculled ICP, unculled residual, culled ICP, culled residual
-        for (int m = 0; m < n && icp; m++) if (!(args.m[m].box_blocks > 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (!culled(m)) add(m, true, ra.m[m].res_blocks);
-        for (int m = 0; m < n && icp; m++) if (args.m[m].box_blocks > 0) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (culled(m)) add(m, true, ra.m[m].res_blocks);
-    } else if (order == 3) {   // unculled residual, culled ICP, unculled ICP, culled residual
-        for (int m = 0; m < n && res; m++) if (!culled(m)) add(m, true, ra.m[m].res_blocks);
-        for (int m = 0; m < n && icp; m++) if (args.m[m].box_blocks > 0) add(m, false, blocks[m]);
-        for (int m = 0; m < n && icp; m++) if (!(args.m[m].box_blocks > 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (culled(m)) add(m, true, ra.m[m].res_blocks);
-    } else {                   // longest first
-        for (int m = 0; m < n && res; m++) if (!culled(m)) add(m, true, ra.m[m].res_blocks);
-        for (int m = 0; m < n && icp; m++) if (!(args.m[m].box_blocks > 0)) add(m, false, blocks[m]);
-        for (int m = 0; m < n && icp; m++) if (args.m[m].box_blocks > 0) add(m, false, blocks[m]);
-        for (int m = 0; m < n && res; m++) if (culled(m)) add(m, true, ra.m[m].res_blocks);
-    }
+    for (int pass = 0; pass < 2 && icp; pass++) for (int m = 0; m < n; m++) if ((args.m[m].box_blocks > 0) == (pass == 0)) add(m, false, blocks[m]);
+    for (int m = 0; m < n && n_res_blocks > 0; m++) add(m, true, ra.m[m].res_blocks);
     args.slots_used = slot;
     for (; slot < kMaxSlots; slot++) { args.slot_end[slot] = 0x7fffffff; args.slot_desc[slot] = 0; }
     const dim3 grid(total);
 #ifdef CF_ABLATE
     g_last_icp_args = args; g_last_n_icp_blocks = n_icp_blocks; g_last_grid = (int)grid.x;
 #endif
-    const unsigned lds = GRAM ? (unsigned)(cfg.threads / 64) * kGramWaveDwords * sizeof(int) : 0u;
-    if (!ev0 && !ev1) {  // plain launches (also what a stream capture records)
-        switch (cfg.ppt) {
-            case 4: icp_reduce_kernel<4, TAG, GRAM><<<grid, dim3(cfg.threads), lds, s>>>(args, ra, n_icp_blocks); break;
-            case 2: icp_reduce_kernel<2, TAG, GRAM><<<grid, dim3(cfg.threads), lds, s>>>(args, ra, n_icp_blocks); break;
-            default: icp_reduce_kernel<1, TAG, GRAM><<<grid, dim3(cfg.threads), lds, s>>>(args, ra, n_icp_blocks); break;
-        }
-        return;
-    }
-    switch (cfg.ppt) {
-        case 4: hipExtLaunchKernelGGL((icp_reduce_kernel<4, TAG, GRAM>), grid, dim3(cfg.threads), lds, s, ev0, ev1, 0, args, ra, n_icp_blocks); break;
-        case 2: hipExtLaunchKernelGGL((icp_reduce_kernel<2, TAG, GRAM>), grid, dim3(cfg.threads), lds, s, ev0, ev1, 0, args, ra, n_icp_blocks); break;
-        default: hipExtLaunchKernelGGL((icp_reduce_kernel<1, TAG, GRAM>), grid, dim3(cfg.threads), lds, s, ev0, ev1, 0, args, ra, n_icp_blocks); break;
-    }
-}
-template <int TAG>
-static void launch_icp_kernel(hipStream_t s, IcpLaunch cfg, const IcpArgs& args, const RgbArgs& ra, bool icp, int n_res_blocks, int n,
-                              hipEvent_t ev0, hipEvent_t ev1)
-{
-    if (cfg.gram) launch_icp_kernel_arith<TAG, true>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-    else launch_icp_kernel_arith<TAG, false>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-}
-
-static void launch_icp_rgbres(hipStream_t s, IcpLaunch cfg, const IcpArgs& args, const RgbArgs& ra, bool icp, bool rgb, int n, int level,
-                              hipEvent_t ev0, hipEvent_t ev1)
-{
-    // pixels per lane of unculled trackers, 0 = the library's choice: two at level 0 in the product form -- half the waves of the launch's
-    // largest slot for the same loads in flight, 12.4 against 13.0 us with five trackers since the accumulators live in LDS (round 5; with
-    // them in registers two pixels cost a wave of occupancy and lost) --, one on the small levels and in the Gram form
-    if (cfg.ppt == 0) cfg.ppt = (level == 0 && !cfg.gram) ? 2 : 1;
-    const int N = (icp ? args.cols * args.rows : ra.cols * ra.rows);
-    const int res_per_block = cfg.threads * (ra.compact ? 4 : 1);  // compact list pass: four pixels per thread
-    const int n_res_blocks = rgb ? (N + res_per_block - 1) / res_per_block : 0;
-    // distinct symbols per pyramid level so that rocprofv3 --stats separates them
-    // (tag = level for one model, level + 4 for lock-step batches of several models)
-    if (n > 1) {
-        if (level == 0) launch_icp_kernel<4>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-        else if (level == 1) launch_icp_kernel<5>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-        else launch_icp_kernel<6>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-    } else if (level == 0) launch_icp_kernel<0>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-    else if (level == 1) launch_icp_kernel<1>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
-    else launch_icp_kernel<2>(s, cfg, args, ra, icp, n_res_blocks, n, ev0, ev1);
+    const unsigned lds = cfg.gram ? (unsigned)(cfg.threads / 64) * kGramWaveDwords * sizeof(int) : 0u;
+    const int tag = (level == 0 ? 0 : level == 1 ? 1 : 2) + (n > 1 ? 4 : 0), ppt_index = cfg.ppt == 4 ? 2 : cfg.ppt == 2 ? 1 : 0;
+    static_assert(kIcpKernels[3][0][0] == nullptr && kIcpKernels[2][2][1] && kIcpKernels[4][0][0], "tags are level (0..2) or level + 4: row 3 is never looked up");
+    launch_plain_or_timed(kIcpKernels[tag][ppt_index][cfg.gram ? 1 : 0], grid, dim3(cfg.threads), lds, s, ev0, ev1, args, ra, n_icp_blocks);
 }
 
 void launch_icp_level(hipStream_t s, IcpLaunch cfg, const IcpArgs& args, int n, int level, hipEvent_t ev0, hipEvent_t ev1)
@@ -2141,8 +934,7 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
             const bool err_here = err_aside && i == 0 && last_of_level;
             const bool err_with_step = err_here && rgb && slots && mode != 2;
             if (err_here && !err_with_step) {
-                IcpArgs e = icp_args[i]; e.cdiv = make_idiv(e.cols);
-                icp_error_surface_kernel<<<dim3((N + 255) / 256, n), 256, 0, s>>>(e);
+                icp_error_surface_kernel<<<dim3((N + 255) / 256, n), 256, 0, s>>>(with_cdiv(icp_args[i]));
             }
             if (hook && hook->fn) {  // split reductions: the partial sums of this rank's row band become the totals on every rank
                 FoldArgs fa{}; int nf = 0;
@@ -2160,10 +952,8 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
             if (rgb) {
                 if (slots) {
                     const int n_slots = (N + ra.slot_px - 1) / ra.slot_px;
-                    if (err_with_step) {
-                        IcpArgs e = icp_args[i]; e.cdiv = make_idiv(e.cols);
-                        rgb_slot_step_err_kernel<<<dim3(n_slots + (N + 255) / 256, n), 256, 0, s>>>(ra, n_slots, e);
-                    } else rgb_slot_step_kernel<<<dim3(n_slots, n), 256, 0, s>>>(ra, n_slots);
+                    if (err_with_step) rgb_slot_step_err_kernel<<<dim3(n_slots + (N + 255) / 256, n), 256, 0, s>>>(ra, n_slots, with_cdiv(icp_args[i]));
+                    else rgb_slot_step_kernel<<<dim3(n_slots, n), 256, 0, s>>>(ra, n_slots);
                 }
                 else rgb_step_kernel<<<dim3((N + 255) / 256, n), 256, 0, s>>>(ra);
             }

@@ -5,7 +5,7 @@ Per case the SAME api.Odometry objects are re-prepared step after step, so from 
 the culled-slot mapping (icp_reduce_body, the box_blocks > 0 branch); every case asserts through cf_odom_last_launch_shape that it did.
 Everything is compared bit for bit: culled == unculled == oracle.
 
-Where the launcher is specified to drop the culled-slot mapping (launch_icp_kernel_arith), and what the tests therefore expect:
+Where the launcher is specified to drop the culled-slot mapping (launch_icp_rgbres), and what the tests therefore expect:
   * step 0 of every case: no hint yet (icp_blocks == 0 everywhere);
   * trackers with culling off (the full-image tracker of the batched cases), and rgb_only (no ICP slots): 0;
   * pyramid=False: levels 1 and 2 do not run: 0 there;
@@ -212,7 +212,7 @@ def test_single_tracker_case(contexts, name, launch):
                     assert a[1].tobytes() == np.ascontiguousarray(st[:3, :3]).tobytes(), f"{what}: rotation moved"
                 assert a[2].last_icp_count == 0 and a[2].last_rgb_count == 0, what
             if name == "whole_image" and s > 0:
-                # capped at the full grid of the launch (launch_icp_kernel_arith: `full`, at the level's pixels per lane)
+                # capped at the full grid of the launch (launch_icp_rgbres: `full`, at the level's pixels per lane)
                 for l in range(3):
                     ppt = launch[1] if launch[1] else (2 if l == 0 else 1)
                     n = (W >> l) * (H >> l)
@@ -255,6 +255,25 @@ def _batched(contexts, name, order=None, launch=(256, 1)):
 @pytest.mark.parametrize("launch", LAUNCHES, ids=lambda l: f"{l[0]}x{l[1]}")
 def test_batch_mixed_5(contexts, launch):
     _batched(contexts, "batch_mixed_5", launch=launch)
+
+
+@pytest.mark.parametrize("gn_mode", [0, 2])
+def test_batch_mixed_5_gn_modes(contexts, gn_mode):
+    """the same case, the same comparison with the oracle, under the two other data paths of the RGB step (cf_set_gn_mode 0: DataTerm records and
+    rgb_step_kernel, the culled trackers' error surfaces by a launch of their own; 2: rgb_step_solve_kernel, the step's last workgroup solves),
+    which share their sums with the default path's kernels.  Mode 2 needs workgroups dealt round-robin over 8 XCDs: refused with CF_ESTATE elsewhere."""
+    from co_fusion_amd import api
+    ctx = contexts(tc.BY_NAME["batch_mixed_5"])
+    try:
+        ctx.set_gn_mode(gn_mode)
+    except api.CofusionError as e:
+        if gn_mode == 2 and "cf_set_gn_mode 2:" in str(e):   # the library's own refusal (CF_ESTATE): no round-robin placement here
+            pytest.skip(str(e))
+        raise
+    try:
+        _batched(contexts, "batch_mixed_5", launch=LAUNCHES[0])
+    finally:
+        ctx.set_gn_mode(1)
 
 
 @pytest.mark.parametrize("order", list(tc.BATCH_ORDERS), ids=lambda o: o)
