@@ -278,6 +278,39 @@ class Context:
         opts = TrackOpts(int(rgb_only), int(pyramid), int(fast_odom), int(so3), icp_weight)
         self._check(self.lib.cf_odom_track_batch_async(self.h, oo, n, pp, C.byref(opts), ee))
 
+    def _batch_args(self, odoms, poses):
+        n = len(odoms)
+        self._keep_poses = [_f(np.asarray(p, np.float32).reshape(16)) for p in poses]
+        pp = (C.POINTER(C.c_float) * max(n, 1))(*[C.cast(k, C.POINTER(C.c_float)) for k in self._keep_poses])
+        oo = (C.c_void_p * max(n, 1))(*[o.h for o in odoms])
+
+        def ptrs(ts):
+            if ts is None:
+                return None
+            assert len(ts) == n
+            return (C.c_void_p * max(n, 1))(*[None if t is None else t.data_ptr() for t in ts])
+        return n, oo, pp, ptrs
+
+    def init_models_batch_select(self, odoms, pred_v4, pred_n4, pred_rgba, poses, frame_rgba, alt_v4=None, alt_n4=None, alt_rgba=None,
+                                 fill_counts=None, ratio=0.0):
+        """cf_odom_init_models_batch_select: initICPModel + initRGBModel + initRGB of all trackers in the same launches.  One device
+        tensor per tracker in every list; alt_* / fill_counts (int32 [2] device tensors holding the u32 counts covered, total) may be
+        None, and so may single entries of fill_counts"""
+        n, oo, pp, ptrs = self._batch_args(odoms, poses)
+        self._check(self.lib.cf_odom_init_models_batch_select(self.h, oo, n, ptrs(pred_v4), ptrs(pred_n4), ptrs(pred_rgba), ptrs(alt_v4),
+                                                              ptrs(alt_n4), ptrs(alt_rgba), ptrs(fill_counts), C.c_float(ratio), pp,
+                                                              ptrs(frame_rgba)))
+
+    def init_models_batch_frames(self, odoms, pred_v4, pred_n4, pred_rgba, poses, frame_rgba):
+        """cf_odom_init_models_batch_frames: one frame image per tracker, no device-side choice"""
+        n, oo, pp, ptrs = self._batch_args(odoms, poses)
+        self._check(self.lib.cf_odom_init_models_batch_frames(self.h, oo, n, ptrs(pred_v4), ptrs(pred_n4), ptrs(pred_rgba), pp, ptrs(frame_rgba)))
+
+    def init_models_batch(self, odoms, pred_v4, pred_n4, pred_rgba, poses, frame_rgba):
+        """cf_odom_init_models_batch: all trackers track the one frame image"""
+        n, oo, pp, ptrs = self._batch_args(odoms, poses)
+        self._check(self.lib.cf_odom_init_models_batch(self.h, oo, n, ptrs(pred_v4), ptrs(pred_n4), ptrs(pred_rgba), pp, _p(frame_rgba)))
+
     def set_icp_arith(self, mode):
         """rounding specification of the ICP sums: 0 / "product" (default), 1 / "gram" or 2 / "reference" (the reference's own f32 trees and host loop; include/cofusion_hip.h: cf_set_icp_arith)"""
         self._check(self.lib.cf_set_icp_arith(self.h, {"product": 0, "gram": 1, "reference": 2}.get(mode, mode)))
@@ -377,7 +410,14 @@ class Odometry:
         self.ctx._check(self.ctx.lib.cf_odom_bench_icp(self.h, level, iters, C.byref(us)))
         return us.value
 
+    def buffer_address(self, which, level):
+        """device address of an internal buffer (cf_odom_buffer); which == 0 has the side effect described in the header"""
+        ptr = C.c_void_p()
+        self.ctx._check(self.ctx.lib.cf_odom_buffer(self.h, which, level, C.byref(ptr), None))
+        return ptr.value
+
     def buffer(self, which, level):
+        """host copy of an internal buffer (cf_odom_buffer: 0..12 as the oracle numbers them, 13 cand, 14 zrange, 15 occ, 16 aabb)"""
         ptr = C.c_void_p(); nbytes = C.c_uint64()
         self.ctx._check(self.ctx.lib.cf_odom_buffer(self.h, which, level, C.byref(ptr), C.byref(nbytes)))
         host = np.empty(nbytes.value, np.uint8)
@@ -387,5 +427,13 @@ class Odometry:
             return host.view(np.float32).reshape(h, w, 3)
         if which == 12:
             return host.view(DATATERM).reshape(h * w)
+        if which == 13:
+            return host.reshape(h, w)
+        if which == 14:
+            return host.view(np.float32).reshape((h * w + 63) // 64, 2)
+        if which == 15:
+            return host.reshape(self.ctx.height // 4, self.ctx.width // 4)
+        if which == 16:
+            return host.view(np.uint32)
         dt, planes = self._BUF[which]
         return host.view(dt).reshape(planes * h, w)

@@ -1348,6 +1348,11 @@ int cf_odom_buffer(cf_odom* od, int which, int level, void** dptr, uint64_t* byt
         case 10: p = od->dIdy[level]; b = n * 2; break;
         case 11: p = od->cloud[level]; b = n * 12; break;
         case 12: p = od->corres[level]; b = n * 16; break;
+        // what the culling decides with (read only: no tracker state changes)
+        case 13: p = od->cand[level]; b = n; break;
+        case 14: p = od->zrange[level]; b = (n + 63) / 64 * sizeof(float2); break;
+        case 15: if (level != 0) return CF_EINVAL; p = od->occ; b = (size_t)(od->ctx->cfg.width >> 2) * (od->ctx->cfg.height >> 2); break;
+        case 16: if (level != 0) return CF_EINVAL; p = od->aabb; b = 6 * sizeof(unsigned); break;
         default: return CF_EINVAL;
     }
     *dptr = p; if (bytes) *bytes = b;

@@ -95,4 +95,8 @@ def load() -> C.CDLL:
         _lib = C.CDLL(LIB_PATH)
         _lib.cf_last_error.restype = C.c_char_p
         _lib.cf_get_stream.restype = C.c_void_p
+        pp = C.POINTER(C.c_void_p)
+        _lib.cf_odom_init_models_batch_select.restype = C.c_int
+        _lib.cf_odom_init_models_batch_select.argtypes = [C.c_void_p, pp, C.c_int, pp, pp, pp, pp, pp, pp, pp, C.c_float,
+                                                          C.POINTER(C.POINTER(C.c_float)), pp]
     return _lib

@@ -268,7 +268,6 @@ int cf_odom_level0_visited(cf_odom *od, uint64_t *icp_pixels, uint64_t *residual
  * previous call, a count as large as the level, or no RGB term).  It is the figure of the level's LAST launch -- at level 0 the
  * error-surface iteration, whose residual pass is sized like every other's.  Any of the three pointers may be NULL. */
 int cf_odom_last_launch_shape(cf_odom *od, int icp_blocks[3], int residual_blocks[3], int *icp_blocks_err);
-/* test access to internal device pyramids (same `which` numbering as the oracle's orc_odom_buffer) */
 /* share the frame-wide current vertex/normal pyramids between models (all models track the same frame,
  * cudafuncs.cu:119); pass NULL arrays to return to the odom-private maps written by cf_odom_init_icp */
 /* Skip the model-map gathers of pixels that project into empty 4x4 blocks of the prediction (an occupancy bitmap written by
@@ -306,6 +305,16 @@ int cf_odom_bind_frame_maps(cf_odom *od, const float *const vmaps[CF_NUM_PYRS], 
 /* ... or, when another tracker of the same context computed them with cf_odom_init_icp: share that tracker's current-frame pyramids
  * (and the per-run depth intervals the culled reduction uses) */
 int cf_odom_share_frame_maps(cf_odom *od, cf_odom *owner);
+/* test access to internal device pyramids: which 0..12 use the numbering of the oracle's orc_odom_buffer (0/1 current vertex / normal
+ * maps, 2/3 model maps, 4/5 last / next depth, 6/7/8 last / next / lastNext intensity, 9/10 dIdx / dIdy, 11 cloud, 12 DataTerm records),
+ * n = (width >> level) * (height >> level).  Reading which == 0 of a tracker's own maps hands out a writable pointer and therefore
+ * drops the per-run depth intervals beside them (the next tracking call does not depth-cull).  What the culling decides with, read
+ * only -- no tracker state changes:
+ *   13  cand[level]    u8, n bytes: the candidate mask of the RGB residual pass (written by the first launch of a tracking call)
+ *   14  zrange[level]  float2 (min, max), (n + 63) / 64 entries: depth interval of every 64-pixel run (cf_odom_init_icp)
+ *   15  occ            u8, (width / 4) * (height / 4) entries, level must be 0: occupancy of the 4x4 blocks of the prediction
+ *   16  aabb           six u32 order-preserving keys, level must be 0: bounding frustum of the prediction (x0, y0, z0 complemented,
+ *                      x1, y1, z1; all zero = empty or culling off); latched and zeroed by the next tracking call */
 int cf_odom_buffer(cf_odom *od, int which, int level, void **dptr, uint64_t *bytes);
 /* Model::generateCUDATextures depth half (Model.cpp:341-343): l1/l2 device outputs */
 int cf_depth_pyramid(cf_ctx *ctx, const float *depth_filtered, int cols, int rows, float *l1, float *l2);
