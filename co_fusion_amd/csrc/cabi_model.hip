@@ -662,6 +662,8 @@ int cf_model_upload_map(cf_model* m, const float* host_surfels, uint32_t count)
 
 // which: 0 index(u32) 1 vertConf 2 colorTime 3 normRad (f32x4) | 4 splat image (rgba8) 5 splat vertexConf 6 splat normalRad
 // (f32x4) 7 splat time (u16) | 8 fill vertex 9 fill normal (f32x4) 10 fill image (rgba8) | 11 surfels (f32x12, count entries)
+// test access, read only: 12 the new unstable surfels the last fuse appended (f32x12, as many as it counted) 13 the packed texel records of
+// the clean stage (f32x8 per texel; written by cf_models_frame_passes only)
 int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
 {
     if (!m || !dptr) return CF_EINVAL;
@@ -680,6 +682,14 @@ int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
         case 9: p = m->fill_normal; b = N * 16; break;
         case 10: p = m->fill_image; b = N * 4; break;
         case 11: { uint32_t c = 0; if (int r = exact_count(m, &c)) return r; p = m->buf[m->target]; b = (size_t)c * 48; break; }
+        case 12: {
+            unsigned nf = 0;
+            HIPCHK(m->ctx, hipMemcpyAsync(&nf, m->d_nfresh, sizeof(unsigned), hipMemcpyDeviceToHost, m->ctx->cur()));
+            HIPCHK(m->ctx, hipStreamSynchronize(m->ctx->cur()));
+            if (nf > N / 4 + 64) { m->ctx->set_error("cf_model_buffer: the new-surfel count exceeds its buffer"); return CF_ESTATE; }
+            p = m->fresh; b = (size_t)nf * 48; break;
+        }
+        case 13: p = m->clean_rec; b = N * 32; break;
         default: return CF_EINVAL;
     }
     *dptr = p; if (bytes) *bytes = b;

@@ -99,4 +99,8 @@ def load() -> C.CDLL:
         _lib.cf_odom_init_models_batch_select.restype = C.c_int
         _lib.cf_odom_init_models_batch_select.argtypes = [C.c_void_p, pp, C.c_int, pp, pp, pp, pp, pp, pp, pp, C.c_float,
                                                           C.POINTER(C.POINTER(C.c_float)), pp]
+        _lib.cf_models_frame_passes.restype = C.c_int
+        _lib.cf_models_frame_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]
+        _lib.cf_models_preindex.restype = C.c_int
+        _lib.cf_models_preindex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
     return _lib

@@ -12,6 +12,50 @@ from .api import Context, Odometry, _f, _p
 SURFEL = 12
 TIME_DELTA = 2 ** 31 // 2 - 1  # openLoop: INT_MAX / 2 (GUI/MainController.cpp:328)
 
+class ModelPass(C.Structure):
+    """cf_model_pass (include/cofusion_hip.h)"""
+    _fields_ = [("model", C.c_void_p), ("pose", C.POINTER(C.c_float)), ("rgba", C.c_void_p), ("mask", C.c_void_p), ("depth_raw", C.c_void_p),
+                ("depth_filtered", C.c_void_p), ("do_fuse", C.c_int), ("time", C.c_int), ("fuse_max_depth", C.c_float), ("weighting", C.c_float),
+                ("mask_id", C.c_int), ("conf_threshold", C.c_float)]
+
+
+class ModelPreindex(C.Structure):
+    """cf_model_preindex (include/cofusion_hip.h)"""
+    _fields_ = [("model", C.c_void_p), ("odom", C.c_void_p), ("time", C.c_int)]
+
+
+def frame_passes(ctx: Context, items, depth_cutoff, outlier_coeff, time_delta=None):
+    """cf_models_frame_passes.  items: dicts with model (a Model), pose, rgba, depth_filt, time, conf_threshold and, for do_fuse (default 1),
+    mask, depth_raw, fuse_max_depth, weighting, mask_id; the images are device tensors"""
+    n = len(items)
+    arr = (ModelPass * n)()
+    keep = []
+    for a, it in zip(arr, items):
+        pose = _f(np.asarray(it["pose"], np.float32).reshape(16))
+        keep.append(pose)
+        a.model = it["model"].h
+        a.pose = C.cast(pose, C.POINTER(C.c_float))
+        a.rgba, a.mask = _p(it["rgba"]), _p(it.get("mask"))
+        a.depth_raw, a.depth_filtered = _p(it.get("depth_raw")), _p(it["depth_filt"])
+        a.do_fuse = int(it.get("do_fuse", 1))
+        a.time = int(it["time"])
+        a.fuse_max_depth = float(it.get("fuse_max_depth", depth_cutoff))
+        a.weighting = float(it.get("weighting", 1.0))
+        a.mask_id = int(it.get("mask_id", 0))
+        a.conf_threshold = float(it["conf_threshold"])
+    ctx._check(ctx.lib.cf_models_frame_passes(ctx.h, arr, n, C.c_float(depth_cutoff), C.c_float(outlier_coeff),
+                                              int(TIME_DELTA if time_delta is None else time_delta)))
+
+
+def preindex(ctx: Context, items, depth_cutoff, time_delta=None):
+    """cf_models_preindex.  items: (Model, Odometry, time) triples"""
+    n = len(items)
+    arr = (ModelPreindex * n)()
+    for a, (m, od, time) in zip(arr, items):
+        a.model, a.odom, a.time = m.h, od.h, int(time)
+    ctx._check(ctx.lib.cf_models_preindex(ctx.h, arr, n, C.c_float(depth_cutoff), int(TIME_DELTA if time_delta is None else time_delta)))
+
+
 _BUF = {0: (np.uint32, 1), 1: (np.float32, 4), 2: (np.float32, 4), 3: (np.float32, 4), 4: (np.uint8, 4), 5: (np.float32, 4),
         6: (np.float32, 4), 7: (np.uint16, 1), 8: (np.float32, 4), 9: (np.float32, 4), 10: (np.uint8, 4)}
 
@@ -113,10 +157,13 @@ class Model:
     def buffer(self, which):
         ptr, nbytes = self.tensor(which)
         host = np.empty(nbytes, np.uint8)
-        self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, host.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_uint64(nbytes)))
+        if nbytes:
+            self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, host.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_uint64(nbytes)))
         h, w = self.ctx.height, self.ctx.width
-        if which == 11:
+        if which in (11, 12):   # the surfels; the new unstable surfels of the last fuse
             return host.view(np.float32).reshape(-1, SURFEL)
+        if which == 13:         # the clean stage's packed texel records
+            return host.view(np.float32).reshape(h, w, 8)
         dt, ch = _BUF[which]
         a = host.view(dt)
         return a.reshape(h, w, ch) if ch > 1 else a.reshape(h, w)

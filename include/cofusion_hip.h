@@ -399,7 +399,12 @@ int cf_model_download_map(cf_model *m, float *host_surfels, uint32_t capacity, u
 int cf_model_upload_map(cf_model *m, const float *host_surfels, uint32_t count);
 /* device views of the projection outputs.  which: 0 index(u32) 1 vertConf 2 colorTime 3 normRad (f32x4) | 4 splat image
  * (rgba8) 5 splat vertexConf 6 splat normalRad (f32x4) 7 splat time (u16) | 8 fill vertex 9 fill normal (f32x4)
- * 10 fill image (rgba8) | 11 surfels */
+ * 10 fill image (rgba8) | 11 surfels
+ * Test access, read only -- no model state changes:
+ *   12  the new unstable surfels the last cf_model_fuse / cf_models_frame_passes appended behind the map before its clean stage
+ *       (f32x12 in column-major pixel order; bytes = 48 x their count; waits for the stream)
+ *   13  the packed per-texel records cf_models_frame_passes leaves for its clean stage: vertConf | colorTime.z, colorTime.w, index (u32
+ *       bits), filtered depth -- 32 bytes per texel (never written by the per-model calls) */
 int cf_model_buffer(cf_model *m, int which, void **dptr, uint64_t *bytes);
 /* Model::computeFusionWeight (Model.cpp:391-406); pure host math */
 float cf_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier);

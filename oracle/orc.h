@@ -166,6 +166,15 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
 int orc_clean(const float *surfels_in, int count, const float *new_unstable, int n_new, const uint32_t *index, const float *vertConf4,
               const float *colorTime4, const float *depth_filt, const uint8_t *mask, const float pose[16], orc_cam cam, int cols,
               int rows, int time, float confThreshold, float outlierCoeff, int timeDelta, int maskID, float *surfels_out);
+/* the same two with what each pixel / surfel went through written out (tests/surfel_cases.py asserts the branches of its crafted cases
+ * with them): see orc_surfel.c for the layouts */
+void orc_fuse_trace(const float *surfels_in, int count, const uint32_t *index, const float *vertConf4, const float *normRad4,
+                    const uint8_t *rgba, const float *depth_raw, const float *depth_filt, const uint8_t *mask, const float pose[16],
+                    orc_cam cam, int cols, int rows, int time, float weighting, int maskID, float maxDepth, float *surfels_out,
+                    float *new_unstable, int *n_new, int32_t *pix_trace, int32_t *upd_trace);
+int orc_clean_trace(const float *surfels_in, int count, const float *new_unstable, int n_new, const uint32_t *index, const float *vertConf4,
+                    const float *colorTime4, const float *depth_filt, const uint8_t *mask, const float pose[16], orc_cam cam, int cols,
+                    int rows, int time, float confThreshold, float outlierCoeff, int timeDelta, int maskID, float *surfels_out, int32_t *trace);
 float orc_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier);
 
 /* ------------------------------ segmentation (orc_segment.c) -------------------------------- */

@@ -366,16 +366,23 @@ static float angle_between(orc_f3 a, orc_f3 b)
     return orc_acosf(orc_f3_dot(a, b) / (orc_f3_norm(a) * orc_f3_norm(b)));
 }
 
-void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const float *vertConf4, const float *normRad4,
+/* pix_trace (nullable), per pixel row-major [4]: why the pixel left the association (0 parity, 1 mask, 2 a zero depth neighbour, 3 depth
+ * out of range, 4 new vertex, 5 merge), the surfel it merges into, how many LATER window samples passed every gate with a distance EQUAL
+ * to the best so far (the sequential loop keeps the earlier one), and how many of those came from another outer iteration.
+ * upd_trace (nullable), per surfel [2]: the branch of update.vert (0 untouched, 1 averaged, 2 radius rejected), the pixels that claimed it. */
+static void fuse_impl(const float *surfels_in, int count, const uint32_t *index, const float *vertConf4, const float *normRad4,
               const uint8_t *rgba, const float *depth_raw, const float *depth_filt, const uint8_t *mask, const float pose[16],
               orc_cam cam, int cols, int rows, int time, float weighting, int maskID, float maxDepth, float *surfels_out,
-              float *new_unstable, int *n_new)
+              float *new_unstable, int *n_new, int32_t *pix_trace, int32_t *upd_trace)
 {
     const float inv_fx = (float)(1.0 / (double)cam.fx), inv_fy = (float)(1.0 / (double)cam.fy);
     const float scale = 1.0f; /* ModelProjection::FACTOR */
     int *owner = malloc(sizeof(int) * (size_t)imax(count, 1));
     float *records = malloc(sizeof(float) * 12 * (size_t)cols * rows);
     for (int i = 0; i < count; i++) owner[i] = -1;
+    if (pix_trace) memset(pix_trace, 0, sizeof(int32_t) * 4 * (size_t)cols * rows);
+    if (upd_trace) memset(upd_trace, 0, sizeof(int32_t) * 2 * (size_t)count);
+#define PIX_TRACE(code) do { if (pix_trace) pix_trace[((size_t)j * cols + i) * 4] = (code); } while (0)
     int nn = 0;
     for (int i = 0; i < cols; i++)
         for (int j = 0; j < rows; j++) { /* column-major draw order, Model.cpp:166-170 */
@@ -383,12 +390,14 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
             const float x = tcx * (float)cols, y = tcy * (float)rows;
             const orc_f3 vPosLocal = get_vertex(depth_raw, cols, rows, i, j, x, y, cam, inv_fx, inv_fy);
             if (!(((int)x % 2 == time % 2) && ((int)y % 2 == time % 2))) continue;
-            if ((int)mask[j * cols + i] != maskID) continue;
+            if ((int)mask[j * cols + i] != maskID) { PIX_TRACE(1); continue; }
             /* checkNeighbours on the RAW depth (data.vert:56-74) */
             if (depth_raw[j * cols + iclamp(i - 1, 0, cols - 1)] == 0 || depth_raw[iclamp(j - 1, 0, rows - 1) * cols + i] == 0 ||
-                depth_raw[j * cols + iclamp(i + 1, 0, cols - 1)] == 0 || depth_raw[iclamp(j + 1, 0, rows - 1) * cols + i] == 0)
+                depth_raw[j * cols + iclamp(i + 1, 0, cols - 1)] == 0 || depth_raw[iclamp(j + 1, 0, rows - 1) * cols + i] == 0) {
+                PIX_TRACE(2);
                 continue;
-            if (!(vPosLocal.z > 0 && vPosLocal.z <= maxDepth)) continue;
+            }
+            if (!(vPosLocal.z > 0 && vPosLocal.z <= maxDepth)) { PIX_TRACE(3); continue; }
 
             const orc_f3 vPos = xform_point(pose, vPosLocal);
             const orc_f3 vPos_f = get_vertex(depth_filt, cols, rows, i, j, x, y, cam, inv_fx, inv_fy);
@@ -405,7 +414,9 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
             const float lambda = sqrtf(xl * xl + yl * yl + 1);
             const orc_f3 ray = orc_f3_make(xl, yl, 1);
             uint32_t best = 0; int operation = 0;
-            for (float ii = tcx - (scale * indexXStep * windowMultiplier); ii < tcx + (scale * indexXStep * windowMultiplier); ii += indexXStep)
+            int outer = -1, bestOuter = -1, ties = 0, tiesOuter = 0;
+            for (float ii = tcx - (scale * indexXStep * windowMultiplier); ii < tcx + (scale * indexXStep * windowMultiplier); ii += indexXStep) {
+                outer++;
                 for (float jj = tcy - (scale * indexYStep * windowMultiplier); jj < tcy + (scale * indexYStep * windowMultiplier); jj += indexYStep) {
                     const uint32_t current = index[(size_t)nearest_texel(jj, rows) * cols + nearest_texel(ii, cols)];
                     if (current > 0U) {
@@ -414,13 +425,22 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
                         if (fabsf(zdiff * lambda) < 0.05f) {
                             const float dist = orc_f3_norm(orc_f3_cross(ray, orc_f3_make(vertConf.v[0], vertConf.v[1], vertConf.v[2])));
                             const f4 normRad = tex4_linear(normRad4, cols, rows, ii, jj);
-                            if (dist < bestDist && (fabsf(normRad.v[2]) < 0.75f ||
-                                                    fabsf(angle_between(orc_f3_make(normRad.v[0], normRad.v[1], normRad.v[2]), vNormLocal)) < 0.5f)) {
+                            const int gate = (fabsf(normRad.v[2]) < 0.75f ||
+                                              fabsf(angle_between(orc_f3_make(normRad.v[0], normRad.v[1], normRad.v[2]), vNormLocal)) < 0.5f);
+                            if (dist < bestDist && gate) {
                                 operation = 1; bestDist = dist; best = current;
+                                bestOuter = outer; ties = 0; tiesOuter = 0;
+                            } else if (operation == 1 && dist == bestDist && gate && current != best) {
+                                ties++; tiesOuter += (outer != bestOuter);
                             }
                         }
                     }
                 }
+            }
+            if (pix_trace) {
+                int32_t *t = pix_trace + ((size_t)j * cols + i) * 4;
+                t[0] = operation == 1 ? 5 : 4; t[1] = (int32_t)best; t[2] = ties; t[3] = tiesOuter;
+            }
             float rec[12] = {vPos.x, vPos.y, vPos.z, conf,
                              (float)(((int)c[0] << 16) + ((int)c[1] << 8) + (int)c[2]), 0, (float)time, 0,
                              nG.x, nG.y, nG.z, radius};
@@ -428,6 +448,7 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
                 rec[7] = -1;
                 const int rank = i * rows + j;
                 if (owner[best] < 0) { owner[best] = rank; memcpy(records + (size_t)rank * 12, rec, sizeof(rec)); } /* first wins */
+                if (upd_trace) upd_trace[(size_t)best * 2 + 1]++;
             } else {
                 rec[7] = -2;
                 memcpy(new_unstable + (size_t)nn * 12, rec, sizeof(rec));
@@ -442,6 +463,7 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
         if (owner[id] < 0) { memcpy(o, s, 48); continue; }
         const float *r = records + (size_t)owner[id] * 12;
         const float c_k = s[3], a = r[3];
+        if (upd_trace) upd_trace[(size_t)id * 2] = (r[11] < (1.0f + 0.5f) * s[11]) ? 1 : 2;
         if (r[11] < (1.0f + 0.5f) * s[11]) {
             for (int k = 0; k < 3; k++) o[k] = ((c_k * s[k]) + (a * r[k])) / (c_k + a);
             o[3] = c_k + a;
@@ -461,6 +483,23 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
         }
     }
     free(records); free(owner);
+#undef PIX_TRACE
+}
+void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const float *vertConf4, const float *normRad4,
+              const uint8_t *rgba, const float *depth_raw, const float *depth_filt, const uint8_t *mask, const float pose[16],
+              orc_cam cam, int cols, int rows, int time, float weighting, int maskID, float maxDepth, float *surfels_out,
+              float *new_unstable, int *n_new)
+{
+    fuse_impl(surfels_in, count, index, vertConf4, normRad4, rgba, depth_raw, depth_filt, mask, pose, cam, cols, rows, time, weighting, maskID,
+              maxDepth, surfels_out, new_unstable, n_new, NULL, NULL);
+}
+void orc_fuse_trace(const float *surfels_in, int count, const uint32_t *index, const float *vertConf4, const float *normRad4,
+                    const uint8_t *rgba, const float *depth_raw, const float *depth_filt, const uint8_t *mask, const float pose[16],
+                    orc_cam cam, int cols, int rows, int time, float weighting, int maskID, float maxDepth, float *surfels_out,
+                    float *new_unstable, int *n_new, int32_t *pix_trace, int32_t *upd_trace)
+{
+    fuse_impl(surfels_in, count, index, vertConf4, normRad4, rgba, depth_raw, depth_filt, mask, pose, cam, cols, rows, time, weighting, maskID,
+              maxDepth, surfels_out, new_unstable, n_new, pix_trace, upd_trace);
 }
 
 /* ============================ clean ==============================================
@@ -468,10 +507,10 @@ void orc_fuse(const float *surfels_in, int count, const uint32_t *index, const f
  * nodes == 0) + copy_unstable.geom: ordered stream compaction of old surfels then appended ones. */
 static int clean_one(float *s /* in/out 12 */, const float t_inv[16], orc_cam cam, int cols, int rows, int time, float confThreshold,
                      float outlierCoeff, int timeDelta, int maskID, const uint32_t *index, const float *vertConf4,
-                     const float *colorTime4, const float *depth_filt, const uint8_t *mask)
+                     const float *colorTime4, const float *depth_filt, const uint8_t *mask, int32_t *trace /* nullable [8], see orc_clean_trace */)
 {
     const float scale = 1.0f;
-    int test = 1;
+    int test = 1, window = 0, foreign = 0;
     const orc_f3 localPos = xform_point(t_inv, orc_f3_make(s[0], s[1], s[2]));
     const float x = ((cam.fx * localPos.x) / localPos.z) + cam.cx, y = ((cam.fy * localPos.y) / localPos.z) + cam.cy;
     const orc_f3 localNorm = orc_f3_normalized(xform_dir(t_inv, orc_f3_make(s[8], s[9], s[10])));
@@ -482,6 +521,7 @@ static int clean_one(float *s /* in/out 12 */, const float t_inv[16], orc_cam ca
     int count = 0, zCount = 0, violationCount = 0;
     float avgViolation = 0;
     if ((float)time - s[7] < (float)timeDelta && localPos.z > 0 && x > 0 && y > 0 && x < (float)cols && y < (float)rows) {
+        window = 1;
         for (float i = x_n - (scale * indexXStep * windowMultiplier); i < x_n + (scale * indexXStep * windowMultiplier); i += indexXStep)
             for (float j = y_n - (scale * indexYStep * windowMultiplier); j < y_n + (scale * indexYStep * windowMultiplier); j += indexYStep) {
                 const uint32_t current = index[(size_t)nearest_texel(j, rows) * cols + nearest_texel(i, cols)];
@@ -505,8 +545,10 @@ static int clean_one(float *s /* in/out 12 */, const float t_inv[16], orc_cam ca
     }
     if (count > 8 || zCount > 4) test = 0;
     if (s[7] == -2) s[7] = (float)time;
-    if ((s[7] == -1 || (((float)time - s[7]) > 20 && s[3] < confThreshold))) test = 0;
-    if (s[7] > 0 && (float)time - s[7] > (float)timeDelta) test = 1;
+    const int old_unconfident = (((float)time - s[7]) > 20 && s[3] < confThreshold);
+    if ((s[7] == -1 || old_unconfident)) test = 0;
+    const int outdated = (s[7] > 0 && (float)time - s[7] > (float)timeDelta);
+    if (outdated) test = 1;
     if (violationCount > 0) {
         avgViolation /= (float)violationCount;
         s[3] *= 1.0f / (1 + outlierCoeff * avgViolation);
@@ -514,14 +556,23 @@ static int clean_one(float *s /* in/out 12 */, const float t_inv[16], orc_cam ca
         const int maskValue = mask[(size_t)my * cols + mx];
         const float wDepth = depth_filt[(size_t)my * cols + mx];
         if (maskValue != maskID && (wDepth > localPos.z - 0.05f && wDepth < localPos.z + 0.05f))
+        {
+            foreign = 1;
             s[3] *= (0.5f + 0.5f * (1 - outlierCoeff / 10.0f));
+        }
+    }
+    if (trace) {
+        trace[0] = window; trace[1] = count; trace[2] = zCount; trace[3] = violationCount; trace[4] = foreign; trace[5] = test;
+        trace[6] = old_unconfident; trace[7] = outdated;
     }
     return test;
 }
 
-int orc_clean(const float *surfels_in, int count, const float *new_unstable, int n_new, const uint32_t *index, const float *vertConf4,
-              const float *colorTime4, const float *depth_filt, const uint8_t *mask, const float pose[16], orc_cam cam, int cols,
-              int rows, int time, float confThreshold, float outlierCoeff, int timeDelta, int maskID, float *surfels_out)
+/* trace (nullable), per input surfel (the old ones, then the appended ones) [8]: window, count, zCount, violationCount, the foreign-mask factor
+ * applied, kept, old and unconfident, older than timeDelta */
+int orc_clean_trace(const float *surfels_in, int count, const float *new_unstable, int n_new, const uint32_t *index, const float *vertConf4,
+                    const float *colorTime4, const float *depth_filt, const uint8_t *mask, const float pose[16], orc_cam cam, int cols,
+                    int rows, int time, float confThreshold, float outlierCoeff, int timeDelta, int maskID, float *surfels_out, int32_t *trace)
 {
     float t_inv[16];
     inv44f(pose, t_inv);
@@ -533,13 +584,20 @@ int orc_clean(const float *surfels_in, int count, const float *new_unstable, int
             float s[12];
             memcpy(s, src + (size_t)k * 12, 48);
             if (clean_one(s, t_inv, cam, cols, rows, time, confThreshold, outlierCoeff, timeDelta, maskID, index, vertConf4, colorTime4,
-                          depth_filt, mask)) {
+                          depth_filt, mask, trace ? trace + ((size_t)(pass ? count : 0) + k) * 8 : NULL)) {
                 memcpy(surfels_out + (size_t)n * 12, s, 48);
                 n++;
             }
         }
     }
     return n;
+}
+int orc_clean(const float *surfels_in, int count, const float *new_unstable, int n_new, const uint32_t *index, const float *vertConf4,
+              const float *colorTime4, const float *depth_filt, const uint8_t *mask, const float pose[16], orc_cam cam, int cols,
+              int rows, int time, float confThreshold, float outlierCoeff, int timeDelta, int maskID, float *surfels_out)
+{
+    return orc_clean_trace(surfels_in, count, new_unstable, n_new, index, vertConf4, colorTime4, depth_filt, mask, pose, cam, cols, rows, time,
+                           confThreshold, outlierCoeff, timeDelta, maskID, surfels_out, NULL);
 }
 
 /* ============================ fusion weight ======================================

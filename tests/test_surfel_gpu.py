@@ -1,7 +1,6 @@
-"""GPU parity of the surfel half of the hot path (bilateral, bootstrap, index map, splat prediction,
-fill-in, fuse, clean) and of the whole `-static` frame loop: HIP through the C-ABI vs the CPU oracle.
-
-Everything is compared bit-for-bit: surfel buffers, counts, index maps, prediction images, poses."""
+"""GPU parity of two single surfel passes, HIP through the C-ABI vs the CPU oracle, bit for bit: the bilateral depth filter
+(bilateral_kernel) and the bootstrap + one index map of a rendered frame at 320x240.  The frame chain (fuse, clean, the compactions,
+splat prediction) is tested in tests/test_surfel_chain_gpu.py; `_same` is shared with it."""
 import warnings
 
 import numpy as np
@@ -49,9 +48,9 @@ def test_bilateral_exact(ctx):
     d[100, 100] = 7.0       # beyond the cutoff
     out = M.bilateral(ctx, ctx.to_device(d), 5.0).cpu().numpy()
     _same(out, op.bilateral(d, 5.0), "bilateral")
-    # the two-pixels-per-lane kernel (even widths) against the one-pixel kernel's cases: holes and non-finite values at the image
-    # borders (a tap outside the image must add exact zeros, a non-finite tap inside must poison its neighbours exactly as the
-    # shader arithmetic does), a window wider than the image, an odd width (one-pixel kernel)
+    # bilateral_kernel is one pixel per lane with the 13x13 window unrolled and taps outside the image skipped: holes and non-finite
+    # values at the image borders (a skipped tap adds nothing, a non-finite tap inside must poison its neighbours exactly as the
+    # shader arithmetic does), a window wider than the image, odd and even widths
     e = d.copy()
     e[0, 5] = np.inf; e[H - 1, W - 3] = np.nan; e[50, 0] = np.inf; e[60, W - 1] = np.nan; e[:, 0:2] = 0.0; e[120:130, W - 7:] = 0.0
     _same(M.bilateral(ctx, ctx.to_device(e), 5.0).cpu().numpy(), op.bilateral(e, 5.0), "bilateral, borders and non-finite values")
