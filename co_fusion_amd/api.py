@@ -437,3 +437,82 @@ class Odometry:
             return host.view(np.uint32)
         dt, planes = self._BUF[which]
         return host.view(dt).reshape(planes * h, w)
+
+
+class FrameDecoder:
+    """cf_frame_decoder (csrc/frame_decode.hip): finishes the frames of a .klg log on the device.  A slot's pinned staging is filled
+    through the numpy views of `slot(s)`, `submit` copies and launches on the decoder's own stream, `acquire` returns the output
+    frame as torch tensors VIEWING the decoder's buffers (depth f32 [H, W], rgba u8 [H, W, 4]), valid until the slot's next submit."""
+
+    def __init__(self, ctx: Context, max_w, max_h, slots=4):
+        from . import klg as _klg
+        self._klg = _klg
+        self.ctx, self.lib = ctx, ctx.lib
+        self.max_w, self.max_h, self.slots = int(max_w), int(max_h), int(slots)
+        self.lib.cf_frame_decoder_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        self.lib.cf_frame_decoder_destroy.argtypes = [C.c_void_p]
+        self.lib.cf_frame_decoder_destroy.restype = None
+        self.lib.cf_frame_decoder_slot.argtypes = [C.c_void_p, C.c_int, C.POINTER(_klg.FrameSlot)]
+        self.lib.cf_frame_decoder_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(_klg.FrameDesc)]
+        self.lib.cf_frame_decoder_acquire.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        self.lib.cf_frame_decoder_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        self.h = C.c_void_p()
+        ctx._check(self.lib.cf_frame_decoder_create(ctx.h, self.max_w, self.max_h, self.slots, C.byref(self.h)))
+        self._size = {}
+
+    def slot(self, s):
+        """numpy views of slot s's pinned staging: dict(header=JpegHeader (in place), coef int16 [blocks, 64], depth u16 [max_h*max_w],
+        rgb u8 [max_h*max_w*3])"""
+        m = self._klg.FrameSlot()
+        self.ctx._check(self.lib.cf_frame_decoder_slot(self.h, int(s), C.byref(m)))
+        n = self.max_w * self.max_h
+        return dict(header=m.header.contents, coef=np.ctypeslib.as_array(m.coef, shape=(int(m.coef_blocks), 64)),
+                    depth=np.ctypeslib.as_array(m.depth, shape=(n,)), rgb=np.ctypeslib.as_array(m.rgb, shape=(n * 3,)))
+
+    def fill(self, s, width, height, depth_mm, kind, colour=None):
+        """stage a frame in slot s: depth_mm u16 [H, W]; colour = (JpegHeader, coef) for COLOR_JPEG, u8 [H, W, 3] for COLOR_RAW /
+        COLOR_DECODED"""
+        m = self.slot(s)
+        n = width * height
+        m["depth"][:n] = np.ascontiguousarray(depth_mm, np.uint16).reshape(n)
+        if kind == self._klg.COLOR_JPEG:
+            hd, coef = colour
+            C.memmove(C.byref(m["header"]), C.byref(hd), C.sizeof(hd))
+            m["coef"][:hd.total_blocks] = np.ascontiguousarray(coef, np.int16).reshape(hd.total_blocks, 64)
+        elif kind != self._klg.COLOR_NONE:
+            m["rgb"][:n * 3] = np.ascontiguousarray(colour, np.uint8).reshape(n * 3)
+
+    def submit(self, s, width, height, kind, flip_colors=False):
+        d = self._klg.FrameDesc(int(width), int(height), int(kind), int(bool(flip_colors)))
+        self.ctx._check(self.lib.cf_frame_decoder_submit(self.h, int(s), C.byref(d)))
+        self._size[int(s)] = (int(height), int(width))
+
+    def acquire(self, s, complete=True):
+        dp, cp = C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.lib.cf_frame_decoder_acquire(self.h, int(s), int(bool(complete)), C.byref(dp), C.byref(cp)))
+        H, W = self._size[int(s)]
+        dev = self.ctx.device
+
+        def view(ptr, shape, typestr):
+            holder = type("_DevView", (), {})()
+            holder.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(ptr), False), version=2)
+            return torch.as_tensor(holder, device=dev)
+
+        return view(dp.value, (H, W), "<f4"), view(cp.value, (H, W, 4), "|u1")
+
+    def timing(self, on=True):
+        """kernel durations from device events accumulated while timing was on: (idct ms, finish ms, frames); resets the sums"""
+        a, b, n = C.c_double(), C.c_double(), C.c_uint64()
+        self.ctx._check(self.lib.cf_frame_decoder_timing(self.h, int(bool(on)), C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cf_frame_decoder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -4,11 +4,19 @@
 // progressive / arithmetic / 12-bit streams are rejected.
 // IDCT (jidctint "islow"), chroma upsampling ("fancy" h2v1 / h2v2) and colour conversion follow libjpeg's defaults, so
 // the pixels match what the reference's JPEGLoader produces (tests compare against Pillow's libjpeg).
+//
+// The decoder is split at the coefficient boundary.  The FRONT END (markers, tables, scan, Huffman) leaves a
+// cf_jpeg_header and the QUANTISED coefficients, 64 per block in natural order, blocks in raster order per component, components planar.
+// The BACK END (dequantisation, IDCT, upsampling, colour conversion) starts from that representation: on the host here
+// (jpegFinishHost), on the device in csrc/frame_decode.hip.  decodeJpegRGB is the one followed by the other.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
+
+#include "../../include/cofusion_hip.h"
 
 namespace cofusion {
 
@@ -125,15 +133,22 @@ void idct8x8(const int* coef, uint8_t* out, int stride)
     }
 }
 
-struct Component { int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0, pred = 0, stride = 0, rows = 0; std::vector<uint8_t> plane; };
+struct Component { int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0, pred = 0, bw = 0, bh = 0; size_t first = 0; };
 
-}  // namespace
 
-// Decodes into rgb [height*width*3]; returns "" on success or an error text.  The image must have the expected size.
-std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int height, uint8_t* rgb)
+// ---- front end: stream -> header + quantised coefficients.  CoefT int16_t is the representation the device back end takes and is
+// STRICT: a stream it cannot hold exactly (a 16-bit quantisation table, a DC predictor outside int16 -- AC coefficients are at most
+// 15 bits and always fit) sets *refused and returns "".  CoefT int32_t with 16-bit tables holds everything the decoder accepts.
+// qt16[ci] is component ci's table in natural order; the header's 8-bit copy is filled when every entry fits.
+template <typename CoefT>
+std::string frontImpl(const uint8_t* data, size_t size, int width, int height, cf_jpeg_header* hdr, uint16_t qt16[3][64], CoefT* coef,
+                      size_t capBlocks, bool* refused)
 {
+    constexpr bool strict = sizeof(CoefT) == 2;
+    *refused = false;
     if (size < 4 || data[0] != 0xFF || data[1] != 0xD8) return "not a JPEG stream";
     uint16_t qt[4][64] = {{0}};
+    bool wide[4] = {false, false, false, false};
     Huff dc[4], ac[4];
     std::vector<Component> comps;
     int W = 0, H = 0, restart = 0, hmax = 1, vmax = 1;
@@ -157,6 +172,7 @@ std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int heigh
                 if (tq > 3) return "bad quantisation table id";
                 if (p + (pq ? 128 : 64) > segend) return "truncated quantisation table";
                 for (int i = 0; i < 64; i++) { qt[tq][kZigzag[i]] = pq ? (uint16_t)be16(p) : data[p]; p += pq ? 2 : 1; }
+                wide[tq] = pq != 0;
             }
         } else if (m == 0xC4) {  // DHT
             size_t p = seg;
@@ -206,10 +222,22 @@ std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int heigh
             }
             const int mcuw = 8 * hmax, mcuh = 8 * vmax;
             const int mx = (W + mcuw - 1) / mcuw, my = (H + mcuh - 1) / mcuh;
-            for (auto& c : comps) {
-                c.stride = mx * c.h * 8; c.rows = my * c.v * 8; c.pred = 0;
-                c.plane.assign((size_t)c.stride * c.rows, 0);
+            memset(hdr, 0, sizeof(*hdr));
+            hdr->width = W; hdr->height = H; hdr->ncomp = (int)comps.size(); hdr->hmax = hmax; hdr->vmax = vmax;
+            size_t total = 0;
+            for (size_t ci = 0; ci < comps.size(); ci++) {
+                Component& c = comps[ci];
+                c.bw = mx * c.h; c.bh = my * c.v; c.pred = 0; c.first = total;
+                total += (size_t)c.bw * c.bh;
                 if (!dc[c.td].present || !ac[c.ta].present) return "missing Huffman table";
+                hdr->comp[ci].h = c.h; hdr->comp[ci].v = c.v; hdr->comp[ci].bw = c.bw; hdr->comp[ci].bh = c.bh; hdr->comp[ci].first = (int32_t)c.first;
+                for (int i = 0; i < 64; i++) { qt16[ci][i] = qt[c.tq][i]; hdr->qt[ci][i] = (uint8_t)qt[c.tq][i]; }
+                if (strict && wide[c.tq]) { *refused = true; return ""; }
+            }
+            hdr->total_blocks = (int32_t)total;
+            if (total > capBlocks) {
+                if (strict) { *refused = true; return ""; }
+                return "coefficient buffer too small";
             }
             BitReader br{data + segend, data + size};
             int count = 0;
@@ -226,11 +254,13 @@ std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int heigh
                     for (auto& c : comps)
                         for (int by = 0; by < c.v; by++)
                             for (int bx = 0; bx < c.h; bx++) {
-                                int coef[64] = {0};
+                                CoefT* blk = coef + (c.first + (size_t)(yy * c.v + by) * c.bw + (xx * c.h + bx)) * 64;
+                                memset(blk, 0, 64 * sizeof(CoefT));
                                 const int t = decode_symbol(br, dc[c.td]);
                                 if (t < 0 || t > 11) return "corrupt DC coefficient";
                                 c.pred += extend(br.receive(t), t);
-                                coef[0] = c.pred * qt[c.tq][0];
+                                if (strict && (c.pred < -32768 || c.pred > 32767)) { *refused = true; return ""; }
+                                blk[0] = (CoefT)c.pred;
                                 for (int k = 1; k < 64;) {
                                     const int rs = decode_symbol(br, ac[c.ta]);
                                     if (rs < 0) return "corrupt AC coefficient";
@@ -238,67 +268,131 @@ std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int heigh
                                     if (s == 0) { if (r == 15) { k += 16; continue; } break; }
                                     k += r;
                                     if (k > 63) return "corrupt AC run";
-                                    coef[kZigzag[k]] = extend(br.receive(s), s) * qt[c.tq][kZigzag[k]];
+                                    blk[kZigzag[k]] = (CoefT)extend(br.receive(s), s);
                                     k++;
                                 }
                                 if (br.bad) return "truncated entropy data";
-                                idct8x8(coef, &c.plane[(size_t)((yy * c.v + by) * 8) * c.stride + (xx * c.h + bx) * 8], c.stride);
                             }
                 }
-            // chroma upsampling as libjpeg does by default ("fancy" triangle filter for 2x1 and 2x2, jdsample.c), replication
-            // for other factors; colour conversion with libjpeg's 16-bit fixed-point tables (jdcolor.c)
-            std::vector<std::vector<uint8_t>> full(comps.size());
-            for (size_t ci = 0; ci < comps.size(); ci++) {
-                const Component& c = comps[ci];
-                std::vector<uint8_t>& o = full[ci];
-                o.assign((size_t)W * H, 0);
-                const int cw = (W * c.h + hmax - 1) / hmax, ch = (H * c.v + vmax - 1) / vmax;  // downsampled size
-                auto at = [&](int x, int y) { return (int)c.plane[(size_t)(y < 0 ? 0 : (y >= ch ? ch - 1 : y)) * c.stride + (x < 0 ? 0 : (x >= cw ? cw - 1 : x))]; };
-                if (c.h == hmax && c.v == vmax) {
-                    for (int y = 0; y < H; y++) memcpy(&o[(size_t)y * W], &c.plane[(size_t)y * c.stride], (size_t)W);
-                } else if (c.h * 2 == hmax && c.v == vmax) {  // h2v1 fancy
-                    for (int y = 0; y < H; y++)
-                        for (int x = 0; x < W; x++) {
-                            const int i = x >> 1;
-                            int v;
-                            if (x & 1) v = (i == cw - 1) ? at(i, y) : (3 * at(i, y) + at(i + 1, y) + 2) >> 2;
-                            else v = (i == 0) ? at(0, y) : (3 * at(i, y) + at(i - 1, y) + 1) >> 2;
-                            o[(size_t)y * W + x] = (uint8_t)v;
-                        }
-                } else if (c.h * 2 == hmax && c.v * 2 == vmax) {  // h2v2 fancy
-                    for (int y = 0; y < H; y++) {
-                        const int r = y >> 1, rn = (y & 1) ? r + 1 : r - 1;
-                        for (int x = 0; x < W; x++) {
-                            const int i = x >> 1;
-                            const int cur = 3 * at(i, r) + at(i, rn);
-                            int v;
-                            if (x & 1) v = (i == cw - 1) ? (cur * 4 + 7) >> 4 : (cur * 3 + 3 * at(i + 1, r) + at(i + 1, rn) + 7) >> 4;
-                            else v = (i == 0) ? (cur * 4 + 8) >> 4 : (cur * 3 + 3 * at(i - 1, r) + at(i - 1, rn) + 8) >> 4;
-                            o[(size_t)y * W + x] = (uint8_t)v;
-                        }
-                    }
-                } else {
-                    for (int y = 0; y < H; y++)
-                        for (int x = 0; x < W; x++) o[(size_t)y * W + x] = (uint8_t)at(x * c.h / hmax, y * c.v / vmax);
-                }
-            }
-            auto fix = [](double v) { return (long)(v * 65536.0 + 0.5); };
-            const long crr = fix(1.40200), cbb = fix(1.77200), crg = -fix(0.71414), cbg = -fix(0.34414), half = 32768;
-            auto clamp = [](long r) { return (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r)); };
-            for (size_t q = 0; q < (size_t)W * H; q++) {
-                uint8_t* o = rgb + q * 3;
-                const long Y = full[0][q];
-                if (comps.size() == 1) { o[0] = o[1] = o[2] = (uint8_t)Y; continue; }
-                const long cb = (long)full[1][q] - 128, cr = (long)full[2][q] - 128;
-                o[0] = clamp(Y + ((crr * cr + half) >> 16));
-                o[1] = clamp(Y + ((cbg * cb + half + crg * cr) >> 16));
-                o[2] = clamp(Y + ((cbb * cb + half) >> 16));
-            }
             return "";
         }
         pos = segend;
     }
     return "no scan found";
+}
+
+// ---- host back end: dequantisation, IDCT into one padded plane per component, then chroma upsampling as libjpeg does by default
+// ("fancy" triangle filter for 2x1 and 2x2, jdsample.c; replication for other factors) and colour conversion with libjpeg's 16-bit
+// fixed-point tables (jdcolor.c).  csrc/frame_decode.hip states the same arithmetic for the device.
+template <typename CoefT>
+void finishImpl(const cf_jpeg_header* hdr, const uint16_t qt16[3][64], const CoefT* coef, uint8_t* rgb)
+{
+    const int W = hdr->width, H = hdr->height, nc = hdr->ncomp, hmax = hdr->hmax, vmax = hdr->vmax;
+    std::vector<std::vector<uint8_t>> planes((size_t)nc), full((size_t)nc);
+    for (int ci = 0; ci < nc; ci++) {
+        const auto& c = hdr->comp[ci];
+        const int stride = c.bw * 8;
+        planes[ci].assign((size_t)stride * c.bh * 8, 0);
+        for (int by = 0; by < c.bh; by++)
+            for (int bx = 0; bx < c.bw; bx++) {
+                const CoefT* blk = coef + ((size_t)c.first + (size_t)by * c.bw + bx) * 64;
+                int deq[64];
+                for (int i = 0; i < 64; i++) deq[i] = (int)blk[i] * qt16[ci][i];
+                idct8x8(deq, &planes[ci][(size_t)(by * 8) * stride + bx * 8], stride);
+            }
+    }
+    for (int ci = 0; ci < nc; ci++) {
+        const auto& c = hdr->comp[ci];
+        const std::vector<uint8_t>& plane = planes[ci];
+        const int stride = c.bw * 8;
+        std::vector<uint8_t>& o = full[ci];
+        o.assign((size_t)W * H, 0);
+        const int cw = (W * c.h + hmax - 1) / hmax, ch = (H * c.v + vmax - 1) / vmax;  // downsampled size
+        auto at = [&](int x, int y) { return (int)plane[(size_t)(y < 0 ? 0 : (y >= ch ? ch - 1 : y)) * stride + (x < 0 ? 0 : (x >= cw ? cw - 1 : x))]; };
+        if (c.h == hmax && c.v == vmax) {
+            for (int y = 0; y < H; y++) memcpy(&o[(size_t)y * W], &plane[(size_t)y * stride], (size_t)W);
+        } else if (c.h * 2 == hmax && c.v == vmax) {  // h2v1 fancy
+            for (int y = 0; y < H; y++)
+                for (int x = 0; x < W; x++) {
+                    const int i = x >> 1;
+                    int v;
+                    if (x & 1) v = (i == cw - 1) ? at(i, y) : (3 * at(i, y) + at(i + 1, y) + 2) >> 2;
+                    else v = (i == 0) ? at(0, y) : (3 * at(i, y) + at(i - 1, y) + 1) >> 2;
+                    o[(size_t)y * W + x] = (uint8_t)v;
+                }
+        } else if (c.h * 2 == hmax && c.v * 2 == vmax) {  // h2v2 fancy
+            for (int y = 0; y < H; y++) {
+                const int r = y >> 1, rn = (y & 1) ? r + 1 : r - 1;
+                for (int x = 0; x < W; x++) {
+                    const int i = x >> 1;
+                    const int cur = 3 * at(i, r) + at(i, rn);
+                    int v;
+                    if (x & 1) v = (i == cw - 1) ? (cur * 4 + 7) >> 4 : (cur * 3 + 3 * at(i + 1, r) + at(i + 1, rn) + 7) >> 4;
+                    else v = (i == 0) ? (cur * 4 + 8) >> 4 : (cur * 3 + 3 * at(i - 1, r) + at(i - 1, rn) + 8) >> 4;
+                    o[(size_t)y * W + x] = (uint8_t)v;
+                }
+            }
+        } else {
+            for (int y = 0; y < H; y++)
+                for (int x = 0; x < W; x++) o[(size_t)y * W + x] = (uint8_t)at(x * c.h / hmax, y * c.v / vmax);
+        }
+    }
+    auto fix = [](double v) { return (long)(v * 65536.0 + 0.5); };
+    const long crr = fix(1.40200), cbb = fix(1.77200), crg = -fix(0.71414), cbg = -fix(0.34414), half = 32768;
+    auto clamp = [](long r) { return (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r)); };
+    for (size_t q = 0; q < (size_t)W * H; q++) {
+        uint8_t* o = rgb + q * 3;
+        const long Y = full[0][q];
+        if (nc == 1) { o[0] = o[1] = o[2] = (uint8_t)Y; continue; }
+        const long cb = (long)full[1][q] - 128, cr = (long)full[2][q] - 128;
+        o[0] = clamp(Y + ((crr * cr + half) >> 16));
+        o[1] = clamp(Y + ((cbg * cb + half + crg * cr) >> 16));
+        o[2] = clamp(Y + ((cbb * cb + half) >> 16));
+    }
+}
+
+}  // namespace
+
+// Front end of the log player: the representation csrc/frame_decode.hip finishes on the device.  "" and *refused = false: header and
+// coef (capBlocks * 64 entries provided by the caller, e.g. a pinned slot) are filled.  *refused = true: the stream is one the device
+// path does not promise to reproduce (see frontImpl) -- decode it with decodeJpegRGB instead.  Otherwise the decoder's error text.
+// The device arithmetic is stated for EVERY int16 coefficient with 8-bit tables: |dequantised| <= 32768 * 255 < 2^23, and both IDCT
+// passes are computed in 64 bits there as here (pass 1 stays below 2^42, pass 2 below 2^50), so nothing narrower is refused.
+std::string jpegFront(const uint8_t* data, size_t size, int width, int height, cf_jpeg_header* hdr, int16_t* coef, size_t capBlocks, bool* refused)
+{
+    uint16_t qt16[3][64];
+    return frontImpl<int16_t>(data, size, width, height, hdr, qt16, coef, capBlocks, refused);
+}
+
+// Host back end from the same representation: rgb [height*width*3] in libjpeg's channel order.
+void jpegFinishHost(const cf_jpeg_header* hdr, const int16_t* coef, uint8_t* rgb)
+{
+    uint16_t qt16[3][64];
+    for (int c = 0; c < 3; c++) for (int i = 0; i < 64; i++) qt16[c][i] = hdr->qt[c][i];
+    finishImpl<int16_t>(hdr, qt16, coef, rgb);
+}
+
+// Decodes into rgb [height*width*3]; returns "" on success or an error text.  The image must have the expected size.
+// Front end plus host back end; a stream the strict front end refuses goes through the wide representation (int32 coefficients,
+// 16-bit tables), which computes the same thing.
+std::string decodeJpegRGB(const uint8_t* data, size_t size, int width, int height, uint8_t* rgb)
+{
+    if (width <= 0 || height <= 0) return "JPEG size differs from the log's resolution";
+    const size_t cap = (size_t)CF_JPEG_MAX_BLOCKS(width, height);
+    cf_jpeg_header hdr;
+    uint16_t qt16[3][64];
+    bool refused = false;
+    {
+        std::unique_ptr<int16_t[]> coef(new int16_t[cap * 64]);
+        const std::string e = frontImpl<int16_t>(data, size, width, height, &hdr, qt16, coef.get(), cap, &refused);
+        if (!e.empty()) return e;
+        if (!refused) { finishImpl<int16_t>(&hdr, qt16, coef.get(), rgb); return ""; }
+    }
+    std::unique_ptr<int32_t[]> coef(new int32_t[cap * 64]);
+    const std::string e = frontImpl<int32_t>(data, size, width, height, &hdr, qt16, coef.get(), cap, &refused);
+    if (!e.empty()) return e;
+    finishImpl<int32_t>(&hdr, qt16, coef.get(), rgb);
+    return "";
 }
 
 }  // namespace cofusion

@@ -10,7 +10,12 @@
 
 #include "CoFusion.h"
 #include "KlgIO.h"
+#include "KlgPlayer.h"
 
+namespace cofusion {   // Jpeg.cpp: the decoder split at the coefficient boundary
+std::string jpegFront(const uint8_t* data, size_t size, int width, int height, cf_jpeg_header* hdr, int16_t* coef, size_t capBlocks, bool* refused);
+void jpegFinishHost(const cf_jpeg_header* hdr, const int16_t* coef, uint8_t* rgb);
+}
 using namespace cofusion;
 
 struct cofusion_handle { CoFusion* cf; bool borrowed = false; };  // borrowed: a sequence of a lock-step group (owned and stepped by the group)
@@ -353,5 +358,99 @@ int cofusion_klg_write(cofusion_klg_writer* w, int64_t ts, const float* depth_m,
     return 0;
 }
 int cofusion_klg_finish(cofusion_klg_writer* w) { if (!w) return -1; w->w.close(); delete w; return 0; }
+
+// ---- .klg log player (KlgPlayer.h) ----
+struct cofusion_klg_player { KlgPlayer p; cofusion_klg_player(CoFusion& cf, const char* f, bool fl, int w) : p(cf, f, fl, w) {} };
+int cofusion_klg_player_open(cofusion_handle* h, const char* file, int flip, int workers, cofusion_klg_player** out, int* num_frames)
+{
+    if (!h || !file || !out) { g_err = "cofusion_klg_player_open: bad arguments"; return -1; }
+    if (h->borrowed) { g_err = "the log player is not available for a sequence of a lock-step group"; return -1; }
+    GUARD(*out = new cofusion_klg_player(*h->cf, file, flip != 0, workers > 0 ? workers : 4));
+    if (num_frames) *num_frames = (*out)->p.getNumFrames();
+    return 0;
+}
+int cofusion_klg_player_next(cofusion_klg_player* p, int64_t* ts, const float** depth_dev, const uint8_t** rgba_dev)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    bool more = false;
+    GUARD(more = p->p.next(ts, depth_dev, rgba_dev));
+    return more ? 0 : 1;
+}
+int cofusion_klg_player_process(cofusion_klg_player* p)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    bool more = false;
+    GUARD(more = p->p.process());
+    return more ? 0 : 1;
+}
+int cofusion_klg_player_rewind(cofusion_klg_player* p)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    GUARD(p->p.rewind());
+    return 0;
+}
+int cofusion_klg_player_set_limits(cofusion_klg_player* p, int reference_compatible, int frame_limit)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    p->p.setLimits(reference_compatible != 0, frame_limit);
+    return 0;
+}
+void cofusion_klg_player_close(cofusion_klg_player* p) { delete p; }
+
+// ---- test access: the JPEG split and the prefetcher alone (no GPU) ----
+int cofusion_jpeg_front(const uint8_t* stream, uint64_t size, int width, int height, cf_jpeg_header* header, int16_t* coef, uint64_t coef_blocks)
+{
+    if (!stream || !header || !coef || width <= 0 || height <= 0) { g_err = "cofusion_jpeg_front: bad arguments"; return -1; }
+    bool refused = false;
+    const std::string e = jpegFront(stream, (size_t)size, width, height, header, coef, (size_t)coef_blocks, &refused);
+    if (!e.empty()) { g_err = e; return -1; }
+    return refused ? 1 : 0;
+}
+int cofusion_jpeg_finish_host(const cf_jpeg_header* header, const int16_t* coef, uint8_t* rgb)
+{
+    if (!header || !coef || !rgb) { g_err = "cofusion_jpeg_finish_host: bad arguments"; return -1; }
+    jpegFinishHost(header, coef, rgb);
+    return 0;
+}
+struct cofusion_klg_prefetcher {
+    std::vector<std::vector<uint8_t>> store;
+    std::vector<cf_frame_slot> mem;
+    KlgPrefetcher* p = nullptr;
+    int held = -1;
+    ~cofusion_klg_prefetcher() { delete p; }
+};
+int cofusion_klg_prefetch_open(const char* file, int width, int height, int workers, int slots, cofusion_klg_prefetcher** out, int* num_frames)
+{
+    if (!file || !out || width <= 0 || height <= 0 || slots < 2 || slots > 64) { g_err = "cofusion_klg_prefetch_open: bad arguments"; return -1; }
+    auto* q = new cofusion_klg_prefetcher();
+    const size_t N = (size_t)width * height, blocks = (size_t)CF_JPEG_MAX_BLOCKS(width, height);
+    const size_t offCoef = 512, offDepth = offCoef + blocks * 128, offRgb = offDepth + ((N * 2 + 15) & ~(size_t)15);
+    for (int s = 0; s < slots; s++) {
+        q->store.emplace_back(offRgb + N * 3);
+        uint8_t* b = q->store.back().data();
+        q->mem.push_back(cf_frame_slot{reinterpret_cast<cf_jpeg_header*>(b), reinterpret_cast<int16_t*>(b + offCoef), blocks,
+                                       reinterpret_cast<uint16_t*>(b + offDepth), b + offRgb});
+    }
+    q->p = new KlgPrefetcher(file, width, height, q->mem, workers > 0 ? workers : 4);
+    if (!q->p->ok()) { g_err = q->p->error(); delete q; return -1; }
+    if (num_frames) *num_frames = q->p->getNumFrames();
+    *out = q;
+    return 0;
+}
+int cofusion_klg_prefetch_next(cofusion_klg_prefetcher* q, int64_t* ts, int* color_kind, cf_frame_slot* slot)
+{
+    if (!q) { g_err = "null prefetcher"; return -1; }
+    if (q->held >= 0) { q->p->release(q->held); q->held = -1; }
+    if (!q->p->hasMore()) return 1;
+    KlgFrame f;
+    if (!q->p->next(&f)) { g_err = q->p->error(); return -1; }
+    q->held = f.slot;
+    if (ts) *ts = f.timestamp;
+    if (color_kind) *color_kind = f.colorKind;
+    if (slot) *slot = q->mem[(size_t)f.slot];
+    return 0;
+}
+int cofusion_klg_prefetch_rewind(cofusion_klg_prefetcher* q) { if (!q) return -1; q->held = -1; q->p->rewind(); return 0; }
+void cofusion_klg_prefetch_close(cofusion_klg_prefetcher* q) { delete q; }
 
 }  // extern "C"

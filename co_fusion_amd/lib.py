@@ -34,6 +34,7 @@ SYMBOLS = [
     "cf_render_create", "cf_render_destroy", "cf_render", "cf_render_palette",
     "cf_ferns_table", "cf_ferns_create", "cf_ferns_destroy", "cf_ferns_get_table", "cf_ferns_encode", "cf_ferns_search", "cf_ferns_append", "cf_ferns_add_async",
     "cf_ferns_relocalise", "cf_ferns_count", "cf_ferns_download", "cf_ferns_last_search",
+    "cf_frame_decoder_create", "cf_frame_decoder_destroy", "cf_frame_decoder_slot", "cf_frame_decoder_submit", "cf_frame_decoder_acquire", "cf_frame_decoder_timing",
 ]
 
 
@@ -59,6 +60,8 @@ HOST_SYMBOLS = [
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
     "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_relocalisation", "cofusion_reloc_stats",
+    "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
+    "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",
 ]
 _host = None
 

@@ -184,6 +184,40 @@ int cofusion_klg_create(const char *file, int width, int height, int compress_de
 int cofusion_klg_write(cofusion_klg_writer *w, int64_t timestamp, const float *depth_m, const uint8_t *rgb);
 int cofusion_klg_finish(cofusion_klg_writer *w);
 
+/* .klg log player (host/KlgPlayer.h): worker threads read the log ahead (inflate, JPEG entropy decoding) into the
+ * pinned slots of a cf_frame_decoder, the device finishes the frames, and they go into cofusion_process_frame_device -- the same
+ * frames cofusion_klg_next delivers, byte for byte, without the decoding in front of every frame.  workers 1..16 (<= 0: 4).
+ * Refused for world > 1 and for a sequence handle of a lock-step group.  The player must be closed before its instance is destroyed.
+ * _next / _process return 0, 1 at the end of the log, -1 on error (a frame that cannot be decoded fails at its position: the frames
+ * before it are played).  _next: the frame's device buffers (depth f32 [H*W] metres, rgba u8x4 [H*W]), complete or ordered on the
+ * instance's stream as cofusion_config.device_frames_complete says, intact until the next call on this player.
+ * _set_limits: reference_compatible as cofusion_klg_set_reference_compatible; frame_limit >= 0: play at most so many frames. */
+typedef struct cofusion_klg_player cofusion_klg_player;
+int cofusion_klg_player_open(cofusion_handle *h, const char *file, int flip_colors, int workers, cofusion_klg_player **out, int *num_frames);
+int cofusion_klg_player_next(cofusion_klg_player *p, int64_t *timestamp, const float **depth_dev, const uint8_t **rgba_dev);
+int cofusion_klg_player_process(cofusion_klg_player *p);
+int cofusion_klg_player_rewind(cofusion_klg_player *p);
+int cofusion_klg_player_set_limits(cofusion_klg_player *p, int reference_compatible, int frame_limit);
+void cofusion_klg_player_close(cofusion_klg_player *p);
+
+/* Test access to the two host halves of the player, usable without a GPU.
+ * The JPEG decoder split at the coefficient boundary (host/Jpeg.cpp): _front writes the header and the quantised coefficients
+ * (coef_blocks * 64 int16, CF_JPEG_MAX_BLOCKS(width, height) blocks always suffice) and returns 0, 1 when it refuses the stream (a
+ * 16-bit quantisation table, a DC predictor outside int16: the player decodes such a frame on the host), -1 on a decoding error;
+ * _finish_host is the host back end from that representation: rgb [H*W*3] in libjpeg's channel order. */
+int cofusion_jpeg_front(const uint8_t *stream, uint64_t size, int width, int height, cf_jpeg_header *header, int16_t *coef,
+                        uint64_t coef_blocks);
+int cofusion_jpeg_finish_host(const cf_jpeg_header *header, const int16_t *coef, uint8_t *rgb);
+/* The prefetcher alone over slots from malloc: _next delivers the next frame in log order (0; 1 at the end; -1 on error) and takes
+ * back the slot of the previous one; slot (nullable) receives the frame's staging: depth u16 mm, and by *color_kind (CF_FRAME_COLOR_*)
+ * header + coef or rgb. */
+typedef struct cofusion_klg_prefetcher cofusion_klg_prefetcher;
+int cofusion_klg_prefetch_open(const char *file, int width, int height, int workers, int slots, cofusion_klg_prefetcher **out,
+                               int *num_frames);
+int cofusion_klg_prefetch_next(cofusion_klg_prefetcher *p, int64_t *timestamp, int *color_kind, cf_frame_slot *slot);
+int cofusion_klg_prefetch_rewind(cofusion_klg_prefetcher *p);
+void cofusion_klg_prefetch_close(cofusion_klg_prefetcher *p);
+
 #ifdef __cplusplus
 }
 #endif

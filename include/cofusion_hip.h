@@ -646,6 +646,56 @@ int cf_ferns_download(cf_ferns *f, int id, uint8_t *codes, int *good, float pose
 int cf_ferns_last_search(cf_ferns *f, int32_t *co_host, int co_capacity, int *searched, float *min_all, float *min_match, int *match_id,
                          int *appended);
 
+/* ------------------------------------------- frame decoder of the .klg log player ---- */
+/* Finishes the frames of a .klg log on the device (csrc/frame_decode.hip): host threads inflate the depth and
+ * entropy-decode the JPEG into a pinned slot, two launches do the rest -- dequantisation + libjpeg's "islow" IDCT, then chroma
+ * upsampling + colour conversion to RGBA8 side by side with u16 mm -> f32 metres.  Integer arithmetic throughout: the outputs equal
+ * host/KlgIO.cpp + host/Jpeg.cpp byte for byte.
+ * cf_jpeg_header + coefficients are what the JPEG front end (host/Jpeg.cpp) leaves: QUANTISED int16 coefficients, 64 per block in
+ * natural (de-zigzagged) order, blocks in raster order per component, components planar (comp[c].first = block offset). */
+typedef struct { int32_t h, v, bw, bh, first; } cf_jpeg_comp;  /* sampling factors, block grid (mx*h x my*v), first block */
+typedef struct {
+    int32_t width, height, ncomp /* 1 or 3 */, hmax, vmax, total_blocks;
+    cf_jpeg_comp comp[3];
+    uint8_t qt[3][64];      /* per component, natural order */
+} cf_jpeg_header;
+/* blocks a width x height frame can have at most, whatever its sampling factors (<= 4): three components at the density of the
+ * densest, MCUs of at most 32 x 32 */
+#define CF_JPEG_MAX_BLOCKS(w, h) (48ull * (uint64_t)(((w) + 31) / 32) * (uint64_t)(((h) + 31) / 32))
+#define CF_FRAME_COLOR_NONE 0     /* no colour block in the log: RGBA = 0, 0, 0, 255 */
+#define CF_FRAME_COLOR_JPEG 1     /* slot header + coef */
+#define CF_FRAME_COLOR_RAW 2      /* slot rgb = the log's 3 B/px block (KlgLogReader::getNext: channels reversed only with flip_colors) */
+#define CF_FRAME_COLOR_DECODED 3  /* slot rgb = a host-decoded JPEG in libjpeg's order (reversed UNLESS flip_colors, like _JPEG) */
+typedef struct {
+    int32_t width, height;        /* 1..max of the decoder */
+    int32_t color_kind;           /* CF_FRAME_COLOR_* */
+    int32_t flip_colors;          /* LogReader::flipColors */
+} cf_frame_desc;
+typedef struct {                  /* pinned host staging of one slot */
+    cf_jpeg_header *header;
+    int16_t *coef;                /* coef_blocks * 64 entries */
+    uint64_t coef_blocks;         /* CF_JPEG_MAX_BLOCKS(max_w, max_h) */
+    uint16_t *depth;              /* max_w * max_h, millimetres */
+    uint8_t *rgb;                 /* max_w * max_h * 3 */
+} cf_frame_slot;
+typedef struct cf_frame_decoder cf_frame_decoder;
+/* slots: 2..16.  Owns the pinned slots, as many device input buffers and output frames (depth f32 [H*W], rgba u8x4 [H*W], alpha 255),
+ * a non-blocking stream of its own and one event per slot; nothing is allocated per frame.  Any max_w, max_h >= 1. */
+int cf_frame_decoder_create(cf_ctx *ctx, int max_w, int max_h, int slots, cf_frame_decoder **out);
+void cf_frame_decoder_destroy(cf_frame_decoder *dec);
+int cf_frame_decoder_slot(cf_frame_decoder *dec, int slot, cf_frame_slot *out);
+/* Copies the slot's staging to the device and launches the two kernels on the decoder's stream, ordered after what the context's
+ * stream holds at this moment (the reader of the output frame this slot produced before), then records the slot's event.
+ * The slot's host memory must stay untouched until the event has passed (cf_frame_decoder_acquire with complete = 1). */
+int cf_frame_decoder_submit(cf_frame_decoder *dec, int slot, const cf_frame_desc *desc);
+/* The output frame of the slot's last submit.  complete = 1: the host blocks on the slot's event (buffers complete at return:
+ * cofusion_config.device_frames_complete = 1); complete = 0: the context's stream waits for it (consumed in stream order).
+ * The pointers (each nullable) stay valid, and the frame intact, until the slot's next submit. */
+int cf_frame_decoder_acquire(cf_frame_decoder *dec, int slot, int complete, const float **depth_dev, const uint8_t **rgba_dev);
+/* accumulated device-event durations of the two kernels over all submits while timing is on (cf_frame_decoder_timing(dec, 1): a
+ * diagnostics mode that adds event pairs to every submit); reading waits for the decoder's stream and resets the sums */
+int cf_frame_decoder_timing(cf_frame_decoder *dec, int on, double *idct_ms, double *finish_ms, uint64_t *frames);
+
 /* micro-benchmark of the ICP reduction on the state of the last tracking call (level 0..2) */
 int cf_odom_bench_icp(cf_odom *od, int level, int iters, float *avg_us);
 

@@ -4,10 +4,12 @@ does head-less, GUI/MainController.cpp):
 
     python tools/run_klg.py seq.klg out/ [--static] [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240]
                             [--frames N] [--flip-colors] [--export-segmentation]
-                            [--export-labels] [--export-normals] [--export-viewport]
+                            [--export-labels] [--export-normals] [--export-viewport] [--player [--workers N]]
 
 Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png, out/Labels<tick>.png, out/Normals<tick>.png,
-out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s."""
+out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s.  --player reads the log ahead on
+worker threads and finishes the frames on the device (klg.KlgPlayer) instead of decoding each frame in front of its processing: the
+same frames, the same outputs."""
 import argparse
 import os
 import sys
@@ -36,11 +38,13 @@ def main():
     ap.add_argument("--photo-threshold", type=float, default=115.0)
     ap.add_argument("--fern-min-age", type=int, default=300, help="ticks a keyframe must be old to be matched")
     ap.add_argument("--fern-seed", type=int, default=0)
+    ap.add_argument("--player", action="store_true", help="threaded prefetch + JPEG finished on the device (default: the serial reader)")
+    ap.add_argument("--workers", type=int, default=4, help="host threads of --player (1..16)")
     a = ap.parse_args()
     from co_fusion_amd import facade, klg
     os.makedirs(a.outdir, exist_ok=True)
     prefix = a.outdir.rstrip("/") + "/"
-    log = klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
+    log = None if a.player else klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
     cf = facade.CoFusion(a.width, a.height, a.fx, a.fy, a.cx, a.cy, max_surfels=a.max_surfels, enable_multiple_models=int(not a.static),
                          enable_pose_logging=1, reloc=int(a.relocalise))
     if a.relocalise:
@@ -50,13 +54,20 @@ def main():
     if a.export_labels or a.export_normals or a.export_viewport:
         cf.set_export_views(prefix, labels=a.export_labels, normals=a.export_normals, viewport=a.export_viewport)
     n, t0 = 0, time.perf_counter()
-    for ts, depth, rgb in log:
-        cf.process_frame(depth, rgb, timestamp=ts)
-        n += 1
-        if 0 < a.frames <= n:
-            break
+    if a.player:
+        log = klg.KlgPlayer(cf, a.log, flip_colors=a.flip_colors, workers=a.workers)
+        log.set_limits(frame_limit=a.frames if a.frames > 0 else -1)
+        n = log.play()
+        log.close()
+    else:
+        for ts, depth, rgb in log:
+            cf.process_frame(depth, rgb, timestamp=ts)
+            n += 1
+            if 0 < a.frames <= n:
+                break
     dt = time.perf_counter() - t0
-    print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s incl. log decoding and upload), {cf.num_models} active models")
+    how = f"log player, {a.workers} workers" if a.player else "incl. log decoding and upload"
+    print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s {how}), {cf.num_models} active models")
     if a.relocalise:
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
     print(f"exported {cf.export_poses(prefix)} pose file(s), {cf.save_ply(prefix)} PLY cloud(s) to {prefix}")
