@@ -18,6 +18,7 @@
 
 #include "cf_host.h"
 #include "cf_surfel_device.h"
+#include "cf_segment.h"
 
 using namespace cf;
 
@@ -104,11 +105,7 @@ __device__ __forceinline__ long long q32(float v)
     return __double2ll_rn((double)c * 4294967296.0);
 }
 
-// The kernels of the segmentation chain take the arguments of up to kSegBatch segmenters (the sequences of a lock-step group, all of
-// one image size) in the kernel-argument segment and pick theirs with the grid's last dimension: one chain of launches for the group
-// instead of one per sequence.  A single segmenter is a batch of one.
-constexpr int kSegBatch = 8;
-template <class A, int N = kSegBatch> struct SegBatch { A m[N]; };
+// (kSegBatch / SegBatch: cf_segment.h)
 
 struct AccArgs {
     const int* labels; const float* depth;
@@ -451,31 +448,8 @@ struct SegUnaryArgs {
     float* depth_range;              // [1]
 };
 
-// Sequential f32 sum init + t[0] + t[1] + ... + t[n-1] (this order) by ONE wave.  term(j) -> the j-th term, 0.0f for "skip" (x + 0.0f == x
-// for every x these sums can reach -- a running sum that starts at +0.0f is never -0.0f --, so skipping an element and adding zero agree).
-// Returns the sum in every lane.
-// Rounds 3-6 moved ONE term per step to the adder (v_readlane, an LDS broadcast, a lane shift): 11-14 ns per addition whichever way, because
-// every step pays a cross-lane operation on top of the addition.  Late in round 6 the terms are BLOCKED instead: lane l owns kSeqBlock
-// consecutive terms of a super-block of 64 x kSeqBlock; in "phase" l every lane adds its own block to the running sum -- sixteen dependent
-// plain v_add_f32 from registers -- and the value lane l arrives at (the only one that started from the true prefix and added the right
-// terms) is read back as the running sum of phase l + 1.  One cross-lane operation per sixteen additions: 8 ns per addition (what a
-// dependent v_add_f32 of a lone wave costs here), 13.4 -> 9.8 us for the average confidences of 1 200 superpixels.  A lane whose block
-// holds only zeros has no phase at all.  The additions and their order are exactly those of the serial loop.
-constexpr int kSeqBlock = 16;
-// the phases of one super-block: lane l holds its kSeqBlock consecutive terms in t[], `any` = one of them is not zero
-__device__ __forceinline__ float seq_block_phases(float sum, const float (&t)[kSeqBlock], bool any)
-{
-    unsigned long long nz = __ballot(any);
-    while (nz) {   // (uniform)
-        const int ph = __builtin_ctzll(nz);
-        nz &= nz - 1;
-        float x = sum;
-#pragma unroll
-        for (int c = 0; c < kSeqBlock; c++) x = x + t[c];
-        sum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), ph));
-    }
-    return sum;
-}
+// (the blocked sequential chain -- kSeqBlock, seq_block_phases and why skipping zero terms is exact -- lives in cf_segment.h: the mask
+// branch of segment_masks.hip walks its sums with the same chain)
 template <class F>
 __device__ __forceinline__ float wave_sequential_sum(float init, int n, int lane, F term)
 {
@@ -1143,38 +1117,12 @@ __global__ void __launch_bounds__(64) pose_publish_kernel(const PosePublishArgs 
     tail[m * kPoseWords + w] = v;
 }
 
-struct cf_segmenter {
-    cf_ctx* ctx = nullptr;
-    int gx = 0, gy = 0, K = 0;
-    int Lcap = 16;                       // label capacity of the buffers = max(16, the context's max_models) (a new label needs a free model slot)
-    const void** d_acc_ptrs = nullptr;   // [2][Lcap] device copies of the models' ICP-error / vertex-confidence image pointers (> kAccTile models)
-    const void** h_acc_ptrs = nullptr;   // pinned staging of the same
-    int* labels = nullptr;
-    float* centres = nullptr;
-    unsigned long long* slic_sums = nullptr;
-    unsigned* spix_count = nullptr; unsigned* depth_count = nullptr;
-    unsigned long long *depth_sum = nullptr, *icp_sum = nullptr, *conf_sum = nullptr;
-    int* resample = nullptr;
-    unsigned char* low_map = nullptr;
-    float *feat1 = nullptr, *feat2 = nullptr, *norm = nullptr, *K1t = nullptr, *K2t = nullptr;
-    float* partial = nullptr;            // chunk partial sums [kCrfChunks][K][2][Lcap]
-    std::vector<float> smooth_cache;     // host copy of the smoothness features K1t was built from
-    float *unary = nullptr, *Q0 = nullptr, *Q1 = nullptr;
-    // device-side unaries / post-processing (cf_seg_sums / cf_seg_infer / cf_seg_fetch)
-    float *raw_mean = nullptr, *low_mean = nullptr;   // [(1 + 2 Lcap)][K]
-    float *avg_conf = nullptr, *depth_range = nullptr;
-    int *parent = nullptr, *comp = nullptr, *cc = nullptr;
-    cf_seg_result* d_result = nullptr;
-    cf_seg_result* h_result = nullptr;   // pinned
-    unsigned char* h_low_map = nullptr;  // pinned [K]
-    long long* h_pose_tail = nullptr;    // pinned [Lcap][kPoseWords]: the tail of the sums block after the caller's all-reduce
-    bool poses_published = false;
-    bool grid_kernel_built = false;      // K1t holds the kernel of the grid's own smoothness features (seg_feat1_kernel)
-};
+// (struct cf_segmenter: cf_segment.h)
 
 template <typename T>
 static int seg_malloc(cf_ctx* ctx, T** p, size_t count)
 {
+    if (count == 0) return CF_OK;   // (a segmenter of the mask branch alone has no superpixel grid: K == 0)
     HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
     HIPCHK(ctx, hipMemsetAsync(*p, 0, count * sizeof(T), ctx->stream));
     return CF_OK;
@@ -1197,19 +1145,23 @@ static int acc_pointers(cf_segmenter* s, AccArgs& a, int n_models, const float* 
 
 extern "C" {
 
-int cf_seg_create(cf_ctx* ctx, cf_segmenter** out)
+// masks_only: no superpixel grid (K == 0) -- the label-mask branch works on whole images of any size the context accepts
+static int seg_create(cf_ctx* ctx, cf_segmenter** out, bool masks_only)
 {
     if (!ctx || !out) return CF_EINVAL;
-    if ((ctx->cfg.width % kSpix) || (ctx->cfg.height % kSpix)) { ctx->set_error("segmentation needs width/height multiples of 16"); return CF_EINVAL; }
-    if ((ctx->cfg.width / kSpix) * (ctx->cfg.height / kSpix) > kSegMaxK) { ctx->set_error("segmentation supports at most 4800 superpixels (1280x960)"); return CF_EINVAL; }
+    if (!masks_only) {
+        if ((ctx->cfg.width % kSpix) || (ctx->cfg.height % kSpix)) { ctx->set_error("segmentation needs width/height multiples of 16"); return CF_EINVAL; }
+        if ((ctx->cfg.width / kSpix) * (ctx->cfg.height / kSpix) > kSegMaxK) { ctx->set_error("segmentation supports at most 4800 superpixels (1280x960)"); return CF_EINVAL; }
+    }
     cf_segmenter* s = new cf_segmenter();
-    s->ctx = ctx; s->gx = ctx->cfg.width / kSpix; s->gy = ctx->cfg.height / kSpix; s->K = s->gx * s->gy;
+    s->ctx = ctx;
+    if (!masks_only) { s->gx = ctx->cfg.width / kSpix; s->gy = ctx->cfg.height / kSpix; s->K = s->gx * s->gy; }
     *out = s;
     s->Lcap = ctx->cfg.max_models < 16 ? 16 : (ctx->cfg.max_models > kMaxL - 1 ? kMaxL - 1 : ctx->cfg.max_models);   // at least 16 (as before round 4); ids 0..254, 255 = rejected
     const size_t N = (size_t)ctx->cfg.width * ctx->cfg.height, K = (size_t)s->K, Lc = (size_t)s->Lcap;
     if (int r = seg_malloc(ctx, &s->d_acc_ptrs, 2 * Lc)) return r;
     HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_acc_ptrs), sizeof(void*) * 2 * Lc));
-    if (int r = seg_malloc(ctx, &s->labels, N)) return r;
+    if (int r = seg_malloc(ctx, &s->labels, masks_only ? (size_t)0 : N)) return r;
     if (int r = seg_malloc(ctx, &s->centres, K * 5)) return r;
     if (int r = seg_malloc(ctx, &s->slic_sums, K * 6)) return r;
     if (int r = seg_malloc(ctx, &s->spix_count, K)) return r;
@@ -1239,11 +1191,22 @@ int cf_seg_create(cf_ctx* ctx, cf_segmenter** out)
     if (int r = seg_malloc(ctx, &s->cc, 6 * K)) return r;
     if (int r = seg_malloc(ctx, &s->d_result, (size_t)1)) return r;
     HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(cf_seg_result), hipHostMallocCoherent));  // seg_post_kernel stores into it
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_low_map), ((size_t)K + 3) / 4 * 4, hipHostMallocCoherent));  // written as 32-bit words by seg_post_kernel
+    if (K) HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_low_map), ((size_t)K + 3) / 4 * 4, hipHostMallocCoherent));  // written as 32-bit words by seg_post_kernel
     memset(s->h_result, 0, sizeof(cf_seg_result));
+    // the mask branch: two work blocks, both in the state a job expects to find (cf_segment.h: kMaskWork)
+    if (int r = seg_malloc(ctx, &s->mask_work, (size_t)2 * kMaskWork)) return r;
+    {
+        const unsigned none = 0xffffffffu;
+        for (int b = 0; b < 2; b++) HIPCHK(ctx, hipMemcpyAsync(s->mask_work + b * kMaskWork, &none, sizeof(none), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_mask_new), sizeof(int), hipHostMallocCoherent));  // stored by mask_stats_kernel
+    *s->h_mask_new = -1;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return CF_OK;
 }
+
+int cf_seg_create(cf_ctx* ctx, cf_segmenter** out) { return seg_create(ctx, out, false); }
+int cf_seg_create_masks(cf_ctx* ctx, cf_segmenter** out) { return seg_create(ctx, out, true); }
 
 void cf_seg_destroy(cf_segmenter* s)
 {
@@ -1251,8 +1214,10 @@ void cf_seg_destroy(cf_segmenter* s)
     (void)hipStreamSynchronize(s->ctx->stream);
     void* ptrs[] = {s->labels, s->centres, s->slic_sums, s->spix_count, s->depth_count, s->depth_sum, s->icp_sum, s->resample,
                     s->low_map, s->feat1, s->feat2, s->norm, s->K1t, s->K2t, s->partial, s->unary, s->Q0, s->Q1,
-                    s->raw_mean, s->low_mean, s->avg_conf, s->depth_range, s->parent, s->comp, s->cc, s->d_result, (void*)s->d_acc_ptrs};
-    for (void* p : ptrs) (void)hipFree(p);
+                    s->raw_mean, s->low_mean, s->avg_conf, s->depth_range, s->parent, s->comp, s->cc, s->d_result, (void*)s->d_acc_ptrs,
+                    s->mask_work};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (s->h_mask_new) (void)hipHostFree(s->h_mask_new);
     if (s->h_result) (void)hipHostFree(s->h_result);
     if (s->h_low_map) (void)hipHostFree(s->h_low_map);
     if (s->h_pose_tail) (void)hipHostFree(s->h_pose_tail);
@@ -1263,7 +1228,7 @@ void cf_seg_destroy(cf_segmenter* s)
 // Slic::setInputImage + processFrame (Slic.cpp:48-81): labels stay on the device
 int cf_seg_slic(cf_segmenter* s, const uint8_t* rgba)
 {
-    if (!s || !rgba) return CF_EINVAL;
+    if (!s || !rgba || !s->K) return CF_EINVAL;
     cf_ctx* ctx = s->ctx; hipStream_t st = ctx->stream;
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     const uchar4* img = reinterpret_cast<const uchar4*>(rgba);
@@ -1284,7 +1249,7 @@ int cf_seg_accumulate(cf_segmenter* s, const float* depth, int n_models, const f
                       uint32_t* spix_count_host, uint32_t* depth_count_host, int64_t* depth_sum_host, int64_t* icp_sum_host,
                       int64_t* conf_sum_host, int32_t* resample_labels_host)
 {
-    if (!s || !depth || n_models < 0 || n_models > s->Lcap) return CF_EINVAL;
+    if (!s || !s->K || !depth || n_models < 0 || n_models > s->Lcap) return CF_EINVAL;
     cf_ctx* ctx = s->ctx; hipStream_t st = ctx->stream;
     const size_t K = (size_t)s->K;
     HIPCHK(ctx, hipMemsetAsync(s->spix_count, 0, sizeof(unsigned) * K, st));
@@ -1342,7 +1307,7 @@ static void build_grid_kernel(cf_segmenter* s, bool make_features)
 int cf_seg_crf(cf_segmenter* s, const float* unary_host, int L, const float* feat_smooth_host, const float* feat_app_host,
                float w_smooth, float w_app, int iterations, float* Q_host)
 {
-    if (!s || !unary_host || !Q_host || L <= 0 || L > s->Lcap) return CF_EINVAL;
+    if (!s || !s->K || !unary_host || !Q_host || L <= 0 || L > s->Lcap) return CF_EINVAL;
     cf_ctx* ctx = s->ctx; hipStream_t st = ctx->stream;
     const int n = s->K;
     HIPCHK(ctx, hipMemcpyAsync(s->unary, unary_host, sizeof(float) * n * L, hipMemcpyHostToDevice, st));
@@ -1369,7 +1334,7 @@ int cf_seg_crf(cf_segmenter* s, const float* unary_host, int L, const float* fea
 // Slic::upsample<unsigned char> (Slic.h:127-139): full-resolution label mask on the device
 int cf_seg_upsample(cf_segmenter* s, const uint8_t* low_map_host, uint8_t* full_dev)
 {
-    if (!s || !low_map_host || !full_dev) return CF_EINVAL;
+    if (!s || !s->K || !low_map_host || !full_dev) return CF_EINVAL;
     cf_ctx* ctx = s->ctx; hipStream_t st = ctx->stream;
     const int N = ctx->cfg.width * ctx->cfg.height;
     HIPCHK(ctx, hipMemcpyAsync(s->low_map, low_map_host, (size_t)s->K, hipMemcpyHostToDevice, st));
@@ -1416,7 +1381,7 @@ static int enqueue_accumulate(cf_ctx* ctx, const SegJob* jobs, int S)
 int cf_seg_sums(cf_segmenter* s, const float* depth, int n_models, const float* const* icp_err, const float* const* vertconf4,
                 int64_t** sums_dev, uint64_t* sums_words)
 {
-    if (!s || !depth || n_models <= 0 || n_models > s->Lcap || !icp_err || !vertconf4) return CF_EINVAL;
+    if (!s || !s->K || !depth || n_models <= 0 || n_models > s->Lcap || !icp_err || !vertconf4) return CF_EINVAL;
     SegJob job{};
     job.s = s; job.depth = depth; job.n_models = n_models; job.icp_err = icp_err; job.vertconf4 = vertconf4;
     if (int r = enqueue_accumulate(s->ctx, &job, 1)) return r;
@@ -1539,7 +1504,7 @@ extern "C" {
 int cf_seg_infer(cf_segmenter* s, const cf_seg_params* P, const uint8_t* rgba, int n_models, const uint32_t* model_ids, uint32_t next_model_id,
                  int allow_new, uint8_t* full_dev)
 {
-    if (!s || !P || !rgba || !model_ids || !full_dev || n_models <= 0) return CF_EINVAL;
+    if (!s || !s->K || !P || !rgba || !model_ids || !full_dev || n_models <= 0) return CF_EINVAL;
     const int L = n_models + (allow_new ? 1 : 0);
     if (L > s->Lcap) { s->ctx->set_error("segmentation: more labels than the context's max_models (" + std::to_string(s->Lcap) + ")"); return CF_EINVAL; }
     SegJob job{};
@@ -1559,7 +1524,7 @@ int cf_seg_run_batch(cf_ctx* ctx, const cf_seg_params* P, const cf_seg_job* jobs
     bool batchable = true;
     for (int e = 0; e < n_jobs; e++) {
         const cf_seg_job& j = jobs_in[e];
-        if (!j.seg || j.seg->ctx != ctx || !j.depth || !j.icp_err || !j.vertconf4 || !j.rgba || !j.model_ids || !j.full_dev || j.n_models <= 0) return CF_EINVAL;
+        if (!j.seg || !j.seg->K || j.seg->ctx != ctx || !j.depth || !j.icp_err || !j.vertconf4 || !j.rgba || !j.model_ids || !j.full_dev || j.n_models <= 0) return CF_EINVAL;
         const int L = j.n_models + (j.allow_new ? 1 : 0);
         if (L > j.seg->Lcap) { ctx->set_error("segmentation: more labels than the context's max_models (" + std::to_string(j.seg->Lcap) + ")"); return CF_EINVAL; }
         for (int k = 0; k < e; k++) if (jobs_in[k].seg == j.seg) return CF_EINVAL;
@@ -1587,7 +1552,12 @@ int cf_seg_fetch(cf_segmenter* s, cf_seg_result* out, uint8_t* low_map_host)
     if (!s || !out) return CF_EINVAL;
     if (int r = cf_wait_stream(s->ctx)) return r;
     *out = *s->h_result;
-    if (low_map_host) memcpy(low_map_host, s->h_low_map, (size_t)s->K);
+    if (low_map_host && s->K) memcpy(low_map_host, s->h_low_map, (size_t)s->K);
+    if (s->mask_pending) {  // the rows are those of a mask job (segment_masks.hip): its new mask value came with them
+        s->mask_pending = false;
+        s->mask_new_value = *s->h_mask_new;
+        s->mask_value_valid = true;
+    }
     return CF_OK;
 }
 

@@ -44,6 +44,13 @@ def rccl_unique_id():
     return bytes(buf)
 
 
+def _check_mask_tensor(mask, depth_t):
+    if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != tuple(depth_t.shape):
+        raise CoFusionError("mask: a contiguous CUDA uint8 tensor of the depth image's shape is expected")
+    if mask.data_ptr() % 16:
+        raise CoFusionError("mask: the tensor's storage must be 16-byte aligned")
+
+
 def _make_config(lib, width, height, fx, fy, cx, cy, device, kw):
     cfg = Config()
     lib.cofusion_default_config(C.byref(cfg))
@@ -279,12 +286,26 @@ class CoFusion:
                                                     None if m is None else m.ctypes.data_as(C.c_void_p),
                                                     None if p is None else p.ctypes.data_as(C.c_void_p)))
 
-    def process_frame_device(self, depth_t, rgba_t, in_pose=None, timestamp=0):
-        """Frame already resident in HBM: torch CUDA tensors depth f32 [H,W], rgba u8 [H,W,4]."""
+    def process_frame_device(self, depth_t, rgba_t, in_pose=None, timestamp=0, mask=None):
+        """Frame already resident in HBM: torch CUDA tensors depth f32 [H,W], rgba u8 [H,W,4]; mask (optional): its label mask, a
+        contiguous torch CUDA tensor u8 [H,W] -- the mask branch of the segmentation then runs as kernels (world == 1 only)."""
         p = None if in_pose is None else np.ascontiguousarray(in_pose, np.float32).reshape(16)
+        if mask is not None:
+            _check_mask_tensor(mask, depth_t)
+            self._check(self.lib.cofusion_process_frame_device_masked(self.h, C.c_int64(timestamp), C.c_void_p(depth_t.data_ptr()),
+                                                                      C.c_void_p(rgba_t.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                                      None if p is None else p.ctypes.data_as(C.c_void_p)))
+            return
         self._check(self.lib.cofusion_process_frame_device(self.h, C.c_int64(timestamp), C.c_void_p(depth_t.data_ptr()),
                                                            C.c_void_p(rgba_t.data_ptr()),
                                                            None if p is None else p.ctypes.data_as(C.c_void_p)))
+
+    def process_frame_device_ptr(self, depth_ptr, rgba_ptr, mask_ptr=None, in_pose=None, timestamp=0):
+        """the same with plain device addresses (e.g. the frame klg.KlgPlayer's iteration hands out); mask_ptr: 16-byte aligned or None"""
+        p = None if in_pose is None else np.ascontiguousarray(in_pose, np.float32).reshape(16)
+        self._check(self.lib.cofusion_process_frame_device_masked(self.h, C.c_int64(timestamp), C.c_void_p(depth_ptr), C.c_void_p(rgba_ptr),
+                                                                  C.c_void_p(mask_ptr) if mask_ptr else None,
+                                                                  None if p is None else p.ctypes.data_as(C.c_void_p)))
 
     @property
     def num_models(self):
@@ -417,10 +438,19 @@ class CoFusionGroup:
             self.g, ts, P(*[r.ctypes.data for r in keep[self.n:]]), P(*[d.ctypes.data for d in keep[:self.n]]),
             P(*[None if m is None else m.ctypes.data for m in mk]) if masks is not None else None))
 
-    def process_frames_device(self, depth_ts, rgba_ts, timestamp=0):
-        """one frame per sequence already resident in HBM: torch CUDA tensors depth f32 [H,W], rgba u8 [H,W,4]"""
+    def process_frames_device(self, depth_ts, rgba_ts, timestamp=0, masks=None):
+        """one frame per sequence already resident in HBM: torch CUDA tensors depth f32 [H,W], rgba u8 [H,W,4]; masks (optional):
+        masks[s] a contiguous torch CUDA tensor u8 [H,W] or None (that sequence runs the motion segmentation)"""
         P = C.c_void_p * self.n
         ts = (C.c_int64 * self.n)(*([timestamp] * self.n))
+        if masks is not None:
+            for m, d in zip(masks, depth_ts):
+                if m is not None:
+                    _check_mask_tensor(m, d)
+            self._check(self.lib.cofusion_group_process_frames_device_masked(
+                self.g, ts, P(*[t.data_ptr() for t in depth_ts]), P(*[t.data_ptr() for t in rgba_ts]),
+                P(*[None if m is None else m.data_ptr() for m in masks])))
+            return
         self._check(self.lib.cofusion_group_process_frames_device(self.g, ts, P(*[t.data_ptr() for t in depth_ts]),
                                                                   P(*[t.data_ptr() for t in rgba_ts])))
 

@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <condition_variable>
 #include <exception>
@@ -438,6 +439,57 @@ void Segmentation::runBatch(cf_ctx* ctx, const Segmentation& params, const std::
     check(ctx, cf_seg_run_batch(ctx, &P, jobs.data(), (int)jobs.size()), "cf_seg_run_batch");
 }
 
+// ---- the label-mask branch on the device (csrc/segment_masks.hip) ----
+void Segmentation::collectMasks(ModelList& models, const uint8_t* mask_in_dev, const float* depth_dev, unsigned char nextModelID, bool allowNew,
+                                uint8_t* full_dev, cf_seg_mask_job& job)
+{
+    const int n_models = (int)models.size();
+    jobIds.resize(n_models);
+    int m = 0;
+    for (auto& mdl : models) jobIds[m++] = mdl->getID();
+    job = cf_seg_mask_job{};
+    job.seg = seg; job.mask_dev = mask_in_dev; job.depth_dev = depth_dev; job.n_models = n_models; job.model_ids = jobIds.data();
+    job.next_model_id = nextModelID; job.allow_new = allowNew ? 1 : 0; job.mapping = gtMapping; job.full_dev = full_dev;
+    pendingModels = n_models; pendingNextId = nextModelID;
+    posesPublished = false;
+}
+
+void Segmentation::enqueueMasks(ModelList& models, const uint8_t* mask_in_dev, const float* depth_dev, unsigned char nextModelID, bool allowNew,
+                                uint8_t* full_dev)
+{
+    PhaseTimer pt(PhaseTimes::SegSlicAccumulate);
+    cf_seg_mask_job job;
+    collectMasks(models, mask_in_dev, depth_dev, nextModelID, allowNew, full_dev, job);
+    check(ctx, cf_seg_masks(&job), "cf_seg_masks");
+}
+
+void Segmentation::runMaskBatch(cf_ctx* ctx, const std::vector<cf_seg_mask_job>& jobs)
+{
+    if (jobs.empty()) return;
+    PhaseTimer pt(PhaseTimes::SegSlicAccumulate);
+    check(ctx, cf_seg_masks_batch(ctx, jobs.data(), (int)jobs.size()), "cf_seg_masks_batch");
+}
+
+SegmentationResult Segmentation::finishMasks()
+{
+    PhaseTimer pt(PhaseTimes::SegPost);
+    SegmentationResult result;
+    cf_seg_result r{};
+    check(ctx, cf_seg_fetch(seg, &r, nullptr), "cf_seg_fetch");
+    int value = -1;
+    check(ctx, cf_seg_new_mask_value(seg, &value), "cf_seg_new_mask_value");
+    if (value >= 0) gtMapping[value & 255] = pendingNextId;   // Segmentation.cpp:80: the function-static mapping of the reference
+    result.hasNewLabel = r.has_new_label != 0;
+    for (int i = 0; i < r.n_models; i++) {
+        SegmentationResult::ModelData md;
+        md.id = r.model[i].id; md.modelIndex = i < pendingModels ? i : -1;
+        md.superPixelCount = r.model[i].superPixelCount; md.avgConfidence = r.model[i].avgConfidence;
+        md.depthMean = r.model[i].depthMean; md.depthStd = r.model[i].depthStd;
+        result.modelData.push_back(md);
+    }
+    return result;
+}
+
 bool Segmentation::fetchPublishedPoses(size_t nModels, std::vector<int64_t>& words)
 {
     if (!posesPublished || (int)nModels != pendingModels) return false;
@@ -813,10 +865,14 @@ CoFusion::CoFusion(const Config& c, cf_ctx* shared, int sequenceIndex)
     check(ctx, cf_malloc(ctx, N * 4, &p), "cf_malloc"); rgba_dev = static_cast<uint8_t*>(p);
     check(ctx, cf_malloc(ctx, N * 3, &p), "cf_malloc"); rgb_dev = static_cast<uint8_t*>(p);
     check(ctx, cf_malloc(ctx, N, &p), "cf_malloc"); mask_dev = static_cast<uint8_t*>(p);  // zero-filled: the -static mask
-    // host-input path: two pinned staging sets (depth f32 + rgb u8x3), so that copying frame t+1 into one does not wait
+    // a host label mask takes the device branch of the segmentation too (single GPU): uploaded with the frame, through the same
+    // staging sets -- owned from creation, no allocation per frame.  CF_MASKS_HOST=1 (diagnostics) keeps the host loops.
+    hostMasksOnDevice = dist.world == 1 && cfg.enableMultipleModels && !(getenv("CF_MASKS_HOST") && atoi(getenv("CF_MASKS_HOST")));
+    if (hostMasksOnDevice) { check(ctx, cf_malloc(ctx, N, &p), "cf_malloc"); maskIn_dev = static_cast<uint8_t*>(p); }
+    // host-input path: two pinned staging sets (depth f32 + rgb u8x3 + mask u8), so that copying frame t+1 into one does not wait
     // for the transfer of frame t out of the other
     for (int b = 0; b < 2; b++) {
-        check(ctx, cf_malloc_host(ctx, N * 4 + N * 3, &p), "cf_malloc_host"); stage[b] = static_cast<uint8_t*>(p);
+        check(ctx, cf_malloc_host(ctx, N * 4 + N * 3 + N, &p), "cf_malloc_host"); stage[b] = static_cast<uint8_t*>(p);
     }
     globalModel = std::make_shared<Model>(ctx, getNextModelID(true), cfg.confGlobalInit, true, cfg.maxSurfels, 3.402823466e+38f,
                                           dist.ownsHere(0));
@@ -843,6 +899,7 @@ CoFusion::~CoFusion()
     cf_free(ctx, depth_dev);
     for (int b = 0; b < 2; b++) { cf_free(ctx, depthFilteredBuf[b]); cf_free(ctx, depthPyr1Buf[b]); cf_free(ctx, depthPyr2Buf[b]); }
     cf_free(ctx, rgba_dev); cf_free(ctx, rgb_dev); cf_free(ctx, mask_dev);
+    if (maskIn_dev) cf_free(ctx, maskIn_dev);
     for (int b = 0; b < 2; b++) if (stage[b]) cf_free_host(ctx, stage[b]);
     labelGenerator.reset();
     if (rcclStage) cf_free(ctx, rcclStage);
@@ -1110,9 +1167,12 @@ void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float wei
 {
     st = FrameStage{};
     st.frame = &frame; st.inPose = inPose; st.weightMultiplier = weightMultiplier; st.bootstrap = bootstrap;
+    if (frame.mask_dev && !(frame.rgba_dev && frame.depth_dev)) throw std::runtime_error("processFrame: a device mask comes with a device-resident frame");
+    if (frame.mask_dev && dist.world > 1) throw std::runtime_error("processFrame: device masks are a single-GPU option (world == 1); pass the mask from the host");
     const size_t N = (size_t)cfg.width * cfg.height;
     if (ownsCtx) check(ctx, cf_join(ctx), "cf_join");  // a previous call that threw inside a forked region must not leave the context on a lane
     // upload (CoFusion.cpp:179-184); RGB -> RGBA like the GL_RGBA texture upload
+    st.maskIn = frame.mask_dev;
     if (frame.rgba_dev && frame.depth_dev) { curRgba = frame.rgba_dev; curDepth = frame.depth_dev; }
     else {
         // one memcpy into pinned staging, transfers only enqueued (no host wait), RGB -> RGBA on the device.  The staging set
@@ -1124,6 +1184,11 @@ void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float wei
         memcpy(sp + N * 4, frame.rgb, N * 3);
         check(ctx, cf_memcpy_h2d_async(ctx, depth_dev, sp, N * 4), "depth upload");
         check(ctx, cf_memcpy_h2d_async(ctx, rgb_dev, sp + N * 4, N * 3), "rgb upload");
+        if (frame.mask && hostMasksOnDevice) {
+            memcpy(sp + N * 7, frame.mask, N);
+            check(ctx, cf_memcpy_h2d_async(ctx, maskIn_dev, sp + N * 7, N), "mask upload");
+            st.maskIn = maskIn_dev;
+        }
         check(ctx, cf_mark(ctx, markBase + 2 + (int)sb), "cf_mark");
         check(ctx, cf_rgb_to_rgba(ctx, rgb_dev, cfg.width, cfg.height, rgba_dev), "rgb expand");
         uploads++;
@@ -1150,7 +1215,15 @@ void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float wei
     } else if (willTrack) {
         // the superpixels only depend on the colour image: SLIC runs on an auxiliary stream beside the (latency-bound)
         // tracking launches and is joined before the segmentation needs it
-        st.slicAside = cfg.enableMultipleModels && !frame.mask && useLanes;
+        st.slicAside = cfg.enableMultipleModels && !frame.mask && !st.maskIn && useLanes;
+        // a device-resident label mask: every input of its three kernels exists now, so lane 7 (free in this mode) is ordered after the
+        // stream HERE, before the tracking launches; frameSegment then enqueues the chain on it without a new dependency (the two
+        // sequential depth sums take ~1 ms at 640x480: beside the Gauss-Newton launches, not behind them)
+        st.masksAside = cfg.enableMultipleModels && st.maskIn && useLanes;
+        if (st.masksAside) {
+            check(ctx, cf_fork(ctx, 7), "cf_fork");
+            check(ctx, cf_main(ctx), "cf_main");
+        }
         if (st.slicAside) {
             check(ctx, cf_fork(ctx, 7), "cf_fork");
             labelGenerator->startSlic(curRgba);
@@ -1159,7 +1232,7 @@ void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float wei
     }
 }
 
-void CoFusion::frameSegment(std::vector<cf_seg_job>* jobs)
+void CoFusion::frameSegment(std::vector<cf_seg_job>* jobs, std::vector<cf_seg_mask_job>* maskJobs)
 {
     const FrameData& frame = *st.frame;
     const Mat4f* inPose = st.inPose;
@@ -1171,7 +1244,8 @@ void CoFusion::frameSegment(std::vector<cf_seg_job>* jobs)
         // a new label needs a free model slot: the context (trackers' staging, the segmenter's label dimension) was sized for
         // cfg.maxModels models, at most 255 -- model ids are 8 bits and 255 marks a rejected superpixel (CoFusion.cpp:631-634)
         bool allowNew = false;
-        const bool segOnDevice = cfg.enableMultipleModels && !frame.mask;
+        const bool masksOnDevice = cfg.enableMultipleModels && st.maskIn;
+        const bool segOnDevice = cfg.enableMultipleModels && !frame.mask && !masksOnDevice;
         if (cfg.enableMultipleModels) {
             if (spawnOffset < cfg.modelSpawnOffset) spawnOffset++;
             const size_t modelCap = (size_t)std::min(cfg.maxModels, 255);
@@ -1188,7 +1262,17 @@ void CoFusion::frameSegment(std::vector<cf_seg_job>* jobs)
             jobs->emplace_back();
             labelGenerator->collectCRF(models, curDepth, curRgba, getNextModelID(), allowNew, mask_dev, jobs->back());
         } else if (segOnDevice) labelGenerator->enqueueCRF(models, curDepth, curRgba, getNextModelID(), allowNew, mask_dev);
-        st.allowNew = allowNew; st.segOnDevice = segOnDevice;
+        // the label-mask branch: its chain goes to the lane frameBegin ordered after the frame's inputs (cf_fork_after(.., -1): no new
+        // dependency, so it runs beside the tracking launches queued above) and is joined before the frame's host wait
+        if (masksOnDevice && maskJobs) {
+            maskJobs->emplace_back();
+            labelGenerator->collectMasks(models, st.maskIn, curDepth, getNextModelID(), allowNew, mask_dev, maskJobs->back());
+        } else if (masksOnDevice) {
+            if (st.masksAside) check(ctx, cf_fork_after(ctx, 7, -1), "cf_fork_after");
+            labelGenerator->enqueueMasks(models, st.maskIn, curDepth, getNextModelID(), allowNew, mask_dev);
+            if (st.masksAside) check(ctx, cf_join_lane(ctx, 7), "cf_join_lane");
+        }
+        st.allowNew = allowNew; st.segOnDevice = segOnDevice; st.masksOnDevice = masksOnDevice;
     }
 }
 
@@ -1232,6 +1316,7 @@ void CoFusion::frameCollect()
             auto getMaxDepth = [](const SegmentationResult::ModelData& d) -> float { return d.depthMean + d.depthStd * 1.2; };
             SegmentationResult seg;
             if (segOnDevice) seg = labelGenerator->finishCRF();
+            else if (st.masksOnDevice) seg = labelGenerator->finishMasks();
             else {
                 // the colour features of the CRF read the first K pixels of the full-resolution image
                 const int K = (cfg.width / 16) * (cfg.height / 16);
@@ -1339,7 +1424,7 @@ bool CoFusion::processFrame(const FrameData& frame, const Mat4f* inPose, float w
     const int frameTick = tick;   // (the number of this frame's Segmentation<n>.png)
     frameBegin(frame, inPose, weightMultiplier, bootstrap);
     if (st.willTrack) { PhaseTimer t(PhaseTimes::Track); trackModels(st.pyr); }
-    frameSegment(nullptr);
+    frameSegment(nullptr, nullptr);
     framePreIndex();
     frameCollect();
     frameFuse(true, 0);
@@ -1468,12 +1553,18 @@ void CoFusionGroup::stepAll(const FrameData* frames, const Mat4f* const* inPoses
     // and the decisions of all sequences
     {
         std::vector<cf_seg_job> jobs;
+        std::vector<cf_seg_mask_job> maskJobs;   // the sequences that came with a device mask: ONE chain of three launches for all of them
         std::vector<int> owner;   // the sequence every job belongs to
-        jobs.reserve((size_t)S);
+        jobs.reserve((size_t)S); maskJobs.reserve((size_t)S);
         for (int s = 0; s < S; s++) {
             const size_t before = jobs.size();
-            seqs[s]->frameSegment(&jobs);
+            seqs[s]->frameSegment(&jobs, &maskJobs);
             if (jobs.size() > before) owner.push_back(s);
+        }
+        if (!maskJobs.empty()) {   // on the lane the sequences' frameBegin ordered after their inputs: beside the tracking launches
+            check(ctx, cf_fork_after(ctx, 7, -1), "cf_fork_after");
+            Segmentation::runMaskBatch(ctx, maskJobs);
+            check(ctx, cf_join_lane(ctx, 7), "cf_join_lane");
         }
         // cf_seg_run_batch takes ONE parameter set per chain: sequences whose CRF settings differ (cofusion_set_crf on a borrowed handle)
         // get chains of their own, so that every sequence still equals a separate instance bit for bit

@@ -35,6 +35,8 @@ struct FrameData {
     // optional: the same frame already resident in HBM (depth f32, rgba u8x4); skips the upload
     const float* depth_dev = nullptr;
     const uint8_t* rgba_dev = nullptr;
+    // optional, with a device-resident frame: its label mask in HBM (u8, 16-byte aligned): the mask branch of the segmentation as kernels
+    const uint8_t* mask_dev = nullptr;
 };
 
 struct SegmentationResult {
@@ -195,6 +197,16 @@ class Segmentation {
     void collectCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev, unsigned char nextModelID, bool allowNew,
                     uint8_t* fullSegmentation_dev, cf_seg_job& job);
     static void runBatch(cf_ctx* ctx, const Segmentation& params, const std::vector<cf_seg_job>& jobs);
+    // The label-mask branch (performSegmentationGT) on the device, the same trio: enqueueMasks enqueues the three kernels of
+    // cf_seg_masks (label image into fullSegmentation_dev) on the context's current stream, collectMasks only describes them as a job
+    // for the group's one chain (runMaskBatch), finishMasks collects the rows after the frame's host wait and enters the mask value that
+    // spawned a label into gtMapping.  depth_dev is the frame's RAW depth.
+    void enqueueMasks(ModelList& models, const uint8_t* mask_in_dev, const float* depth_dev, unsigned char nextModelID, bool allowNew,
+                      uint8_t* fullSegmentation_dev);
+    void collectMasks(ModelList& models, const uint8_t* mask_in_dev, const float* depth_dev, unsigned char nextModelID, bool allowNew,
+                      uint8_t* fullSegmentation_dev, cf_seg_mask_job& job);
+    static void runMaskBatch(cf_ctx* ctx, const std::vector<cf_seg_mask_job>& jobs);
+    SegmentationResult finishMasks();
     // model-parallel operation: enqueueCRF put every owner's tracked pose behind the sums it all-reduces; after the frame's host wait
     // this hands out [models][18] words (pose row-major, ICP error, ICP inlier count as f32 bit patterns).  false: nothing was published
     bool fetchPublishedPoses(size_t nModels, std::vector<int64_t>& words);
@@ -216,7 +228,8 @@ class Segmentation {
     uint8_t gtMapping[256];
     const Distributed* dist = nullptr;
     bool slicStarted = false;
-    int pendingModels = 0;        // models of the segmentation enqueueCRF left in flight
+    int pendingModels = 0;        // models of the segmentation enqueueCRF / enqueueMasks left in flight
+    unsigned char pendingNextId = 0;  // the id a new label of the mask job in flight would get
     bool posesPublished = false;  // ... which carries the owners' poses in its all-reduce
     float* zeroImage = nullptr;   // device zeros [H*W*4] standing in for the ICP error / confidence maps of shadow models
     std::vector<const float*> jobIcp, jobConf;  // collectCRF's arrays
@@ -340,7 +353,7 @@ class CoFusion {
     void trackCollect(TrackBatch& batch) { trackCollect(batch, st.pyr); }
     static void trackLaunch(cf_ctx* ctx, TrackBatch& batch, const Config& cfg);
     // segmentation enqueued (jobs != nullptr: described as a job for the group's shared launches instead -- Segmentation::runBatch)
-    void frameSegment(std::vector<cf_seg_job>* jobs);
+    void frameSegment(std::vector<cf_seg_job>* jobs, std::vector<cf_seg_mask_job>* maskJobs);
     void framePreIndex();
     void frameCollect();           // the frame's host wait (poses + segmentation decisions), model bookkeeping
     void frameFuse(bool join, int laneOffset);
@@ -356,6 +369,8 @@ class CoFusion {
     struct FrameStage {   // what the stages of one frame hand to each other
         const FrameData* frame = nullptr; const Mat4f* inPose = nullptr; float weightMultiplier = 1.f; bool bootstrap = false;
         unsigned b = 0; bool willTrack = false, slicAside = false, fuseNow = false, allowNew = false, segOnDevice = false;
+        bool masksAside = false, masksOnDevice = false;   // the mask chain: lane 7 forked at frameBegin; enqueued by frameSegment
+        const uint8_t* maskIn = nullptr;                  // the frame's label mask in device memory (given so, or uploaded from the host)
         const float* pyr[3] = {nullptr, nullptr, nullptr};
     } st;
     bool ownsCtx = true;
@@ -396,7 +411,9 @@ class CoFusion {
     float *depthFilteredBuf[2] = {nullptr, nullptr}, *depthPyr1Buf[2] = {nullptr, nullptr}, *depthPyr2Buf[2] = {nullptr, nullptr};
     unsigned frameParity = 0;
     uint8_t *rgba_dev = nullptr, *rgb_dev = nullptr, *mask_dev = nullptr;
-    uint8_t* stage[2] = {nullptr, nullptr};   // pinned staging of the host-input path (depth f32 | rgb u8x3)
+    uint8_t* stage[2] = {nullptr, nullptr};   // pinned staging of the host-input path (depth f32 | rgb u8x3 | mask u8)
+    uint8_t* maskIn_dev = nullptr;            // where a host label mask is uploaded to (hostMasksOnDevice)
+    bool hostMasksOnDevice = false;           // host masks take the mask kernels (world == 1) instead of the host loops
     unsigned uploads = 0;
     const float* curDepth = nullptr;   // device pointers of the frame being processed
     const uint8_t* curRgba = nullptr;

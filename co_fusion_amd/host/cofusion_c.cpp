@@ -104,6 +104,14 @@ int cofusion_process_frame_device(cofusion_handle* h, int64_t ts, const float* d
     FrameData f; f.timestamp = ts; f.depth_dev = depth_dev; f.rgba_dev = rgba_dev;
     return run_frame(h, f, in_pose);
 }
+// ... with the frame's label mask in device memory as well: the mask branch of the segmentation runs as kernels (csrc/segment_masks.hip)
+int cofusion_process_frame_device_masked(cofusion_handle* h, int64_t ts, const float* depth_dev, const uint8_t* rgba_dev, const uint8_t* mask_dev,
+                                         const float* in_pose)
+{
+    if (h && mask_dev && h->cf->cfg.world > 1) { g_err = "device masks are a single-GPU option (world == 1): pass the mask from the host (cofusion_process_frame)"; return -1; }
+    FrameData f; f.timestamp = ts; f.depth_dev = depth_dev; f.rgba_dev = rgba_dev; f.mask_dev = mask_dev;
+    return run_frame(h, f, in_pose);
+}
 int cofusion_num_models(cofusion_handle* h) { return (int)h->cf->getModels().size(); }
 int cofusion_tick(cofusion_handle* h) { return h->cf->getTick(); }
 int cofusion_is_lost(cofusion_handle* h) { return h && h->cf->getLost() ? 1 : 0; }
@@ -240,6 +248,19 @@ int cofusion_group_process_frames_device(cofusion_group* g, const int64_t* ts, c
     if (!g || !rgba_dev || !depth_dev) { g_err = "null argument"; return -1; }
     std::vector<FrameData> f((size_t)g->g->size());
     for (size_t s = 0; s < f.size(); s++) { f[s].timestamp = ts ? ts[s] : 0; f[s].depth_dev = depth_dev[s]; f[s].rgba_dev = rgba_dev[s]; }
+    GUARD(g->g->processFrames(f.data()));
+    return 0;
+}
+
+int cofusion_group_process_frames_device_masked(cofusion_group* g, const int64_t* ts, const float* const* depth_dev, const uint8_t* const* rgba_dev,
+                                                const uint8_t* const* mask_dev)
+{
+    if (!g || !rgba_dev || !depth_dev) { g_err = "null argument"; return -1; }
+    std::vector<FrameData> f((size_t)g->g->size());
+    for (size_t s = 0; s < f.size(); s++) {
+        f[s].timestamp = ts ? ts[s] : 0; f[s].depth_dev = depth_dev[s]; f[s].rgba_dev = rgba_dev[s];
+        f[s].mask_dev = mask_dev ? mask_dev[s] : nullptr;   // (a null entry: that sequence runs the motion segmentation as before)
+    }
     GUARD(g->g->processFrames(f.data()));
     return 0;
 }

@@ -63,6 +63,13 @@ int cofusion_process_frame(cofusion_handle *h, int64_t timestamp, const uint8_t 
 /* same with the frame already resident in HBM (depth f32, rgba u8x4) */
 int cofusion_process_frame_device(cofusion_handle *h, int64_t timestamp, const float *depth_dev, const uint8_t *rgba_dev,
                                   const float *in_pose);
+/* ... and its label mask as well (u8 [H*W], one value per object, 0 = background; 16-byte aligned): the mask branch of the
+ * segmentation (the reference's pre-processed Mask#### input) runs as kernels beside the tracking, no pixel visits the host.  Results
+ * are those of cofusion_process_frame with the same mask, bit for bit.  mask_dev follows the frame's rule (device_frames_complete: it
+ * is complete at call time, or consumed in stream order).  mask_dev == NULL is cofusion_process_frame_device.  Refused for world > 1
+ * (pass the mask from the host there). */
+int cofusion_process_frame_device_masked(cofusion_handle *h, int64_t timestamp, const float *depth_dev, const uint8_t *rgba_dev,
+                                         const uint8_t *mask_dev, const float *in_pose);
 int cofusion_num_models(cofusion_handle *h);
 int cofusion_tick(cofusion_handle *h);
 /* CoFusion::getLost (CoFusion.h:183-185): 1 while the camera is lost (cofusion_config.reloc) */
@@ -118,6 +125,10 @@ int cofusion_group_process_frames(cofusion_group *g, const int64_t *timestamps, 
                                   const uint8_t *const *mask);
 int cofusion_group_process_frames_device(cofusion_group *g, const int64_t *timestamps, const float *const *depth_dev,
                                          const uint8_t *const *rgba_dev);
+/* ... with device masks (see cofusion_process_frame_device_masked): mask_dev nullable, its entries nullable -- a sequence without a
+ * mask runs the motion segmentation as before.  The mask kernels of all masked sequences are ONE chain of three launches. */
+int cofusion_group_process_frames_device_masked(cofusion_group *g, const int64_t *timestamps, const float *const *depth_dev,
+                                                const uint8_t *const *rgba_dev, const uint8_t *const *mask_dev);
 
 /* Model-parallel mode (cfg.world > 1, one process per GPU, every rank fed the same frames): the object models are placed
  * round-robin on ranks 1.., the background on rank 0; every rank runs the same frame loop and keeps data-less shadows of

@@ -485,6 +485,35 @@ int cf_seg_publish_poses(cf_segmenter *s, int n_models, cf_odom *const *trackers
 int cf_seg_fetch_poses(cf_segmenter *s, int n_models, int64_t *words_host);
 /* device view of the SLIC labels, int32 [H*W] */
 int cf_seg_labels(cf_segmenter *s, void **dptr, uint64_t *bytes);
+/* The label-mask branch (Segmentation.cpp:59-119; the reference's "pre-processed segmentation" input, Mask####.png) as kernels: a mask
+ * with one value per object arrives with the frame (u8 [H*W], device memory), `mapping` binds mask values to model ids (0 = unmapped)
+ * and, when allow_new is set, the value of the raster-first pixel that is non-zero and unmapped becomes next_model_id -- at most one new
+ * label per frame; pixels of other unmapped values get label 0.  cf_seg_masks only ENQUEUES (three launches on the context's current
+ * stream, no host wait): the label image goes to full_dev, the decisions arrive through cf_seg_fetch -- has_new_label, n_models, the
+ * models' rows in list order and the new label's row last (superPixelCount = pixels / 256, at least 1 for the new label; avgConfidence
+ * 0.4; depthMean / depthStd: the sequential f32 sums of the RAW depth in raster order, bit for bit those of the reference's loops;
+ * boxes and depth_range zero).  cf_seg_new_mask_value (after that fetch; CF_ESTATE before it) gives the mask value that was bound to
+ * next_model_id, -1 when none was: the caller owns the mapping and enters it there.
+ * mask_dev, depth_dev and full_dev are 16-byte aligned; full_dev is not mask_dev; 1 <= n_models <= 255 (CF_EINVAL otherwise).
+ * cf_seg_masks_batch: the jobs of several segmenters of one context (the sequences of a lock-step group) in shared launches, the
+ * chain issued once per 8 jobs; per segmenter the results of the single call.
+ * cf_seg_create_masks: a segmenter that serves this branch ONLY (the other cf_seg_* calls return CF_EINVAL) and therefore has no
+ * superpixel grid: any image size the context accepts, not only multiples of 16. */
+typedef struct cf_seg_mask_job {
+    cf_segmenter *seg;
+    const uint8_t *mask_dev;            /* u8 [H*W] */
+    const float *depth_dev;             /* the frame's raw depth, f32 [H*W] */
+    int32_t n_models;
+    const uint32_t *model_ids;          /* in list order (host) */
+    uint32_t next_model_id;
+    int32_t allow_new;
+    const uint8_t *mapping;             /* [256] (host): mask value -> model id, 0 = unmapped; read before the call returns */
+    uint8_t *full_dev;                  /* out: u8 [H*W] label image */
+} cf_seg_mask_job;
+int cf_seg_create_masks(cf_ctx *ctx, cf_segmenter **out);
+int cf_seg_masks(const cf_seg_mask_job *job);
+int cf_seg_masks_batch(cf_ctx *ctx, const cf_seg_mask_job *jobs, int n_jobs);
+int cf_seg_new_mask_value(cf_segmenter *s, int *value);
 
 /* data path between the RGB residual pass and the RGB step inside the device-resident Gauss-Newton loop.  1 (default): the
  * residual pass packs the valid correspondences of each workgroup into 8 B records, RGB step and 6x6 solve are launches of their
