@@ -67,6 +67,11 @@ struct cf_segmenter {
     long long* h_pose_tail = nullptr;    // pinned [Lcap][kPoseWords]: the tail of the sums block after the caller's all-reduce
     bool poses_published = false;
     bool grid_kernel_built = false;      // K1t holds the kernel of the grid's own smoothness features (seg_feat1_kernel)
+    // cf_seg_early: 0 nothing pending, 1 the early half is enqueued, 2 cf_seg_sums put the ICP sums behind it -- and what it ran with
+    int early = 0, early_n = 0;
+    const float* early_depth = nullptr; const uint8_t* early_rgba = nullptr;
+    std::vector<const float*> early_vconf;
+    float early_scale[3] = {0.f, 0.f, 0.f};
     // label-mask branch (segment_masks.hip; cf_seg_masks / cf_seg_masks_batch / cf_seg_new_mask_value)
     unsigned* mask_work = nullptr;       // [2][kMaskWork] first new pixel + histograms: job k works in block k & 1 and leaves the other one reset
     int* h_mask_new = nullptr;           // pinned [1]: the mask value bound to the new label (-1: none), stored by mask_stats_kernel

@@ -11,6 +11,16 @@
 //   * accumulation: same tiling; exact Q32 fixed-point sums (order independent).
 //   * CRF: the two 1200x1200 Gaussian kernels are evaluated exactly (no permutohedral lattice), stored
 //     transposed so that the sequential-in-j mean-field sums read coalesced rows.
+//
+// The device-resident chain (cf_seg_sums + cf_seg_infer) is seg_accumulate -> seg_unary -> crf_rownorm + crf_kernel_matrix (+ first
+// marginals) -> iterations x (crf_message, crf_update) -> seg_post -> seg_upsample, one stream, behind the frame's tracking.  Of its inputs
+// only the models' ICP error surfaces come from the tracker; the frame's depth and colour, the SLIC labels and the models' confidence
+// projections (the previous frame's prediction) exist when the frame starts.  cf_seg_early therefore runs, beside the tracking launches,
+//   seg_accumulate<kAccFrame | kAccConf> -> seg_unary<kUnaryFrame> -> crf_rownorm + crf_kernel_matrix
+// and leaves behind the tracker
+//   seg_accumulate<kAccIcp> -> seg_unary<kUnaryTrack> (+ first marginals) -> iterations x (crf_message, crf_update) -> seg_post -> seg_upsample
+// Both halves are flavours of the SAME kernel texts (compile-time masks), all sums are exact integers or keep their sequential order: the
+// split chain's results are the plain chain's bit for bit (tests/test_segment_early_gpu.py; DESIGN-NOTES R7).
 #include <string.h>
 
 #include <string>
@@ -120,8 +130,15 @@ struct AccArgs {
     unsigned long long* conf_sum;    // [n][K]
 };
 
+// PARTS selects the sums of a launch.  Only the ICP error surfaces wait for the frame's tracking; the frame's own sums (pixel and depth
+// counts, depth sums, resample labels) and the models' confidence sums read what exists at the start of the frame (the confidences are
+// the PREVIOUS frame's prediction), so cf_seg_early takes kAccFrame | kAccConf beside the tracking launches and the launch behind the
+// tracker is left with the slot search and one atomic per model.  kAccAll is the single launch of the plain chain; the three share one text.
+constexpr int kAccFrame = 1, kAccConf = 2, kAccIcp = 4, kAccAll = 7;
+template <int PARTS>
 __global__ void __launch_bounds__(256) seg_accumulate_kernel(const SegBatch<AccArgs> B)
 {
+    constexpr bool kFrame = (PARTS & kAccFrame) != 0, kConf = (PARTS & kAccConf) != 0, kIcp = (PARTS & kAccIcp) != 0;
     const AccArgs& a = B.m[blockIdx.z];
     __shared__ int s_lab[9];
     __shared__ unsigned s_cnt[9], s_dcnt[9];
@@ -130,7 +147,7 @@ __global__ void __launch_bounds__(256) seg_accumulate_kernel(const SegBatch<AccA
     const int cx0 = blockIdx.x, cy0 = blockIdx.y, t = threadIdx.x;
     if (cy0 == a.gy) {  // the extra grid row: labels at the "empty superpixel" resample coordinates (Slic.h:192-206; index / spixelY is the reference's)
         const int k = cx0 * 256 + t;
-        if (k >= a.gx * a.gy) return;
+        if (!kFrame || k >= a.gx * a.gy) return;   // (a launch without the frame's part has no such row)
         int x = (int)((k % a.gx) * kSpix + kSpix * 0.5), y = (int)((k / a.gy) * kSpix + kSpix * 0.5);
         if (y >= a.rows) y = a.rows - 1;
         if (x >= a.cols) x = a.cols - 1;
@@ -141,9 +158,9 @@ __global__ void __launch_bounds__(256) seg_accumulate_kernel(const SegBatch<AccA
     if (t < 9) {
         const int dx = t % 3 - 1, dy = t / 3 - 1, cx = cx0 + dx, cy = cy0 + dy;
         s_lab[t] = (cx < 0 || cy < 0 || cx >= a.gx || cy >= a.gy) ? -1 : cy * a.gx + cx;
-        s_cnt[t] = 0; s_dcnt[t] = 0; s_dsum[t] = 0;
+        if (kFrame) { s_cnt[t] = 0; s_dcnt[t] = 0; s_dsum[t] = 0; }
     }
-    for (int k = t; k < kAccTile * 9; k += 256) { s_icp[k / 9][k % 9] = 0; s_conf[k / 9][k % 9] = 0; }
+    for (int k = t; k < kAccTile * 9; k += 256) { if (kIcp) s_icp[k / 9][k % 9] = 0; if (kConf) s_conf[k / 9][k % 9] = 0; }
     __syncthreads();
     const int x = cx0 * kSpix + (t & 15), y = cy0 * kSpix + (t >> 4);
     const int q = y * a.cols + x;
@@ -151,34 +168,40 @@ __global__ void __launch_bounds__(256) seg_accumulate_kernel(const SegBatch<AccA
     int slot = 4;
 #pragma unroll
     for (int n = 0; n < 9; n++) if (s_lab[n] == lab) slot = n;
-    atomicAdd(&s_cnt[slot], 1u);
-    const float d = a.depth[q];
-    if (d > 0.02f) { atomicAdd(&s_dcnt[slot], 1u); atomicAdd(&s_dsum[slot], (unsigned long long)q32(d)); }
+    if (kFrame) {
+        atomicAdd(&s_cnt[slot], 1u);
+        const float d = a.depth[q];
+        if (d > 0.02f) { atomicAdd(&s_dcnt[slot], 1u); atomicAdd(&s_dsum[slot], (unsigned long long)q32(d)); }
+    }
     // the models in tiles of kAccTile (one pass for up to 16 models: what a frame normally has)
-    for (int m0 = 0; m0 < a.n_models; m0 += kAccTile) {
+    for (int m0 = 0; (kIcp || kConf) && m0 < a.n_models; m0 += kAccTile) {
         const int nm = min(kAccTile, a.n_models - m0);
         if (m0 > 0) {
             __syncthreads();
-            for (int k = t; k < kAccTile * 9; k += 256) { s_icp[k / 9][k % 9] = 0; s_conf[k / 9][k % 9] = 0; }
+            for (int k = t; k < kAccTile * 9; k += 256) { if (kIcp) s_icp[k / 9][k % 9] = 0; if (kConf) s_conf[k / 9][k % 9] = 0; }
             __syncthreads();
         }
         for (int m = 0; m < nm; m++) {
-            const float* icp = a.n_models <= kAccTile ? a.icp[m] : a.icp_dev[m0 + m];
-            const float4* vc = a.n_models <= kAccTile ? a.vconf[m] : a.vconf_dev[m0 + m];
-            atomicAdd(&s_icp[m][slot], (unsigned long long)q32(icp[q]));
-            atomicAdd(&s_conf[m][slot], (unsigned long long)q32(vc[q].w));
+            if (kIcp) {
+                const float* icp = a.n_models <= kAccTile ? a.icp[m] : a.icp_dev[m0 + m];
+                atomicAdd(&s_icp[m][slot], (unsigned long long)q32(icp[q]));
+            }
+            if (kConf) {
+                const float4* vc = a.n_models <= kAccTile ? a.vconf[m] : a.vconf_dev[m0 + m];
+                atomicAdd(&s_conf[m][slot], (unsigned long long)q32(vc[q].w));
+            }
         }
         __syncthreads();
         if (t < 9 && s_lab[t] >= 0) {
             const int L = s_lab[t];
             for (int m = 0; m < nm; m++) {
-                if (s_icp[m][t]) atomicAdd(&a.icp_sum[(size_t)(m0 + m) * K + L], s_icp[m][t]);
-                if (s_conf[m][t]) atomicAdd(&a.conf_sum[(size_t)(m0 + m) * K + L], s_conf[m][t]);
+                if (kIcp && s_icp[m][t]) atomicAdd(&a.icp_sum[(size_t)(m0 + m) * K + L], s_icp[m][t]);
+                if (kConf && s_conf[m][t]) atomicAdd(&a.conf_sum[(size_t)(m0 + m) * K + L], s_conf[m][t]);
             }
         }
     }
     __syncthreads();
-    if (t < 9 && s_lab[t] >= 0) {
+    if (kFrame && t < 9 && s_lab[t] >= 0) {
         const int L = s_lab[t];
         if (s_cnt[t]) atomicAdd(&a.spix_count[L], s_cnt[t]);
         if (s_dcnt[t]) { atomicAdd(&a.depth_count[L], s_dcnt[t]); atomicAdd(&a.depth_sum[L], s_dsum[t]); }
@@ -442,6 +465,8 @@ struct SegUnaryArgs {
     const int* resample;
     const uchar4* rgba;              // the CRF colour features read the first K pixels of the full-resolution image (sic, :445-447)
     float* raw;                      // scratch [(1 + 2n)][K]
+    int* empties;                    // scratch [2][K] + [2]: the ordered lists of the depth-empty and the pixel-empty superpixels, their lengths
+    float* Q0;                       // [K][L]: the mean field's first marginals (kUnaryTrack alone)
     float* low;                      // [(1 + 2n)][K]: lowDepth, lowICP[m], lowConf[m]
     float* unary; float* feat2;      // [K][L], [K][6]
     float* avg_conf;                 // [n]
@@ -596,28 +621,42 @@ __device__ __forceinline__ int block_scan_inclusive(int v, int* s_wave, int* tot
 // order by the reference: an empty superpixel k reads entry `read`, which has ALREADY been divided when read < k and is still the
 // raw sum when read > k.  Non-empty entries do not depend on anything else (phase 1, parallel); the rare empty ones are replayed in
 // index order by one lane per array (phase 2) from a list built with an ordered scan.
+//
+// PHASES: what of this needs the frame's tracking is little -- the ICP-error rows (raw -> mean, their replay), the unaries and the first
+// marginals.  kUnaryFrame (cf_seg_early, beside the tracking launches) does everything else for the depth row and the confidence rows:
+// means, both lists, replay, depth range, the sequential average confidences, the appearance features; it zeroes the accumulators it
+// consumed and leaves spix_count, resample and the pixel-empty list for kUnaryTrack, which runs behind the tracker on the ICP rows, forms
+// the unaries from the stored depth range and the confidence rows (non-finite entries already zeroed) and writes the first marginals
+// (crf_init_node: the kernel matrices were built early, so no launch carries them).  The replay rule is per array -- each replay reads
+// its own array, spix_count and resample only -- so the split changes no bit.  kUnaryAll is the plain chain's kernel; one text for all.
+constexpr int kUnaryFrame = 1, kUnaryTrack = 2, kUnaryAll = 3;
+template <int PHASES>
 __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnaryArgs> B)
 {
+    constexpr bool kF = (PHASES & kUnaryFrame) != 0, kT = (PHASES & kUnaryTrack) != 0;
     const SegUnaryArgs a = B.m[blockIdx.x];  // (by value: the fields are loaded into scalar registers once, ahead of the phases)
     const int K = a.K, n = a.n_models, A = 1 + 2 * n, L = a.L;
+    // the arrays of this flavour: row r of `rows` is array row_array(r) of [depth | icp[n] | conf[n]]
+    const int rows = PHASES == kUnaryAll ? A : (kF ? 1 + n : n);
+    auto row_array = [n](int r) { return PHASES == kUnaryAll ? r : (kF ? (r == 0 ? 0 : r + n) : r + 1); };
     const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float s_min[16], s_max[16];
     __shared__ float s_range;
     __shared__ int s_scan[16];
     __shared__ int s_nempty[2];
-    int* empties = reinterpret_cast<int*>(a.raw + (size_t)A * K);  // scratch behind the raw sums: [2][K] (depth-empty, pixel-empty)
+    int* empties = a.empties;   // [2][K] (depth-empty, pixel-empty), then the two lengths
     GSTAMP(0, 0);
     // A: raw sums as f32, phase 1 of the normalisation
     // (eight entries per lane in flight -- sixteen, one round at five models, measured slower late in round 6: 9.6 against 7.2 us --: this workgroup is alone on the GPU, a loop of dependent round trips to HBM -- 13 of them at five
     // models -- was a third of the kernel)
-    for (int base = 0; base < A * K; base += 8 * T) {
+    for (int base = 0; base < rows * K; base += 8 * T) {
         unsigned long long sv[8]; int cv[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int idx = base + u * T + tid;
             sv[u] = 0; cv[u] = 0;
-            if (idx < A * K) {
-                const int arr = idx / K, k = idx - arr * K;
+            if (idx < rows * K) {
+                const int r = idx / K, k = idx - r * K, arr = row_array(r);
                 const unsigned long long* sums = arr == 0 ? a.depth_sum : (arr <= n ? a.icp_sum + (size_t)(arr - 1) * K : a.conf_sum + (size_t)(arr - 1 - n) * K);
                 sv[u] = sums[k];
                 cv[u] = (int)(arr == 0 ? a.depth_count[k] : a.spix_count[k]);
@@ -626,10 +665,11 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int idx = base + u * T + tid;
-            if (idx < A * K) {
+            if (idx < rows * K) {
+                const int r = idx / K, at = row_array(r) * K + (idx - r * K);
                 const float raw = (float)((double)(long long)sv[u] * 2.3283064365386963e-10 /* 2^-32 */);
-                a.raw[idx] = raw;
-                a.low[idx] = cv[u] != 0 ? raw / (float)cv[u] : raw;
+                a.raw[at] = raw;
+                a.low[at] = cv[u] != 0 ? raw / (float)cv[u] : raw;
             }
         }
     }
@@ -637,7 +677,7 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
     // ordered lists of the empty superpixels (which == 0: no depth sample, which == 1: no pixel at all): both counts ride through ONE
     // scan, sixteen bits each (K <= 4800)
     const int per = (K + T - 1) / T;
-    {
+    if (kF) {
         int c0 = 0, c1 = 0;
         for (int k = tid * per; k < min(K, (tid + 1) * per); k++) { c0 += a.depth_count[k] == 0; c1 += a.spix_count[k] == 0; }
         int total = 0;
@@ -647,15 +687,22 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
             if (a.depth_count[k] == 0) empties[pos0++] = k;
             if (a.spix_count[k] == 0) empties[K + pos1++] = k;
         }
-        if (tid == 0) { s_nempty[0] = total & 0xffff; s_nempty[1] = total >> 16; }
+        if (tid == 0) {
+            s_nempty[0] = total & 0xffff; s_nempty[1] = total >> 16;
+            if (!kT) empties[2 * K + 1] = total >> 16;   // (the pixel-empty list outlives this launch)
+        }
+        __syncthreads();
+    } else {
+        if (tid == 0) { s_nempty[0] = 0; s_nempty[1] = empties[2 * K + 1]; }
         __syncthreads();
     }
     GSTAMP(0, 2);   // ordered lists
     // phase 2: empty superpixels in index order, one lane per array
-    if (tid < A) {
-        float* low = a.low + (size_t)tid * K;
-        const float* raw = a.raw + (size_t)tid * K;
-        const int which = tid == 0 ? 0 : 1, ne = s_nempty[which];
+    if (tid < rows) {
+        const int arr = row_array(tid);
+        float* low = a.low + (size_t)arr * K;
+        const float* raw = a.raw + (size_t)arr * K;
+        const int which = arr == 0 ? 0 : 1, ne = s_nempty[which];
         for (int e = 0; e < ne; e++) {
             const int k = empties[which * K + e];
             const int read = a.resample[k];
@@ -681,7 +728,7 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
         }
         if (lane == 0) a.avg_conf[m] = avg / (float)K;
     };
-    {
+    if (kF) {
         float mn = 3.402823466e+38f, mx = 0.f;
         if (beside && wave < n) average_confidence(wave);
         else {
@@ -708,11 +755,11 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
         }
     }
     GSTAMP(0, 4);   // depth range (+ the average confidences beside it)
-    if (!beside)
+    if (kF && !beside)
         for (int m = wave; m < n; m += nw) average_confidence(m);
     __syncthreads();
     GSTAMP(0, 5);   // average confidences
-    const float depthRange = s_range;
+    const float depthRange = kF ? s_range : a.depth_range[0];
     // unaries (:237-298, 458-460) and the appearance features (:441-450), one lane per superpixel -- and per lane TWO superpixels (k and
     // k + T: K = 1200 against 1024 lanes was two rounds) with every input of both in one flight of loads: the confidences and errors of
     // eight models at a time instead of one dependent round trip per model (8.8 -> 4.5 us, late in round 6).  The stores go to elements only
@@ -726,10 +773,12 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
             const int kk[2] = {k0, k0 + T};
             const bool ok[2] = {true, k0 + T < K};
             const int kc[2] = {k0, ok[1] ? k0 + T : k0};
-            uchar4 px[2]; float lowd[2], lowest[2] = {0.f, 0.f};
+            uchar4 px[2] = {}; float lowd[2] = {0.f, 0.f}, lowest[2] = {0.f, 0.f};
+            if (kF) {
 #pragma unroll
-            for (int r = 0; r < 2; r++) { px[r] = a.rgba[kc[r]]; lowd[r] = a.low[kc[r]]; }
-            for (int i0 = 0; i0 < nn; i0 += 8) {
+                for (int r = 0; r < 2; r++) { px[r] = a.rgba[kc[r]]; lowd[r] = a.low[kc[r]]; }
+            }
+            for (int i0 = 0; kT && i0 < nn; i0 += 8) {
                 float cf[8][2], ic[8][2];
 #pragma unroll
                 for (int u = 0; u < 8; u++)
@@ -764,24 +813,27 @@ __global__ void __launch_bounds__(1024) seg_unary_kernel(const SegBatch<SegUnary
             for (int r = 0; r < 2; r++)
                 if (ok[r]) {
                     const int k = kk[r];
-                    if (a.allow_new) {
+                    if (kT && a.allow_new) {
                         float un = fmaxf(a.unaryThresholdNew - a.unaryWeightError * lowest[r], 0.01f);
                         if (un <= 1e-5f) un = 1e-5f;
                         a.unary[(size_t)k * L + n] = un;
                     }
-                    const int i = k % a.gx, j = k / a.gx;
-                    float* f = a.feat2 + (size_t)k * 6;
-                    f[0] = (float)i * a.scaleFeaturesPos; f[1] = (float)j * a.scaleFeaturesPos;
-                    f[2] = (float)px[r].x * a.scaleFeaturesRGB; f[3] = (float)px[r].y * a.scaleFeaturesRGB; f[4] = (float)px[r].z * a.scaleFeaturesRGB;
-                    f[5] = fminf(lowd[r] * a.scaleFeaturesDepth, 100.0f);
+                    if (kF) {
+                        const int i = k % a.gx, j = k / a.gx;
+                        float* f = a.feat2 + (size_t)k * 6;
+                        f[0] = (float)i * a.scaleFeaturesPos; f[1] = (float)j * a.scaleFeaturesPos;
+                        f[2] = (float)px[r].x * a.scaleFeaturesRGB; f[3] = (float)px[r].y * a.scaleFeaturesRGB; f[4] = (float)px[r].z * a.scaleFeaturesRGB;
+                        f[5] = fminf(lowd[r] * a.scaleFeaturesDepth, 100.0f);
+                    }
+                    if (!kF) crf_init_node(a.unary, L, k, a.Q0);   // (the node's unaries are this lane's own stores)
                 }
         }
     }
     __syncthreads();
     GSTAMP(0, 6);   // unaries + features
     // leave the accumulators clean for the next frame
-    for (int k = tid; k < K; k += T) { a.spix_count[k] = 0; a.depth_count[k] = 0; a.depth_sum[k] = 0; }
-    for (int idx = tid; idx < n * K; idx += T) { a.icp_sum[idx] = 0; a.conf_sum[idx] = 0; }
+    for (int k = tid; k < K; k += T) { if (kT) a.spix_count[k] = 0; if (kF) { a.depth_count[k] = 0; a.depth_sum[k] = 0; } }
+    for (int idx = tid; idx < n * K; idx += T) { if (kT) a.icp_sum[idx] = 0; if (kF) a.conf_sum[idx] = 0; }
     GSTAMP(0, 7);
 }
 
@@ -1129,14 +1181,21 @@ static int seg_malloc(cf_ctx* ctx, T** p, size_t count)
 }
 
 // the models' image pointers of the accumulation launch: kernel arguments for up to kAccTile models, a device table beyond
+// (icp_err / vertconf4 may be NULL where the launch does not take that part: the table keeps what an earlier call put there)
 static int acc_pointers(cf_segmenter* s, AccArgs& a, int n_models, const float* const* icp_err, const float* const* vertconf4)
 {
     if (n_models <= kAccTile) {
-        for (int m = 0; m < n_models; m++) { a.icp[m] = icp_err[m]; a.vconf[m] = reinterpret_cast<const float4*>(vertconf4[m]); }
+        for (int m = 0; m < n_models; m++) {
+            if (icp_err) a.icp[m] = icp_err[m];
+            if (vertconf4) a.vconf[m] = reinterpret_cast<const float4*>(vertconf4[m]);
+        }
         return CF_OK;
     }
     cf_ctx* ctx = s->ctx;
-    for (int m = 0; m < n_models; m++) { s->h_acc_ptrs[m] = icp_err[m]; s->h_acc_ptrs[s->Lcap + m] = vertconf4[m]; }
+    for (int m = 0; m < n_models; m++) {
+        if (icp_err) s->h_acc_ptrs[m] = icp_err[m];
+        if (vertconf4) s->h_acc_ptrs[s->Lcap + m] = vertconf4[m];
+    }
     HIPCHK(ctx, hipMemcpyAsync(s->d_acc_ptrs, s->h_acc_ptrs, sizeof(void*) * 2 * (size_t)s->Lcap, hipMemcpyHostToDevice, ctx->stream));
     a.icp_dev = reinterpret_cast<const float* const*>(s->d_acc_ptrs);
     a.vconf_dev = reinterpret_cast<const float4* const*>(s->d_acc_ptrs + s->Lcap);
@@ -1182,7 +1241,7 @@ static int seg_create(cf_ctx* ctx, cf_segmenter** out, bool masks_only)
     if (int r = seg_malloc(ctx, &s->unary, K * Lc)) return r;
     if (int r = seg_malloc(ctx, &s->Q0, K * Lc)) return r;
     if (int r = seg_malloc(ctx, &s->Q1, K * Lc)) return r;
-    if (int r = seg_malloc(ctx, &s->raw_mean, K * (3 + 2 * Lc))) return r;  // raw sums + the two lists of empty superpixels
+    if (int r = seg_malloc(ctx, &s->raw_mean, K ? K * (3 + 2 * Lc) + 2 : (size_t)0)) return r;  // raw sums + the two lists of empty superpixels + their lengths
     if (int r = seg_malloc(ctx, &s->low_mean, K * (1 + 2 * Lc))) return r;
     if (int r = seg_malloc(ctx, &s->avg_conf, Lc)) return r;
     if (int r = seg_malloc(ctx, &s->depth_range, (size_t)1)) return r;
@@ -1252,6 +1311,7 @@ int cf_seg_accumulate(cf_segmenter* s, const float* depth, int n_models, const f
     if (!s || !s->K || !depth || n_models < 0 || n_models > s->Lcap) return CF_EINVAL;
     cf_ctx* ctx = s->ctx; hipStream_t st = ctx->stream;
     const size_t K = (size_t)s->K;
+    s->early = 0;   // (every accumulator is cleared below)
     HIPCHK(ctx, hipMemsetAsync(s->spix_count, 0, sizeof(unsigned) * K, st));
     HIPCHK(ctx, hipMemsetAsync(s->depth_count, 0, sizeof(unsigned) * K, st));
     HIPCHK(ctx, hipMemsetAsync(s->depth_sum, 0, sizeof(unsigned long long) * K, st));
@@ -1266,7 +1326,7 @@ int cf_seg_accumulate(cf_segmenter* s, const float* depth, int n_models, const f
         SegBatch<AccArgs> B;
         memset(&B, 0, sizeof(B));
         B.m[0] = a;
-        seg_accumulate_kernel<<<dim3(s->gx, s->gy, 1), 256, 0, st>>>(B);
+        seg_accumulate_kernel<kAccAll><<<dim3(s->gx, s->gy, 1), 256, 0, st>>>(B);
     }
     seg_resample_kernel<<<(s->K + 255) / 256, 256, 0, st>>>(s->labels, ctx->cfg.width, ctx->cfg.height, s->gx, s->gy, s->resample);
     LAUNCHCHK(ctx);
@@ -1350,14 +1410,26 @@ struct SegJob {
     cf_segmenter* s; const float* depth; int n_models; const float* const* icp_err; const float* const* vertconf4;
     const uint8_t* rgba; const uint32_t* model_ids; uint32_t next_model_id; int allow_new; uint8_t* full_dev;
 };
-// the sums of S <= kSegBatch segmenters of one image size in ONE launch (+ the resample labels in its extra grid row)
-static int enqueue_accumulate(cf_ctx* ctx, const SegJob* jobs, int S)
+// An early half (cf_seg_early) that no inference will finish: what it left for the late half goes, so that the accumulators are
+// clean again (the early unary kernel zeroed the ones it consumed)
+static int early_discard(cf_segmenter* s)
+{
+    const int was = s->early;
+    if (!was) return CF_OK;
+    s->early = 0;
+    HIPCHK(s->ctx, hipMemsetAsync(s->spix_count, 0, sizeof(unsigned) * (size_t)s->K, s->ctx->stream));
+    if (was >= 2) HIPCHK(s->ctx, hipMemsetAsync(s->icp_sum, 0, sizeof(unsigned long long) * (size_t)s->K * s->early_n, s->ctx->stream));
+    return CF_OK;
+}
+// the sums of S <= kSegBatch segmenters of one image size in ONE launch (+ the resample labels in its extra grid row); parts: kAcc*
+static int enqueue_accumulate(cf_ctx* ctx, const SegJob* jobs, int S, int parts = kAccAll)
 {
     hipStream_t st = ctx->stream;
     cf_segmenter* s0 = jobs[0].s;
     SegBatch<AccArgs> B;
     memset(&B, 0, sizeof(B));
-    const bool ride = s0->gy <= 256;  // (gx workgroups of 256 threads cover the K = gx * gy resample points)
+    const bool frame = (parts & kAccFrame) != 0;
+    const bool ride = frame && s0->gy <= 256;  // (gx workgroups of 256 threads cover the K = gx * gy resample points)
     for (int e = 0; e < S; e++) {
         cf_segmenter* s = jobs[e].s;
         AccArgs& a = B.m[e];
@@ -1366,8 +1438,12 @@ static int enqueue_accumulate(cf_ctx* ctx, const SegJob* jobs, int S)
         a.spix_count = s->spix_count; a.depth_count = s->depth_count; a.depth_sum = s->depth_sum; a.icp_sum = s->icp_sum; a.conf_sum = s->conf_sum;
         a.resample = ride ? s->resample : nullptr;
     }
-    seg_accumulate_kernel<<<dim3(s0->gx, s0->gy + (ride ? 1 : 0), S), 256, 0, st>>>(B);
-    if (!ride)
+    const dim3 grid(s0->gx, s0->gy + (ride ? 1 : 0), S);
+    if (parts == kAccAll) seg_accumulate_kernel<kAccAll><<<grid, 256, 0, st>>>(B);
+    else if (parts == (kAccFrame | kAccConf)) seg_accumulate_kernel<kAccFrame | kAccConf><<<grid, 256, 0, st>>>(B);
+    else if (parts == kAccIcp) seg_accumulate_kernel<kAccIcp><<<grid, 256, 0, st>>>(B);
+    else { ctx->set_error("segmentation: no accumulation kernel for these parts"); return CF_EINVAL; }
+    if (frame && !ride)
         for (int e = 0; e < S; e++)
             seg_resample_kernel<<<(jobs[e].s->K + 255) / 256, 256, 0, st>>>(jobs[e].s->labels, ctx->cfg.width, ctx->cfg.height, s0->gx, s0->gy, jobs[e].s->resample);
     LAUNCHCHK(ctx);
@@ -1384,7 +1460,17 @@ int cf_seg_sums(cf_segmenter* s, const float* depth, int n_models, const float* 
     if (!s || !s->K || !depth || n_models <= 0 || n_models > s->Lcap || !icp_err || !vertconf4) return CF_EINVAL;
     SegJob job{};
     job.s = s; job.depth = depth; job.n_models = n_models; job.icp_err = icp_err; job.vertconf4 = vertconf4;
-    if (int r = enqueue_accumulate(s->ctx, &job, 1)) return r;
+    // behind a matching cf_seg_early only the ICP-error sums are left (the block then holds those alone: the confidence sums were
+    // consumed beside the tracking); an early half that does not match is dropped and the whole launch runs
+    bool late = s->early == 1 && s->early_n == n_models && s->early_depth == depth;
+    for (int m = 0; late && m < n_models; m++) late = s->early_vconf[m] == vertconf4[m];
+    if (late) {
+        if (int r = enqueue_accumulate(s->ctx, &job, 1, kAccIcp)) return r;
+        s->early = 2;
+    } else {
+        if (int r = early_discard(s)) return r;
+        if (int r = enqueue_accumulate(s->ctx, &job, 1)) return r;
+    }
     if (sums_dev) *sums_dev = reinterpret_cast<int64_t*>(s->icp_sum);
     if (sums_words) *sums_words = 2ull * (uint64_t)s->Lcap * (uint64_t)s->K + (uint64_t)s->Lcap * kPoseWords;  // the pose tail rides along (zeros unless published)
     return CF_OK;
@@ -1419,8 +1505,29 @@ int cf_seg_fetch_poses(cf_segmenter* s, int n_models, int64_t* words_host)
 // Everything after the sums (Segmentation.cpp:160-706) for S <= kSegBatch segmenters of one image size in one chain of launches: unaries,
 // kernel matrices, mean-field steps, arg-max / connected components / gates / statistics, up-sampling into full_dev.  CAP: the capacity
 // of the id table in the post-processing arguments (17 for a batch, 257 for one segmenter with many labels).
+static void unary_args(SegUnaryArgs& u, cf_segmenter* s, const SegJob& job, const cf_seg_params* P)
+{
+    const int n_models = job.n_models, L = n_models + (job.allow_new ? 1 : 0);
+    u.K = s->K; u.gx = s->gx; u.gy = s->gy; u.n_models = n_models; u.L = L; u.allow_new = job.allow_new ? 1 : 0;
+    u.unaryWeightError = P->unaryWeightError; u.unaryKError = P->unaryKError; u.unaryThresholdNew = P->unaryThresholdNew;
+    u.scaleFeaturesRGB = P->scaleFeaturesRGB; u.scaleFeaturesDepth = P->scaleFeaturesDepth; u.scaleFeaturesPos = P->scaleFeaturesPos;
+    u.spix_count = s->spix_count; u.depth_count = s->depth_count; u.depth_sum = s->depth_sum; u.icp_sum = s->icp_sum; u.conf_sum = s->conf_sum;
+    u.resample = s->resample; u.rgba = reinterpret_cast<const uchar4*>(job.rgba);
+    u.raw = s->raw_mean; u.low = s->low_mean; u.unary = s->unary; u.feat2 = s->feat2; u.avg_conf = s->avg_conf; u.depth_range = s->depth_range;
+    u.empties = reinterpret_cast<int*>(s->raw_mean + (size_t)(1 + 2 * s->Lcap) * s->K);   // behind the rows of every model count
+    u.Q0 = s->Q0;
+}
+// the smoothness kernel only depends on the superpixel grid: built once per segmenter
+static void ensure_grid_kernel(cf_segmenter* s)
+{
+    if (s->grid_kernel_built) return;
+    build_grid_kernel(s, true);
+    s->grid_kernel_built = true;
+    s->smooth_cache.clear();
+}
+// `late`: the jobs' early halves ran (cf_seg_early) -- the unary kernel's kUnaryTrack flavour, and the appearance kernels exist
 template <int CAP, int N>
-static int enqueue_infer(cf_ctx* ctx, const cf_seg_params* P, const SegJob* jobs, int S)
+static int enqueue_infer(cf_ctx* ctx, const cf_seg_params* P, const SegJob* jobs, int S, bool late = false)
 {
     hipStream_t st = ctx->stream;
     const int n = jobs[0].s->K;
@@ -1431,26 +1538,15 @@ static int enqueue_infer(cf_ctx* ctx, const cf_seg_params* P, const SegJob* jobs
     memset(&U, 0, sizeof(U)); memset(&C, 0, sizeof(C)); memset(&PB, 0, sizeof(PB)); memset(&UP, 0, sizeof(UP));
     for (int e = 0; e < S; e++) {
         cf_segmenter* s = jobs[e].s;
-        const int n_models = jobs[e].n_models, L = n_models + (jobs[e].allow_new ? 1 : 0);
-        SegUnaryArgs& u = U.m[e];
-        u.K = n; u.gx = s->gx; u.gy = s->gy; u.n_models = n_models; u.L = L; u.allow_new = jobs[e].allow_new ? 1 : 0;
-        u.unaryWeightError = P->unaryWeightError; u.unaryKError = P->unaryKError; u.unaryThresholdNew = P->unaryThresholdNew;
-        u.scaleFeaturesRGB = P->scaleFeaturesRGB; u.scaleFeaturesDepth = P->scaleFeaturesDepth; u.scaleFeaturesPos = P->scaleFeaturesPos;
-        u.spix_count = s->spix_count; u.depth_count = s->depth_count; u.depth_sum = s->depth_sum; u.icp_sum = s->icp_sum; u.conf_sum = s->conf_sum;
-        u.resample = s->resample; u.rgba = reinterpret_cast<const uchar4*>(jobs[e].rgba);
-        u.raw = s->raw_mean; u.low = s->low_mean; u.unary = s->unary; u.feat2 = s->feat2; u.avg_conf = s->avg_conf; u.depth_range = s->depth_range;
-        C.m[e] = crf_seq(s, L);
+        unary_args(U.m[e], s, jobs[e], P);
+        C.m[e] = crf_seq(s, U.m[e].L);
     }
-    seg_unary_kernel<<<S, 1024, 0, st>>>(U);
-    for (int e = 0; e < S; e++) {
-        cf_segmenter* s = jobs[e].s;
-        if (!s->grid_kernel_built) {  // the smoothness kernel only depends on the superpixel grid: built once per segmenter
-            build_grid_kernel(s, true);
-            s->grid_kernel_built = true;
-            s->smooth_cache.clear();
-        }
+    if (late) seg_unary_kernel<kUnaryTrack><<<S, 1024, 0, st>>>(U);   // (+ the first marginals)
+    else {
+        seg_unary_kernel<kUnaryAll><<<S, 1024, 0, st>>>(U);
+        for (int e = 0; e < S; e++) ensure_grid_kernel(jobs[e].s);
+        launch_crf_kernel_matrix<6>(st, C, S, n, true);
     }
-    launch_crf_kernel_matrix<6>(st, C, S, n, true);
     const int flip = launch_mean_field(st, C, S, n, P->crfIterations, P->weightSmoothness, P->weightAppearance);
     for (int e = 0; e < S; e++) {
         cf_segmenter* s = jobs[e].s;
@@ -1509,8 +1605,53 @@ int cf_seg_infer(cf_segmenter* s, const cf_seg_params* P, const uint8_t* rgba, i
     if (L > s->Lcap) { s->ctx->set_error("segmentation: more labels than the context's max_models (" + std::to_string(s->Lcap) + ")"); return CF_EINVAL; }
     SegJob job{};
     job.s = s; job.n_models = n_models; job.rgba = rgba; job.model_ids = model_ids; job.next_model_id = next_model_id; job.allow_new = allow_new; job.full_dev = full_dev;
-    if (L <= 16) return enqueue_infer<17, kSegBatch>(s->ctx, P, &job, 1);
-    return enqueue_infer<kMaxL + 1, 1>(s->ctx, P, &job, 1);
+    // the late half, when the early half ran with what this call would have given it; otherwise the whole chain
+    bool late = false;
+    if (s->early == 2) {
+        late = s->early_n == n_models && s->early_rgba == rgba && s->early_scale[0] == P->scaleFeaturesRGB && s->early_scale[1] == P->scaleFeaturesDepth &&
+               s->early_scale[2] == P->scaleFeaturesPos;
+        if (!late) {
+            // the ICP sums are in place; the frame's and the confidences' (consumed early) are formed again from the recorded images
+            if (s->early_n != n_models) { s->ctx->set_error("cf_seg_infer: n_models differs from cf_seg_sums'"); return CF_EINVAL; }
+            HIPCHK(s->ctx, hipMemsetAsync(s->spix_count, 0, sizeof(unsigned) * (size_t)s->K, s->ctx->stream));
+            SegJob again{};
+            again.s = s; again.depth = s->early_depth; again.n_models = n_models; again.vertconf4 = s->early_vconf.data();
+            if (int r = enqueue_accumulate(s->ctx, &again, 1, kAccFrame | kAccConf)) return r;
+        }
+        s->early = 0;
+    } else if (int r = early_discard(s)) return r;
+    if (L <= 16) return enqueue_infer<17, kSegBatch>(s->ctx, P, &job, 1, late);
+    return enqueue_infer<kMaxL + 1, 1>(s->ctx, P, &job, 1, late);
+}
+
+// The half of cf_seg_sums + cf_seg_infer that does not need the frame's tracking, for a caller that has another stream to put it on
+// beside the tracking launches (behind cf_seg_slic): the frame's and the confidences' sums, their means / replay / depth range /
+// average confidences / appearance features (seg_unary_kernel<kUnaryFrame>) and the appearance kernel matrix.  vertconf4[m] must hold
+// what cf_seg_sums will be given (the previous frame's prediction), rgba and the three scaleFeatures* what cf_seg_infer will be given:
+// the segmenter remembers them, and calls that match enqueue the late half only; calls that do not match fall back to the whole chain.
+// An early half nobody finishes is dropped by the next cf_seg_early / cf_seg_sums / cf_seg_accumulate / cf_seg_run_batch.
+int cf_seg_early(cf_segmenter* s, const float* depth, const uint8_t* rgba, int n_models, const float* const* vertconf4, const cf_seg_params* P)
+{
+    if (!s || !s->K || !depth || !rgba || !P || n_models <= 0 || n_models > s->Lcap || !vertconf4) return CF_EINVAL;
+    cf_ctx* ctx = s->ctx;
+    if (int r = early_discard(s)) return r;
+    SegJob job{};
+    job.s = s; job.depth = depth; job.n_models = n_models; job.vertconf4 = vertconf4; job.rgba = rgba;
+    if (int r = enqueue_accumulate(ctx, &job, 1, kAccFrame | kAccConf)) return r;
+    SegBatch<SegUnaryArgs> U;
+    memset(&U, 0, sizeof(U));
+    unary_args(U.m[0], s, job, P);
+    seg_unary_kernel<kUnaryFrame><<<1, 1024, 0, ctx->stream>>>(U);
+    ensure_grid_kernel(s);
+    CrfBatch C;
+    memset(&C, 0, sizeof(C));
+    C.m[0] = crf_seq(s, 0);
+    launch_crf_kernel_matrix<6>(ctx->stream, C, 1, s->K, false);
+    LAUNCHCHK(ctx);
+    s->early = 1; s->early_n = n_models; s->early_depth = depth; s->early_rgba = rgba;
+    s->early_vconf.assign(vertconf4, vertconf4 + n_models);
+    s->early_scale[0] = P->scaleFeaturesRGB; s->early_scale[1] = P->scaleFeaturesDepth; s->early_scale[2] = P->scaleFeaturesPos;
+    return CF_OK;
 }
 
 // cf_seg_sums + cf_seg_infer of several segmenters of ONE context (the sequences of a lock-step group) through shared launches: the
@@ -1530,6 +1671,7 @@ int cf_seg_run_batch(cf_ctx* ctx, const cf_seg_params* P, const cf_seg_job* jobs
         for (int k = 0; k < e; k++) if (jobs_in[k].seg == j.seg) return CF_EINVAL;
         batchable = batchable && L <= 16 && j.seg->K == jobs_in[0].seg->K && j.seg->gx == jobs_in[0].seg->gx;
         jobs[e] = SegJob{j.seg, j.depth, j.n_models, j.icp_err, j.vertconf4, j.rgba, j.model_ids, j.next_model_id, j.allow_new, j.full_dev};
+        if (int r = early_discard(j.seg)) return r;   // (the batched chain is the whole chain)
     }
     if (!batchable) {  // (a sequence with more than 16 labels: one chain per segmenter)
         for (int e = 0; e < n_jobs; e++) {

@@ -277,6 +277,10 @@ class CoFusion:
                                               f(weight_smoothness), f(sigma_rgb), f(sigma_depth), f(sigma_pos), f(min_rel_size_new),
                                               f(max_rel_size_new), C.c_uint(iterations)))
 
+    def set_seg_early(self, on=True):
+        """The motion segmentation's tracking-independent half beside the tracking launches (default on); the results do not depend on it."""
+        self._check(self.lib.cofusion_set_seg_early(self.h, 1 if on else 0))
+
     def process_frame(self, depth, rgb, mask=None, in_pose=None, timestamp=0):
         """Host numpy inputs: depth f32 [H,W] metres, rgb u8 [H,W,3], optional GT mask u8 [H,W]."""
         d = np.ascontiguousarray(depth, np.float32); c = np.ascontiguousarray(rgb, np.uint8)

@@ -285,6 +285,14 @@ void Segmentation::startSlic(const uint8_t* rgba_dev)
     check(ctx, cf_seg_slic(seg, rgba_dev), "cf_seg_slic");
     slicStarted = true;
 }
+void Segmentation::startEarly(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev)
+{
+    if (dist && dist->active()) throw std::runtime_error("Segmentation::startEarly: the early half is for single-process sequences");
+    std::vector<const float*> vcPtr;
+    for (auto& mdl : models) vcPtr.push_back(mdl->vertexConfProjection());
+    const cf_seg_params P = deviceParams();
+    check(ctx, cf_seg_early(seg, depth_dev, rgba_dev, (int)vcPtr.size(), vcPtr.data(), &P), "cf_seg_early");
+}
 Segmentation::~Segmentation()
 {
     if (zeroImage) cf_free(ctx, zeroImage);
@@ -1227,6 +1235,11 @@ void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float wei
         if (st.slicAside) {
             check(ctx, cf_fork(ctx, 7), "cf_fork");
             labelGenerator->startSlic(curRgba);
+            // ... and with them the half of the CRF chain that reads the frame and the previous prediction only.  Nothing enqueued up to
+            // frameSegment's cf_join_lane(7) writes curDepth, curRgba or a model's confidence projection (the tracking launches read them;
+            // fill-in and the prediction belong to the previous frame's end, ahead of this fork), and the model list changes in
+            // frameCollect at the earliest.  A sequence of a lock-step group keeps the whole chain for the group's batched launches.
+            if (segEarly && ownsCtx && !dist.active()) labelGenerator->startEarly(models, curDepth, curRgba);
             check(ctx, cf_main(ctx), "cf_main");
         }
     }

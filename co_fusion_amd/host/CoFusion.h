@@ -186,6 +186,11 @@ class Segmentation {
                                            uint8_t* fullSegmentation_dev);
     // enqueue SLIC for this frame's image ahead of performSegmentation (on whatever stream the context currently uses)
     void startSlic(const uint8_t* rgba_dev);
+    // ... and, behind it, everything else of the device-resident CRF chain that does not need this frame's tracking (cf_seg_early: the
+    // frame's and the confidences' sums, means, depth range, average confidences, appearance features and kernel matrix).  The models'
+    // confidence projections are the previous frame's prediction; enqueueCRF then finds the segmenter prepared and enqueues the rest.
+    // Single-process sequences only (the confidence sums are consumed here: no collective could add the other ranks' to them).
+    void startEarly(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev);
     // performSegmentationCRF in two halves without a host wait in between: everything is enqueued (sums, unaries, mean field,
     // component analysis, up-sampling into fullSegmentation_dev), the decisions are collected later
     void enqueueCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev, unsigned char nextModelID, bool allowNew,
@@ -335,6 +340,9 @@ class CoFusion {
                            uint64_t seed = 0, int capacity = 1024);
     void relocStats(int* keyframes, int* lastClosest, int* recoveries, int* databaseFull);
     bool isGroupSequence() const { return !ownsCtx; }
+    // The motion-CRF chain's tracking-independent half beside the tracking launches (Segmentation::startEarly).  On by default; off
+    // leaves the whole chain behind the tracker -- the same results bit for bit, for A/B measurements and parity tests.
+    void setSegEarly(bool on) { segEarly = on; }
     const uint8_t* maskDevice() const { return mask_dev; }
     Segmentation& segmentation() { return *labelGenerator; }
     cf_ctx* context() { return ctx; }
@@ -374,6 +382,7 @@ class CoFusion {
         const float* pyr[3] = {nullptr, nullptr, nullptr};
     } st;
     bool ownsCtx = true;
+    bool segEarly = true;
     int markBase = 0;   // this sequence's four event slots of the context (cf_mark)
     void trackCollect(TrackBatch& batch, const float* const depthPyr[3]);
     void spawnObjectModel();

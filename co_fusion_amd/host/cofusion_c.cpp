@@ -202,6 +202,12 @@ int cofusion_set_crf(cofusion_handle* h, float uwe, float uke, float thn, float 
     s.minRelSizeNew = minr; s.maxRelSizeNew = maxr; s.crfIterations = its;
     return 0;
 }
+int cofusion_set_seg_early(cofusion_handle* h, int on)
+{
+    if (!h) { g_err = "null argument"; return -1; }
+    h->cf->setSegEarly(on != 0);
+    return 0;
+}
 
 int cofusion_set_allreduce(cofusion_handle* h, cofusion_allreduce_i64_fn fn, void* user)
 {

@@ -107,6 +107,10 @@ void *cofusion_context(cofusion_handle *h);
 int cofusion_set_crf(cofusion_handle *h, float unary_weight_error, float unary_k_error, float threshold_new, float weight_appearance,
                      float weight_smoothness, float sigma_rgb, float sigma_depth, float sigma_pos, float min_rel_size_new,
                      float max_rel_size_new, unsigned iterations);
+/* The motion segmentation's tracking-independent half (superpixel sums of the frame and of the models' confidences, their statistics,
+ * the appearance kernel) runs beside the tracking launches: on (default) / off.  The results are the same bit for bit; off is the
+ * whole chain behind the tracker, for A/B measurements.  Sequences of a lock-step group and model-parallel runs always use the latter. */
+int cofusion_set_seg_early(cofusion_handle *h, int on);
 
 /* Several independent RGB-D sequences on ONE GPU in lock-step (throughput mode): the sequences share one context, and every set of
  * tracking launches (map preparation, SO(3) pre-alignment, the Gauss-Newton loop) carries the trackers of all of them, up to 16 per

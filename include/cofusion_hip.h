@@ -458,6 +458,16 @@ int cf_seg_sums(cf_segmenter *s, const float *depth, int n_models, const float *
 int cf_seg_infer(cf_segmenter *s, const cf_seg_params *params, const uint8_t *rgba, int n_models, const uint32_t *model_ids,
                  uint32_t next_model_id, int allow_new, uint8_t *full_dev);
 int cf_seg_fetch(cf_segmenter *s, cf_seg_result *out, uint8_t *low_map_host);
+/* The half of cf_seg_sums + cf_seg_infer that does not need the frame's tracking: the frame's own sums and the models' confidence sums
+ * (vertconf4[m]: the previous frame's prediction), their means, the depth range, the average confidences, the appearance features and
+ * the appearance kernel matrix.  Only enqueues, on the context's current stream, behind cf_seg_slic -- for a caller that puts it on a
+ * lane beside the tracking launches.  The segmenter remembers depth, rgba, n_models, the vertconf4 pointers and params' three
+ * scaleFeatures*; a following cf_seg_sums + cf_seg_infer with the same values enqueue the rest only (ICP-error sums, unaries, first
+ * marginals, mean field, post-processing, up-sampling) -- the block cf_seg_sums hands out then holds the ICP-error sums alone, so no
+ * collective can be placed there.  Calls that do not match run the whole chain (the results are those of the plain chain either way,
+ * bit for bit); an early half that no inference follows is dropped by the segmenter's next cf_seg_early / cf_seg_sums. */
+int cf_seg_early(cf_segmenter *s, const float *depth, const uint8_t *rgba, int n_models, const float *const *vertconf4,
+                 const cf_seg_params *params);
 /* cf_seg_sums + cf_seg_infer of SEVERAL segmenters of one context -- the sequences of a lock-step group (the reference runs one
  * performSegmentation per CoFusion instance, Segmentation.cpp:124-706) -- through shared launches: the chain of ~30 small kernels is
  * issued once per 8 segmenters (all of one image size, <= 16 labels each; otherwise one chain per segmenter) instead of once per
