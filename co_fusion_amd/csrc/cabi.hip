@@ -14,17 +14,6 @@
 
 using namespace cf;
 
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-
-#define LAUNCHCHK(ctx) HIPCHK(ctx, hipGetLastError())
-
 void cf_ctx::set_error(const std::string& m)
 {
     std::lock_guard<std::mutex> lk(error_mutex);

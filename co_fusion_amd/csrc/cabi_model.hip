@@ -11,16 +11,6 @@
 
 using namespace cf;
 
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-#define LAUNCHCHK(ctx) HIPCHK(ctx, hipGetLastError())
-
 struct cf_model {
     cf_ctx* ctx = nullptr;
     uint32_t max_surfels = 0;

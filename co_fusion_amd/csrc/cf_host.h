@@ -70,6 +70,16 @@ struct cf_ctx {
     void set_error(const std::string& m);
 };
 extern "C" int cf_wait_stream(cf_ctx* ctx);   // the frame's host wait (cabi.hip)
+// A failed HIP call of a C-ABI entry point: its text and the runtime's message become the context's last error, the entry returns CF_EHIP
+#define HIPCHK(ctx, call)                                                                      \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess) {                                                                \
+            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
+            return CF_EHIP;                                                                    \
+        }                                                                                      \
+    } while (0)
+#define LAUNCHCHK(ctx) HIPCHK(ctx, hipGetLastError())   // behind a chain of launches
 struct cf_odom;
 namespace cf {
 // the reference-order tracker (track_ref.hip): RGBDOdometry::getIncrementalTransformation for one prepared tracker, host loop included

@@ -1,5 +1,6 @@
 // cf_segment.h -- what segment.hip (the motion branch) and segment_masks.hip (the label-mask branch) share: the batching of kernel
-// arguments over the sequences of a lock-step group, the blocked sequential f32 chain, and the segmenter itself.
+// arguments over the sequences of a lock-step group, the blocked sequential f32 chain, the workgroup scan and the phase stamps of the
+// single-workgroup kernels, the capacities of their tables, and the segmenter itself.
 #pragma once
 #include <vector>
 
@@ -38,6 +39,39 @@ __device__ __forceinline__ float seq_block_phases(float sum, const float (&t)[kS
     }
     return sum;
 }
+
+// label capacity of the kernels' static tables (labels incl. the "new model" label): model ids are 8 bits and 255 marks a rejected
+// superpixel, the reference's own limit (CoFusion.cpp:631-634, Segmentation.cpp).  A segmenter's buffers are sized for
+// cf_segmenter::Lcap = the context's max_models (cf_config), 16 by default.
+constexpr int kMaxL = 256;
+constexpr int kSegMaxK = 4800;   // superpixels of the largest supported image (1280x960): what the single-workgroup kernels hold in LDS
+
+#ifdef CF_ABLATE
+// diagnostics build (CF_SEG_TRACE=<inference>): phase stamps of segmenter 0's two single-workgroup kernels, 100 MHz constant clock, into
+// g_seg_trace[2][16] -- defined once, by the translation unit whose kernels stamp (segment.hip, ahead of its stage headers)
+#define GSTAMP(which, k) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x == 0) g_seg_trace[which][k] = wall_clock64(); } while (0)
+#else
+#define GSTAMP(which, k) do {} while (0)
+#endif
+
+// Inclusive scan of one int per thread over the workgroup (<= 1024 threads): a wave-level scan (six shuffle steps), the waves' totals
+// through LDS, every thread adds the totals of the waves in front of it -- two barriers instead of the 2 x log2(T) of the
+// Hillis-Steele loop these kernels used until round 6 (twenty with sixteen waves, a few hundred ns each).  Returns the inclusive prefix;
+// *total = the sum over the workgroup.  s_wave: >= 16 ints of LDS, free before and after.
+__device__ __forceinline__ int block_scan_inclusive(int v, int* s_wave, int* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x + 63) >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    __syncthreads();   // (s_wave may still be read from a previous scan)
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < nw; w++) { const int t = s_wave[w]; all += t; if (w < wave) before += t; }
+    *total = all;
+    return incl + before;
+}
 }  // namespace cf
 
 struct cf_segmenter {
@@ -60,7 +94,7 @@ struct cf_segmenter {
     // device-side unaries / post-processing (cf_seg_sums / cf_seg_infer / cf_seg_fetch)
     float *raw_mean = nullptr, *low_mean = nullptr;   // [(1 + 2 Lcap)][K]
     float *avg_conf = nullptr, *depth_range = nullptr;
-    int *parent = nullptr, *comp = nullptr, *cc = nullptr;
+    int* cc = nullptr;                   // [6][K]: seg_post_kernel's component statistics when they outgrow LDS
     cf_seg_result* d_result = nullptr;
     cf_seg_result* h_result = nullptr;   // pinned
     unsigned char* h_low_map = nullptr;  // pinned [K]

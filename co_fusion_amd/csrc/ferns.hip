@@ -24,15 +24,6 @@
 
 using namespace cf;
 
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-
 namespace {
 
 constexpr unsigned long long kArmed = ~0ull;

@@ -20,15 +20,6 @@
 
 using namespace cf;
 
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-
 namespace {
 
 constexpr int kIdctBlocksPerGroup = 32;   // eight lanes per 8x8 block: 256 threads

@@ -302,15 +302,6 @@ __global__ void __launch_bounds__(kB) render_resolve_kernel(const ViewDev v, con
 using namespace cf;
 using namespace cf::rnd;
 
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-
 struct cf_renderer {
     cf_ctx* ctx = nullptr;
     int max_w = 0, max_h = 0;

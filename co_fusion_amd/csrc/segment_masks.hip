@@ -254,16 +254,6 @@ __global__ void __launch_bounds__(64) mask_stats_kernel(const SegBatch<MaskStats
 }  // namespace cf
 
 // ===================================================================================== C-ABI ====
-#define HIPCHK(ctx, call)                                                                      \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CF_EHIP;                                                                    \
-        }                                                                                      \
-    } while (0)
-#define LAUNCHCHK(ctx) HIPCHK(ctx, hipGetLastError())
-
 static int check_mask_job(cf_ctx* ctx, const cf_seg_mask_job& j)
 {
     if (!j.seg || j.seg->ctx != ctx || !j.mask_dev || !j.depth_dev || !j.model_ids || !j.mapping || !j.full_dev || j.n_models <= 0) return CF_EINVAL;

@@ -299,77 +299,7 @@ Segmentation::~Segmentation()
     cf_seg_destroy(seg);
 }
 
-SegmentationResult Segmentation::performSegmentation(ModelList& models, const FrameData& frame, const float* depth_dev, const uint8_t* rgba_dev,
-                                                     const uint8_t* rgba_first_rows, unsigned char nextModelID, bool allowNew,
-                                                     uint8_t* full_dev)
-{
-    if (frame.mask) return performSegmentationGT(models, frame, nextModelID, allowNew, full_dev);
-    return performSegmentationCRF(models, depth_dev, rgba_dev, rgba_first_rows, nextModelID, allowNew, full_dev);
-}
-
-namespace {
-struct CompData { unsigned char label; int top, right, bottom, left, size; };
-
-// ConnectedLabels.hpp:50-172
-int connectedLabels(const uint8_t* in, int cols, int rows, std::vector<int>& comp, std::vector<CompData>& stats)
-{
-    std::vector<int> roots;
-    auto newComponent = [&roots]() { int r = (int)roots.size(); roots.push_back(r); return r; };
-    auto findRoot = [&roots](int i) { while (i != roots[i]) i = roots[i]; return i; };
-    comp.assign((size_t)cols * rows, 0);
-    comp[0] = newComponent();
-    for (int c = 1; c < cols; c++) comp[c] = (in[c] == in[c - 1]) ? comp[c - 1] : newComponent();
-    for (int r = 1; r < rows; r++) {
-        const uint8_t *row = in + (size_t)r * cols, *last = in + (size_t)(r - 1) * cols;
-        int *cr = comp.data() + (size_t)r * cols, *lc = comp.data() + (size_t)(r - 1) * cols;
-        cr[0] = (row[0] == last[0]) ? lc[0] : newComponent();
-        for (int c = 1; c < cols; c++) {
-            if (row[c] == row[c - 1]) {
-                const int cLeft = cr[c - 1], cTop = lc[c];
-                if (row[c] == last[c] && cLeft != cTop) {
-                    const int r1 = findRoot(cTop), r2 = findRoot(cLeft);
-                    if (r1 < r2) { roots[r2] = r1; cr[c] = r1; } else { roots[r1] = r2; cr[c] = r2; }
-                } else cr[c] = cLeft;
-            } else if (row[c] == last[c]) cr[c] = lc[c];
-            else cr[c] = newComponent();
-        }
-    }
-    std::vector<int> mapping(roots.size());
-    int rootCnt = 0;
-    for (int id = 0; id < (int)roots.size(); id++) {
-        const int root = findRoot(id);
-        if (root == id) mapping[root] = rootCnt++;
-        else roots[id] = root;
-    }
-    for (auto& c : roots) c = mapping[c];
-    stats.assign(rootCnt, CompData{0, 2147483647, 0, 0, 2147483647, 0});
-    for (int y = 0; y < rows; y++)
-        for (int x = 0; x < cols; x++) {
-            const int c = roots[comp[(size_t)y * cols + x]];
-            comp[(size_t)y * cols + x] = c;
-            CompData& d = stats[c];
-            d.size++; d.label = in[(size_t)y * cols + x];
-            if (y < d.top) d.top = y;
-            if (y > d.bottom) d.bottom = y;
-            if (x < d.left) d.left = x;
-            if (x > d.right) d.right = x;
-        }
-    return rootCnt;
-}
-
-// Slic::downsample<float> normalisation incl. the empty-superpixel fallback (Slic.h:63-76, 192-206)
-void finishMean(const int64_t* sumq, const uint32_t* cntOwn, const uint32_t* spixelCounts, const int32_t* resample, int K, float* out)
-{
-    for (int k = 0; k < K; k++) out[k] = (float)std::ldexp((double)sumq[k], -32);
-    for (int k = 0; k < K; k++) {
-        int cnt = (int)cntOwn[k], read = k;
-        if (cnt == 0) { read = resample[k]; cnt = (int)spixelCounts[read]; }
-        out[k] = out[read] / (float)cnt;
-    }
-}
-}  // namespace
-
-// Device-resident flavour (default): sums, unaries, mean field, component analysis and up-sampling are enqueued without a host wait;
+// The motion segmentation: sums, unaries, mean field, component analysis and up-sampling are enqueued without a host wait;
 // finishCRF() collects the decisions after the frame's one synchronisation.
 void Segmentation::enqueueCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev, unsigned char nextModelID, bool allowNew,
                               uint8_t* full_dev)
@@ -478,24 +408,31 @@ void Segmentation::runMaskBatch(cf_ctx* ctx, const std::vector<cf_seg_mask_job>&
     check(ctx, cf_seg_masks_batch(ctx, jobs.data(), (int)jobs.size()), "cf_seg_masks_batch");
 }
 
-SegmentationResult Segmentation::finishMasks()
+// the rows a job left behind as SegmentationResult::ModelData; boxes: the motion branch reports them, the mask branch never did
+SegmentationResult Segmentation::resultRows(const cf_seg_result& r, bool boxes) const
 {
-    PhaseTimer pt(PhaseTimes::SegPost);
     SegmentationResult result;
-    cf_seg_result r{};
-    check(ctx, cf_seg_fetch(seg, &r, nullptr), "cf_seg_fetch");
-    int value = -1;
-    check(ctx, cf_seg_new_mask_value(seg, &value), "cf_seg_new_mask_value");
-    if (value >= 0) gtMapping[value & 255] = pendingNextId;   // Segmentation.cpp:80: the function-static mapping of the reference
     result.hasNewLabel = r.has_new_label != 0;
     for (int i = 0; i < r.n_models; i++) {
         SegmentationResult::ModelData md;
         md.id = r.model[i].id; md.modelIndex = i < pendingModels ? i : -1;
         md.superPixelCount = r.model[i].superPixelCount; md.avgConfidence = r.model[i].avgConfidence;
         md.depthMean = r.model[i].depthMean; md.depthStd = r.model[i].depthStd;
+        if (boxes) { md.top = r.model[i].top; md.right = r.model[i].right; md.bottom = r.model[i].bottom; md.left = r.model[i].left; }
         result.modelData.push_back(md);
     }
     return result;
+}
+
+SegmentationResult Segmentation::finishMasks()
+{
+    PhaseTimer pt(PhaseTimes::SegPost);
+    cf_seg_result r{};
+    check(ctx, cf_seg_fetch(seg, &r, nullptr), "cf_seg_fetch");
+    int value = -1;
+    check(ctx, cf_seg_new_mask_value(seg, &value), "cf_seg_new_mask_value");
+    if (value >= 0) gtMapping[value & 255] = pendingNextId;   // Segmentation.cpp:80: the function-static mapping of the reference
+    return resultRows(r, false);
 }
 
 bool Segmentation::fetchPublishedPoses(size_t nModels, std::vector<int64_t>& words)
@@ -510,214 +447,12 @@ bool Segmentation::fetchPublishedPoses(size_t nModels, std::vector<int64_t>& wor
 SegmentationResult Segmentation::finishCRF()
 {
     PhaseTimer pt(PhaseTimes::SegPost);
-    SegmentationResult result;
     cf_seg_result r{};
-    const int K = (width / SPIX) * (height / SPIX);
-    result.lowMap.resize(K);
-    check(ctx, cf_seg_fetch(seg, &r, result.lowMap.data()), "cf_seg_fetch");
-    result.hasNewLabel = r.has_new_label != 0;
+    std::vector<uint8_t> lowMap((size_t)(width / SPIX) * (height / SPIX));
+    check(ctx, cf_seg_fetch(seg, &r, lowMap.data()), "cf_seg_fetch");
+    SegmentationResult result = resultRows(r, true);
     result.depthRange = r.depth_range;
-    for (int i = 0; i < r.n_models; i++) {
-        SegmentationResult::ModelData md;
-        md.id = r.model[i].id; md.modelIndex = i < pendingModels ? i : -1;
-        md.superPixelCount = r.model[i].superPixelCount; md.avgConfidence = r.model[i].avgConfidence;
-        md.depthMean = r.model[i].depthMean; md.depthStd = r.model[i].depthStd;
-        md.top = r.model[i].top; md.right = r.model[i].right; md.bottom = r.model[i].bottom; md.left = r.model[i].left;
-        result.modelData.push_back(md);
-    }
-    return result;
-}
-
-// Host flavour (CF_SEG_HOST=1, diagnostics): the reference's host logic verbatim around the GPU SLIC / sums / mean field, with a
-// host wait after each of them.  Same results as the device flavour.
-SegmentationResult Segmentation::performSegmentationCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev,
-                                                        const uint8_t* rgba_first_rows, unsigned char nextModelID, bool allowNew,
-                                                        uint8_t* full_dev)
-{
-    SegmentationResult result;
-    const int n_models = (int)models.size();
-    const int numLabels = allowNew ? n_models + 1 : n_models;
-    const float MAX_DEPTH = 100;
-    const int gx = width / SPIX, gy = height / SPIX, K = gx * gy;
-
-    std::unique_ptr<PhaseTimer> pt(new PhaseTimer(PhaseTimes::SegSlicAccumulate));
-    if (!slicStarted) check(ctx, cf_seg_slic(seg, rgba_dev), "cf_seg_slic");  // otherwise enqueued by startSlic() beside the tracking
-    slicStarted = false;
-    std::vector<uint32_t> spc(K), dcnt(K);
-    std::vector<int64_t> dsum(K), icpSum((size_t)K * n_models), confSum((size_t)K * n_models);
-    std::vector<int32_t> resample(K);
-    std::vector<const float*> icpPtr(n_models), vcPtr(n_models);
-    {
-        int m = 0;
-        for (auto& mdl : models) {
-            // a shadow contributes zeros here; its owner's sums arrive through the all-reduce below
-            const bool mine = mdl->isOwned() && (!dist || dist->contributes(mdl->getID()));
-            icpPtr[m] = mine ? mdl->icpErrorSurface() : zeroImage;
-            vcPtr[m] = mine ? mdl->vertexConfProjection() : zeroImage;
-            m++;
-        }
-    }
-    check(ctx, cf_seg_accumulate(seg, depth_dev, n_models, icpPtr.data(), vcPtr.data(), spc.data(), dcnt.data(), dsum.data(), icpSum.data(),
-                                 confSum.data(), resample.data()),
-          "cf_seg_accumulate");
-    if (dist && dist->active()) {  // exact: integer sums, every model has exactly one owner
-        dist->sum(icpSum.data(), icpSum.size());
-        dist->sum(confSum.data(), confSum.size());
-    }
-    pt.reset(new PhaseTimer(PhaseTimes::SegUnary));
-    std::vector<float> lowDepth(K);
-    finishMean(dsum.data(), dcnt.data(), spc.data(), resample.data(), K, lowDepth.data());
-    float depthMin = 3.402823466e+38f, depthMax = 0;
-    for (int i = 0; i < K; i++) {
-        const float d = lowDepth[i];
-        if (d > MAX_DEPTH || d < 0 || !std::isfinite(d)) continue;
-        if (depthMax < d) depthMax = d;
-        if (depthMin > d) depthMin = d;
-    }
-    result.depthRange = depthMax - depthMin;
-    const float depthRange = result.depthRange;
-
-    std::vector<std::vector<float>> lowICP(n_models, std::vector<float>(K)), lowConf(n_models, std::vector<float>(K));
-    int modelIdToIndex[256];
-    for (int i = 0; i < 256; i++) modelIdToIndex[i] = 0;
-    {
-        int m = 0;
-        for (auto& mdl : models) {
-            finishMean(icpSum.data() + (size_t)m * K, spc.data(), spc.data(), resample.data(), K, lowICP[m].data());
-            finishMean(confSum.data() + (size_t)m * K, spc.data(), spc.data(), resample.data(), K, lowConf[m].data());
-            SegmentationResult::ModelData md;
-            md.id = mdl->getID(); md.modelIndex = m;
-            modelIdToIndex[md.id & 255] = m;
-            float avg = 0;
-            for (int j = 0; j < K; j++) {
-                float& c = lowConf[m][j];
-                if (!std::isfinite(c)) { c = 0; continue; }
-                avg += c;
-            }
-            md.avgConfidence = avg / (float)K;
-            result.modelData.push_back(md);
-            m++;
-        }
-    }
-    if (allowNew) {
-        modelIdToIndex[nextModelID] = n_models;
-        SegmentationResult::ModelData md;
-        md.id = nextModelID; md.modelIndex = -1;
-        result.modelData.push_back(md);
-    }
-    int n_md = (int)result.modelData.size();
-
-    const int L = numLabels;
-    std::vector<float> unary((size_t)K * L);
-    for (int k = 0; k < K; k++) {  // Segmentation.cpp:237-298
-        if ((double)lowConf[0][k] < 0.3) lowICP[0][k] = (float)((double)depthRange * 0.01);
-        for (int i = 1; i < n_models; i++)
-            if ((double)lowConf[i][k] <= 0.4) lowICP[i][k] = depthRange * unaryKError;
-        float lowestError = lowICP[0][k] / depthRange;
-        for (int i = 0; i < n_models; i++) {
-            float error = lowICP[i][k];
-            error /= depthRange;
-            if (error < lowestError) lowestError = error;
-            unary[(size_t)k * L + i] = unaryWeightError * error;
-        }
-        if (allowNew) unary[(size_t)k * L + n_models] = std::fmax(unaryThresholdNew - unaryWeightError * lowestError, 0.01f);
-    }
-    std::vector<float> f1((size_t)K * 2), f2((size_t)K * 6);
-    for (int j = 0; j < gy; j++)
-        for (int i = 0; i < gx; i++) {
-            const int index = j * gx + i;
-            f1[index * 2 + 0] = (float)i / 2.0f; f1[index * 2 + 1] = (float)j / 2.0f;
-            f2[index * 6 + 0] = (float)i * scaleFeaturesPos;
-            f2[index * 6 + 1] = (float)j * scaleFeaturesPos;
-            // colour features index the FULL-resolution image with the LOW-resolution index (Segmentation.cpp:445-447)
-            f2[index * 6 + 2] = (float)rgba_first_rows[(size_t)index * 4 + 0] * scaleFeaturesRGB;
-            f2[index * 6 + 3] = (float)rgba_first_rows[(size_t)index * 4 + 1] * scaleFeaturesRGB;
-            f2[index * 6 + 4] = (float)rgba_first_rows[(size_t)index * 4 + 2] * scaleFeaturesRGB;
-            f2[index * 6 + 5] = std::fmin(lowDepth[index] * scaleFeaturesDepth, 100.0f);
-        }
-    for (auto& u : unary) if (u <= 1e-5f) u = 1e-5f;
-    std::vector<float> Q((size_t)K * L);
-    pt.reset(new PhaseTimer(PhaseTimes::SegCrf));
-    check(ctx, cf_seg_crf(seg, unary.data(), L, f1.data(), f2.data(), weightSmoothness, weightAppearance, (int)crfIterations, Q.data()), "cf_seg_crf");
-    pt.reset(new PhaseTimer(PhaseTimes::SegPost));
-    std::vector<uint8_t> map(K);
-    for (int i = 0; i < K; i++) {
-        int m = 0; float best = Q[(size_t)i * L];
-        for (int l = 1; l < L; l++) if (Q[(size_t)i * L + l] > best) { best = Q[(size_t)i * L + l]; m = l; }
-        map[i] = (uint8_t)result.modelData[m].id;
-    }
-
-    std::vector<int> comp; std::vector<CompData> cc;
-    const int ncc = connectedLabels(map.data(), gx, gy, comp, cc);
-    {  // onlyKeepLargest (Segmentation.cpp:496-517): every label but the smallest key keeps its largest component
-        int minLabel = 256;
-        for (int i = 0; i < ncc; i++) if (cc[i].label < minLabel) minLabel = cc[i].label;
-        for (int lab2 = 0; lab2 < 256; lab2++) {
-            if (lab2 == minLabel) continue;
-            int keep = -1;
-            for (int i = 0; i < ncc; i++) {
-                if (cc[i].label != lab2) continue;
-                if (keep < 0) { keep = i; continue; }
-                if (cc[keep].size < cc[i].size) { cc[keep].label = 255; keep = i; } else cc[i].label = 255;
-            }
-        }
-    }
-    if (allowNew) {  // :521-530
-        const int minSize = (int)((float)K * minRelSizeNew), maxSize = (int)((float)K * maxRelSizeNew);
-        for (int i = 0; i < ncc; i++)
-            if (cc[i].label == nextModelID && (cc[i].size < minSize || cc[i].size > maxSize)) cc[i].label = 255;
-    }
-    for (auto& md : result.modelData) {  // :532-547
-        for (int i = 0; i < ncc; i++) {
-            if (cc[i].label != (md.id & 255)) continue;
-            if (cc[i].left < md.left) md.left = cc[i].left;
-            if (cc[i].top < md.top) md.top = cc[i].top;
-            if (cc[i].right > md.right) md.right = cc[i].right;
-            if (cc[i].bottom > md.bottom) md.bottom = cc[i].bottom;
-        }
-        md.left = (unsigned short)(int)(md.left * SPIX + SPIX * 0.5); md.top = (unsigned short)(int)(md.top * SPIX + SPIX * 0.5);
-        md.right = (unsigned short)(int)(md.right * SPIX + SPIX * 0.5); md.bottom = (unsigned short)(int)(md.bottom * SPIX + SPIX * 0.5);
-    }
-    {
-        const unsigned borderSize = 20, fullHeight = (unsigned)height, fullWidth = (unsigned)width;  // :549-563
-        for (auto& md : result.modelData) {
-            if (md.id == 0) continue;
-            const unsigned top = (unsigned)md.top, bottom = (unsigned)md.bottom, left = (unsigned)md.left, right = (unsigned)md.right;
-            if ((top < borderSize && bottom < borderSize) || (left < borderSize && right < borderSize) ||
-                (top > fullHeight - borderSize && bottom > fullHeight - borderSize) || (left > fullWidth - borderSize && right > fullWidth - borderSize))
-                for (int i = 0; i < ncc; i++) if (cc[i].label == (md.id & 255)) cc[i].label = 255;
-        }
-    }
-    for (int i = 0; i < K; i++) map[i] = cc[comp[i]].label;
-    {  // depth statistics with one trimming pass (:570-621)
-        std::vector<float> sumsDepth(n_md, 0.f), sumsDev(n_md, 0.f);
-        std::vector<unsigned> cnts(n_md, 0);
-        for (int i = 0; i < K; i++) { if (map[i] == 255) continue; const int ix = modelIdToIndex[map[i]]; sumsDepth[ix] += lowDepth[i]; cnts[ix]++; }
-        for (int m = 0; m < n_md; m++) result.modelData[m].depthMean = cnts[m] ? sumsDepth[m] / (float)cnts[m] : 0;
-        for (int i = 0; i < K; i++) { if (map[i] == 255) continue; const int ix = modelIdToIndex[map[i]]; sumsDev[ix] += std::fabs(result.modelData[ix].depthMean - lowDepth[i]); }
-        for (int m = 0; m < n_md; m++) result.modelData[m].depthStd = cnts[m] ? sumsDev[m] / (float)cnts[m] : 0;
-        for (int i = 0; i < K; i++) {
-            if (map[i] == 255) continue;
-            const int ix = modelIdToIndex[map[i]];
-            if (ix != 0) {
-                const float d = lowDepth[i];
-                if ((double)d > 1.1 * (double)result.modelData[ix].depthStd + (double)result.modelData[ix].depthMean) {
-                    sumsDepth[ix] -= d; sumsDev[ix] -= std::fabs(result.modelData[ix].depthMean - d); cnts[ix]--;
-                }
-            }
-        }
-        for (int m = 0; m < n_md; m++) {
-            result.modelData[m].depthMean = cnts[m] ? sumsDepth[m] / (float)cnts[m] : 0;
-            result.modelData[m].depthStd = cnts[m] ? sumsDev[m] / (float)cnts[m] : 0;
-        }
-    }
-    for (int k = 0; k < K; k++) { if (map[k] == 255) continue; result.modelData[modelIdToIndex[map[k]]].superPixelCount++; }
-    if (allowNew) {
-        if (result.modelData.back().superPixelCount > 0) result.hasNewLabel = true;
-        else result.modelData.pop_back();
-    }
-    check(ctx, cf_seg_upsample(seg, map.data(), full_dev), "cf_seg_upsample");
-    result.lowMap = map;
+    result.lowMap = std::move(lowMap);
     return result;
 }
 
@@ -1330,14 +1065,7 @@ void CoFusion::frameCollect()
             SegmentationResult seg;
             if (segOnDevice) seg = labelGenerator->finishCRF();
             else if (st.masksOnDevice) seg = labelGenerator->finishMasks();
-            else {
-                // the colour features of the CRF read the first K pixels of the full-resolution image
-                const int K = (cfg.width / 16) * (cfg.height / 16);
-                std::vector<uint8_t> firstRows((size_t)K * 4);
-                if (frame.rgba_dev) check(ctx, cf_memcpy_d2h(ctx, firstRows.data(), curRgba, (size_t)K * 4), "rgb readback");
-                else for (int i = 0; i < K; i++) { firstRows[i * 4] = frame.rgb[i * 3]; firstRows[i * 4 + 1] = frame.rgb[i * 3 + 1]; firstRows[i * 4 + 2] = frame.rgb[i * 3 + 2]; firstRows[i * 4 + 3] = 255; }
-                seg = labelGenerator->performSegmentation(models, frame, curDepth, curRgba, firstRows.data(), getNextModelID(), allowNew, mask_dev);
-            }
+            else seg = labelGenerator->performSegmentationGT(models, frame, getNextModelID(), allowNew, mask_dev);   // a host mask (frame.mask)
             if (!exportSegmentationPrefix.empty()) {  // CoFusion.cpp:235-240: labels > 254 (rejected) are written as 0
                 std::vector<uint8_t> labels(N);
                 check(ctx, cf_memcpy_d2h(ctx, labels.data(), mask_dev, N), "mask readback");

@@ -180,19 +180,20 @@ class Segmentation {
     ~Segmentation();
     Segmentation(const Segmentation&) = delete;
     Segmentation& operator=(const Segmentation&) = delete;
-    // Segmentation::performSegmentation (Segmentation.cpp:59-119 GT branch, :124-706 CRF branch)
-    SegmentationResult performSegmentation(ModelList& models, const FrameData& frame, const float* depth_dev, const uint8_t* rgba_dev,
-                                           const uint8_t* rgba_host_first_rows, unsigned char nextModelID, bool allowNew,
-                                           uint8_t* fullSegmentation_dev);
-    // enqueue SLIC for this frame's image ahead of performSegmentation (on whatever stream the context currently uses)
+    // Segmentation::performSegmentation's GT branch (Segmentation.cpp:59-119) on the host, for a frame whose label mask is a host buffer
+    // (frame.mask: model-parallel runs and CF_MASKS_HOST=1); uploads the label image into fullSegmentation_dev.  Its CRF branch
+    // (:124-706) is the device-resident chain below.
+    SegmentationResult performSegmentationGT(ModelList& models, const FrameData& frame, unsigned char nextModelID, bool allowNew,
+                                             uint8_t* fullSegmentation_dev);
+    // enqueue SLIC for this frame's image ahead of enqueueCRF / collectCRF (on whatever stream the context currently uses)
     void startSlic(const uint8_t* rgba_dev);
     // ... and, behind it, everything else of the device-resident CRF chain that does not need this frame's tracking (cf_seg_early: the
     // frame's and the confidences' sums, means, depth range, average confidences, appearance features and kernel matrix).  The models'
     // confidence projections are the previous frame's prediction; enqueueCRF then finds the segmenter prepared and enqueues the rest.
     // Single-process sequences only (the confidence sums are consumed here: no collective could add the other ranks' to them).
     void startEarly(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev);
-    // performSegmentationCRF in two halves without a host wait in between: everything is enqueued (sums, unaries, mean field,
-    // component analysis, up-sampling into fullSegmentation_dev), the decisions are collected later
+    // the reference's performSegmentationCRF in two halves without a host wait in between: everything is enqueued (sums, unaries, mean
+    // field, component analysis, up-sampling into fullSegmentation_dev), the decisions are collected later
     void enqueueCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev, unsigned char nextModelID, bool allowNew,
                     uint8_t* fullSegmentation_dev);
     SegmentationResult finishCRF();
@@ -223,10 +224,7 @@ class Segmentation {
     unsigned crfIterations = 10;
 
   private:
-    SegmentationResult performSegmentationCRF(ModelList& models, const float* depth_dev, const uint8_t* rgba_dev,
-                                              const uint8_t* rgba_first_rows, unsigned char nextModelID, bool allowNew, uint8_t* full_dev);
-    SegmentationResult performSegmentationGT(ModelList& models, const FrameData& frame, unsigned char nextModelID, bool allowNew,
-                                             uint8_t* full_dev);
+    SegmentationResult resultRows(const cf_seg_result& r, bool boxes) const;   // finishCRF / finishMasks
     cf_ctx* ctx;
     cf_segmenter* seg = nullptr;
     int width, height;

@@ -419,22 +419,16 @@ int cf_seg_create(cf_ctx *ctx, cf_segmenter **out);
 void cf_seg_destroy(cf_segmenter *s);
 /* Slic::setInputImage + processFrame (Slic.cpp:48-81) */
 int cf_seg_slic(cf_segmenter *s, const uint8_t *rgba);
-/* Slic::downsample / downsampleThresholded sums (Slic.h:48-120) as exact Q32 fixed point: per superpixel
- * pixel count, count and sum of depth > 0.02, and per model the sums of the ICP error surface and of the
- * splat confidence (vertexConf.w).  Host outputs: [K], [K], [K], [n_models*K], [n_models*K], [K]. */
-int cf_seg_accumulate(cf_segmenter *s, const float *depth, int n_models, const float *const *icp_err,
-                      const float *const *vertconf4, uint32_t *spix_count_host, uint32_t *depth_count_host,
-                      int64_t *depth_sum_host, int64_t *icp_sum_host, int64_t *conf_sum_host, int32_t *resample_labels_host);
 /* DenseCRF2D inference of Segmentation.cpp:436-480: unary [K*L], Gaussian features [K*2] and bilateral
  * features [K*6] from the host, marginals Q [K*L] back to the host. */
 int cf_seg_crf(cf_segmenter *s, const float *unary_host, int L, const float *feat_smooth_host, const float *feat_app_host,
                float w_smooth, float w_app, int iterations, float *Q_host);
-/* Slic::upsample<unsigned char> (Slic.h:127-139): low_map [K] host -> full-resolution mask on the device */
-int cf_seg_upsample(cf_segmenter *s, const uint8_t *low_map_host, uint8_t *full_dev);
-/* Device-resident flavour of the three calls above (what the facade uses): per-superpixel sums stay on the device
- * (cf_seg_sums), unary construction, the mean field, arg-max, connected components (ConnectedLabels.hpp:50-172), the
- * largest-component / size / border gates, bounding boxes, depth statistics and the up-sampling into full_dev all run as
- * kernels (cf_seg_infer, Segmentation.cpp:160-706); only the decisions come back (cf_seg_fetch, the one host wait). */
+/* The device-resident chain (what the facade uses).  cf_seg_sums: Slic::downsample / downsampleThresholded sums (Slic.h:48-120) as
+ * exact Q32 fixed point, left on the device -- per superpixel the pixel count, count and sum of depth > 0.02, and per model the sums of
+ * the ICP error surface and of the splat confidence (vertexConf.w).  cf_seg_infer (Segmentation.cpp:160-706): unary construction, the
+ * mean field, arg-max, connected components (ConnectedLabels.hpp:50-172), the largest-component / size / border gates, bounding boxes,
+ * depth statistics and Slic::upsample<unsigned char> (Slic.h:127-139) into full_dev, all as kernels; only the decisions come back
+ * (cf_seg_fetch, the one host wait). */
 typedef struct {
     float unaryWeightError, unaryKError, unaryThresholdNew;        /* GUI defaults 75, 0.0375, 5.5 (GUI.h:222-224) */
     float weightAppearance, weightSmoothness;                      /* 7, 2 */
