@@ -456,6 +456,13 @@ class FrameDecoder:
         self.lib.cf_frame_decoder_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(_klg.FrameDesc)]
         self.lib.cf_frame_decoder_acquire.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         self.lib.cf_frame_decoder_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        from . import images as _im
+        self._im = _im
+        self.lib.cf_frame_decoder_enable_images.argtypes = [C.c_void_p]
+        self.lib.cf_frame_decoder_image_slot.argtypes = [C.c_void_p, C.c_int, C.POINTER(_im.ImageSlot)]
+        self.lib.cf_frame_decoder_submit_images.argtypes = [C.c_void_p, C.c_int, C.POINTER(_im.ImageDesc)]
+        self.lib.cf_frame_decoder_acquire_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        self.lib.cf_frame_decoder_image_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         self.h = C.c_void_p()
         ctx._check(self.lib.cf_frame_decoder_create(ctx.h, self.max_w, self.max_h, self.slots, C.byref(self.h)))
         self._size = {}
@@ -499,6 +506,107 @@ class FrameDecoder:
             return torch.as_tensor(holder, device=dev)
 
         return view(dp.value, (H, W), "<f4"), view(cp.value, (H, W, 4), "|u1")
+
+    # ---- image-sequence frames (csrc/image_decode.hip) ----
+    def enable_images(self):
+        """allocate the image staging of every slot (once); without it the image entries are refused"""
+        self.ctx._check(self.lib.cf_frame_decoder_enable_images(self.h))
+
+    def image_slot(self, s):
+        """slot s's pinned image staging: the ImageSlot itself and numpy views dict(color, depth, mask, palette u8; blocks EXR_BLOCK)"""
+        _im = self._im
+        m = _im.ImageSlot()
+        self.ctx._check(self.lib.cf_frame_decoder_image_slot(self.h, int(s), C.byref(m)))
+        v = dict(color=np.ctypeslib.as_array(m.color, shape=(int(m.color_bytes),)), depth=np.ctypeslib.as_array(m.depth, shape=(int(m.depth_bytes),)),
+                 mask=np.ctypeslib.as_array(m.mask, shape=(int(m.mask_bytes),)), palette=np.ctypeslib.as_array(m.palette, shape=(768,)),
+                 blocks=np.ctypeslib.as_array(C.cast(m.blocks, C.POINTER(C.c_uint32)), shape=(int(m.max_blocks), 4)))
+        return m, v
+
+    def submit_images(self, s, desc):
+        """cf_frame_decoder_submit_images with an images.ImageDesc the caller filled beside the slot's staging"""
+        self.ctx._check(self.lib.cf_frame_decoder_submit_images(self.h, int(s), C.byref(desc)))
+        self._size[int(s)] = (int(desc.height), int(desc.width))
+
+    def submit_image_files(self, s, color=None, depth=None, mask=None, flip_colors=False, depth_scale=None, size=None):
+        """Stage the files of one frame in slot s and submit it: what a worker of the image player does.  Each plane is (ext, bytes) or
+        None: color ".png" / ".jpg" / ".ppm", depth ".png" / ".exr", mask ".png" / ".pgm".  The host parsers (cofusion_png_decode,
+        cofusion_exr_decode, cofusion_jpeg_front) write straight into the pinned staging.  size = (W, H) where no PNG / EXR / PNM
+        plane gives it.  Returns the ImageDesc."""
+        _im, host = self._im, self._im._host()
+        m, v = self.image_slot(s)
+        d = _im.ImageDesc()
+        d.flip_colors = int(bool(flip_colors))
+        d.depth_scale = _im.DEFAULT_DEPTH_SCALE if depth_scale is None else float(depth_scale)
+        dims = [tuple(size)] if size else []
+
+        def png(data, role, dst, cap, palette=None):
+            info = _im.PngInfo()
+            data = bytes(data)
+            if host.cofusion_png_decode(data, C.c_uint64(len(data)), role, C.byref(info), dst, C.c_uint64(cap), palette) != 0:
+                raise CofusionError(host.cofusion_last_error().decode())
+            dims.append((info.width, info.height))
+            return info
+
+        if depth is not None and depth[0] == ".png":
+            png(depth[1], _im.ROLE_DEPTH, m.depth, m.depth_bytes)
+            d.depth_kind = _im.IMAGE_PNG
+        elif depth is not None:
+            info, data = _im.ExrInfo(), bytes(depth[1])
+            if host.cofusion_exr_decode(data, C.c_uint64(len(data)), C.byref(info), m.depth, C.c_uint64(m.depth_bytes), m.blocks, C.c_uint64(m.max_blocks)) != 0:
+                raise CofusionError(host.cofusion_last_error().decode())
+            dims.append((info.width, info.height))
+            d.depth_kind = _im.IMAGE_EXR
+            d.exr_blocks, d.exr_lines_per_block, d.exr_line_bytes = info.blocks, info.lines_per_block, info.line_bytes
+            d.exr_chan_offset, d.exr_chan_half = info.chan_offset, info.chan_half
+        if mask is not None and mask[0] == ".png":
+            png(mask[1], _im.ROLE_MASK, m.mask, m.mask_bytes)
+            d.mask_kind = _im.IMAGE_PNG
+        elif mask is not None:
+            from . import masks as _masks
+            g = _masks.parse_pgm(bytes(mask[1]))
+            dims.append((g.shape[1], g.shape[0]))
+            v["mask"][:g.size] = g.reshape(-1)
+            d.mask_kind = _im.IMAGE_RAW
+        if color is not None and color[0] == ".png":
+            info = png(color[1], _im.ROLE_COLOR, m.color, m.color_bytes, m.palette)
+            d.color_kind, d.png_color_type, d.png_palette_entries = _im.IMAGE_PNG, info.color_type, info.palette_entries
+        elif color is not None and color[0] == ".ppm":
+            rgb = _im.decode_ppm(color[1])
+            dims.append((rgb.shape[1], rgb.shape[0]))
+            self.slot(s)["rgb"][:rgb.size] = rgb.reshape(-1)
+            d.color_kind = _im.IMAGE_RAW
+        elif color is not None:
+            W, H = dims[0]
+            ks = self._klg.FrameSlot()
+            self.ctx._check(self.lib.cf_frame_decoder_slot(self.h, int(s), C.byref(ks)))
+            data = bytes(color[1])
+            rc = host.cofusion_jpeg_front(data, C.c_uint64(len(data)), W, H, ks.header, ks.coef, C.c_uint64(ks.coef_blocks))
+            if rc != 0:
+                raise CofusionError("JPEG front end: " + (host.cofusion_last_error().decode() if rc < 0 else "refused"))
+            d.color_kind = _im.IMAGE_JPEG
+        if len(set(dims)) != 1:
+            raise CofusionError(f"the planes of the frame differ in size: {dims}")
+        d.width, d.height = dims[0]
+        self.submit_images(s, d)
+        return d
+
+    def acquire_mask(self, s, complete=True):
+        """the u8 mask [H, W] of the slot's last image frame as a torch tensor viewing the decoder's buffer, None where it had none"""
+        mp = C.c_void_p()
+        self.ctx._check(self.lib.cf_frame_decoder_acquire_mask(self.h, int(s), int(bool(complete)), C.byref(mp)))
+        if not mp.value:
+            return None
+        H, W = self._size[int(s)]
+        holder = type("_DevView", (), {})()
+        holder.__cuda_array_interface__ = dict(shape=(H, W), typestr="|u1", data=(int(mp.value), False), version=2)
+        return torch.as_tensor(holder, device=self.ctx.device)
+
+    def image_timing(self):
+        """device-event durations of the two image kernels over the image frames submitted while timing(True) was on:
+        (exr_depth_kernel ms, frames that launched it, png_finish_kernel ms, frames that launched it); resets the sums"""
+        a, na, b, nb = C.c_double(), C.c_uint64(), C.c_double(), C.c_uint64()
+        self.ctx._check(self.lib.cf_frame_decoder_image_timing(self.h, C.byref(a), C.byref(na), C.byref(b), C.byref(nb)))
+        return a.value, na.value, b.value, nb.value
 
     def timing(self, on=True):
         """kernel durations from device events accumulated while timing was on: (idct ms, finish ms, frames); resets the sums"""

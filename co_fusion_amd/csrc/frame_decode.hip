@@ -15,8 +15,7 @@
 
 #include <string>
 
-#include "cf_device.h"
-#include "cf_host.h"
+#include "cf_frame_decoder.h"
 
 using namespace cf;
 
@@ -24,8 +23,7 @@ namespace {
 
 constexpr int kIdctBlocksPerGroup = 32;   // eight lanes per 8x8 block: 256 threads
 constexpr int kWsPitch = 9;               // row pitch of the transposition buffer in 8-byte words (8 + 1: rows start on different banks)
-constexpr int kHeaderBytes = 512;         // the header's place at the front of a slot's staging block (coefficients follow, 16 B aligned)
-constexpr int kMaxDecSlots = 16;
+constexpr int kHeaderBytes = kDecHeaderBytes;
 
 typedef long long i64;
 
@@ -204,32 +202,11 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-struct cf_frame_decoder {
-    cf_ctx* ctx = nullptr;
-    int max_w = 0, max_h = 0, slots = 0;
-    uint64_t cap_blocks = 0;
-    size_t off_depth = 0, off_rgb = 0, slot_bytes = 0;   // staging block: header | coefficients | depth | rgb (host and device alike)
-    hipStream_t stream = nullptr;
-    hipEvent_t consumed = nullptr;
-    hipEvent_t done[kMaxDecSlots]{};
-    uint8_t* h_slot[kMaxDecSlots]{};   // pinned
-    uint8_t* d_slot[kMaxDecSlots]{};
-    uint8_t* d_planes = nullptr;    // one set: the decoder's stream runs the frames one after the other
-    float* d_depth[kMaxDecSlots]{};
-    uint8_t* d_rgba[kMaxDecSlots]{};
-    bool submitted[kMaxDecSlots]{};
-    // diagnostics (cf_frame_decoder_timing)
-    bool timing = false;
-    hipEvent_t tev[kMaxDecSlots][3]{};
-    bool timed[kMaxDecSlots]{};
-    double idct_ms = 0, finish_ms = 0;
-    uint64_t frames = 0;
-};
-
 namespace {
 
 int harvest(cf_frame_decoder* d, int s)
 {
+    if (int r = image_ext_harvest(d, s)) return r;   // an image frame timed in this slot (the slot's events are shared)
     if (!d->timed[s]) return CF_OK;
     HIPCHK(d->ctx, hipEventSynchronize(d->tev[s][2]));
     float a = 0, b = 0;
@@ -260,6 +237,58 @@ bool header_fits(const cf_jpeg_header& h, const cf_frame_desc& desc, uint64_t ca
 }
 
 }  // namespace
+
+namespace cf {
+
+int frame_decoder_harvest(cf_frame_decoder* d, int slot) { return harvest(d, slot); }
+
+// The copies and the two launches of a frame whose colour lies in the slot's .klg staging, shared by cf_frame_decoder_submit
+// (with_depth: u16 mm depth converted in the depth half of the finishing grid, timing events recorded) and
+// cf_frame_decoder_submit_images (colour alone).  swap: store the triple reversed.
+int frame_decoder_colour(cf_frame_decoder* d, int slot, int width, int height, int color_kind, bool swap, bool with_depth)
+{
+    cf_ctx* ctx = d->ctx;
+    const size_t N = (size_t)width * height;
+    uint8_t *hs = d->h_slot[slot], *ds = d->d_slot[slot];
+    const cf_jpeg_header hdr = *reinterpret_cast<const cf_jpeg_header*>(hs);   // a copy: what is checked is what sizes the launch
+    const bool jpeg = color_kind == CF_FRAME_COLOR_JPEG;
+    cf_frame_desc desc;
+    desc.width = width; desc.height = height; desc.color_kind = color_kind; desc.flip_colors = 0;
+    if (jpeg && !header_fits(hdr, desc, d->cap_blocks)) {
+        ctx->set_error("cf_frame_decoder_submit: the slot's JPEG header does not describe a frame of this size");
+        return CF_EINVAL;
+    }
+    const bool timing = d->timing && with_depth;
+    if (with_depth) HIPCHK(ctx, hipMemcpyAsync(ds + d->off_depth, hs + d->off_depth, N * 2, hipMemcpyHostToDevice, d->stream));
+    if (jpeg) {
+        memcpy(hs, &hdr, sizeof(hdr));
+        HIPCHK(ctx, hipMemcpyAsync(ds, hs, kHeaderBytes + (size_t)hdr.total_blocks * 128, hipMemcpyHostToDevice, d->stream));
+    } else if (color_kind != CF_FRAME_COLOR_NONE) {
+        HIPCHK(ctx, hipMemcpyAsync(ds + d->off_rgb, hs + d->off_rgb, N * 3, hipMemcpyHostToDevice, d->stream));
+    }
+    if (timing) HIPCHK(ctx, hipEventRecord(d->tev[slot][0], d->stream));
+    if (jpeg) {
+        const int groups = (hdr.total_blocks + kIdctBlocksPerGroup - 1) / kIdctBlocksPerGroup;
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(groups), dim3(256), 0, d->stream, reinterpret_cast<const cf_jpeg_header*>(ds),
+                           reinterpret_cast<const int16_t*>(ds + kHeaderBytes), d->d_planes, hdr.total_blocks);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (timing) HIPCHK(ctx, hipEventRecord(d->tev[slot][1], d->stream));
+    FinishArgs a;
+    a.hdr = reinterpret_cast<const cf_jpeg_header*>(ds); a.planes = d->d_planes; a.rgb = ds + d->off_rgb;
+    a.depth_mm = reinterpret_cast<const uint16_t*>(ds + d->off_depth);
+    a.depth_out = d->d_depth[slot]; a.rgba_out = d->d_rgba[slot];
+    a.W = width; a.H = height; a.N = (int)N; a.kind = color_kind;
+    a.swap = swap ? 1 : 0;
+    a.colour_groups = (int)((N + 1023) / 1024);
+    // colour in the first colour_groups workgroups, depth in as many more: without them the colour half runs alone
+    hipLaunchKernelGGL(jpeg_finish_kernel, dim3((with_depth ? 2 : 1) * a.colour_groups), dim3(256), 0, d->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    if (timing) { HIPCHK(ctx, hipEventRecord(d->tev[slot][2], d->stream)); d->timed[slot] = true; }
+    return CF_OK;
+}
+
+}  // namespace cf
 
 extern "C" {
 
@@ -314,6 +343,7 @@ void cf_frame_decoder_destroy(cf_frame_decoder* d)
         if (d->d_rgba[s]) (void)hipFree(d->d_rgba[s]);
     }
     if (d->d_planes) (void)hipFree(d->d_planes);
+    image_ext_destroy(d->img);
     if (d->consumed) (void)hipEventDestroy(d->consumed);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
@@ -340,45 +370,15 @@ int cf_frame_decoder_submit(cf_frame_decoder* d, int slot, const cf_frame_desc* 
         ctx->set_error("cf_frame_decoder_submit: frame size outside the decoder's maximum, or an unknown colour kind");
         return CF_EINVAL;
     }
-    const size_t N = (size_t)desc->width * desc->height;
-    uint8_t *hs = d->h_slot[slot], *ds = d->d_slot[slot];
-    const cf_jpeg_header hdr = *reinterpret_cast<const cf_jpeg_header*>(hs);   // a copy: what is checked is what sizes the launch
-    const bool jpeg = desc->color_kind == CF_FRAME_COLOR_JPEG;
-    if (jpeg && !header_fits(hdr, *desc, d->cap_blocks)) {
-        ctx->set_error("cf_frame_decoder_submit: the slot's JPEG header does not describe a frame of this size");
-        return CF_EINVAL;
-    }
     if (d->timing) { if (int r = harvest(d, slot)) return r; }
     // the output frame (and the device input) of this slot may still be read by work the context's stream holds
     HIPCHK(ctx, hipEventRecord(d->consumed, ctx->stream));
     HIPCHK(ctx, hipStreamWaitEvent(d->stream, d->consumed, 0));
-    HIPCHK(ctx, hipMemcpyAsync(ds + d->off_depth, hs + d->off_depth, N * 2, hipMemcpyHostToDevice, d->stream));
-    if (jpeg) {
-        memcpy(hs, &hdr, sizeof(hdr));
-        HIPCHK(ctx, hipMemcpyAsync(ds, hs, kHeaderBytes + (size_t)hdr.total_blocks * 128, hipMemcpyHostToDevice, d->stream));
-    } else if (desc->color_kind != CF_FRAME_COLOR_NONE) {
-        HIPCHK(ctx, hipMemcpyAsync(ds + d->off_rgb, hs + d->off_rgb, N * 3, hipMemcpyHostToDevice, d->stream));
-    }
-    if (d->timing) HIPCHK(ctx, hipEventRecord(d->tev[slot][0], d->stream));
-    if (jpeg) {
-        const int groups = (hdr.total_blocks + kIdctBlocksPerGroup - 1) / kIdctBlocksPerGroup;
-        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(groups), dim3(256), 0, d->stream, reinterpret_cast<const cf_jpeg_header*>(ds),
-                           reinterpret_cast<const int16_t*>(ds + kHeaderBytes), d->d_planes, hdr.total_blocks);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    if (d->timing) HIPCHK(ctx, hipEventRecord(d->tev[slot][1], d->stream));
-    FinishArgs a;
-    a.hdr = reinterpret_cast<const cf_jpeg_header*>(ds); a.planes = d->d_planes; a.rgb = ds + d->off_rgb;
-    a.depth_mm = reinterpret_cast<const uint16_t*>(ds + d->off_depth);
-    a.depth_out = d->d_depth[slot]; a.rgba_out = d->d_rgba[slot];
-    a.W = desc->width; a.H = desc->height; a.N = (int)N; a.kind = desc->color_kind;
     // KlgLogReader::getNext: a JPEG is stored reversed (JPEGLoader::readData) and flip_colors reverses once more; raw colour is
     // reversed by flip_colors alone
-    a.swap = desc->color_kind == CF_FRAME_COLOR_RAW ? (desc->flip_colors != 0) : (desc->flip_colors == 0);
-    a.colour_groups = (int)((N + 1023) / 1024);
-    hipLaunchKernelGGL(jpeg_finish_kernel, dim3(2 * a.colour_groups), dim3(256), 0, d->stream, a);
-    HIPCHK(ctx, hipGetLastError());
-    if (d->timing) { HIPCHK(ctx, hipEventRecord(d->tev[slot][2], d->stream)); d->timed[slot] = true; }
+    const bool swap = desc->color_kind == CF_FRAME_COLOR_RAW ? (desc->flip_colors != 0) : (desc->flip_colors == 0);
+    if (int r = frame_decoder_colour(d, slot, desc->width, desc->height, desc->color_kind, swap, true)) return r;
+    image_ext_clear_mask(d->img, slot);   // a .klg frame has no mask: cf_frame_decoder_acquire_mask answers NULL for it
     HIPCHK(ctx, hipEventRecord(d->done[slot], d->stream));
     d->submitted[slot] = true;
     return CF_OK;

@@ -9,6 +9,8 @@
 
 
 #include "CoFusion.h"
+#include "ImageIO.h"
+#include "ImagePlayer.h"
 #include "KlgIO.h"
 #include "KlgPlayer.h"
 
@@ -479,5 +481,256 @@ int cofusion_klg_prefetch_next(cofusion_klg_prefetcher* q, int64_t* ts, int* col
 }
 int cofusion_klg_prefetch_rewind(cofusion_klg_prefetcher* q) { if (!q) return -1; q->held = -1; q->p->rewind(); return 0; }
 void cofusion_klg_prefetch_close(cofusion_klg_prefetcher* q) { delete q; }
+
+// ---- image-sequence datasets: the serial reader and the parsers alone (no GPU) ----
+struct cofusion_image_reader {
+    imageio::ImageSequenceReader r;
+    explicit cofusion_image_reader(const imageio::SequenceOptions& o) : r(o) {}
+};
+static imageio::SequenceOptions image_options(const cofusion_image_options* o)
+{
+    imageio::SequenceOptions s;
+    auto str = [](const char* c) { return std::string(c ? c : ""); };
+    s.colorDir = str(o->color_dir); s.depthDir = str(o->depth_dir); s.maskDir = str(o->mask_dir);
+    s.colorPrefix = str(o->color_prefix); s.depthPrefix = str(o->depth_prefix); s.maskPrefix = str(o->mask_prefix);
+    s.indexWidth = o->index_width > 0 ? o->index_width : 4;
+    s.startIndex = o->start_index;
+    s.flipColors = o->flip_colors != 0;
+    if (o->depth_scale > 0) s.depthScale = o->depth_scale;
+    if (o->rate_hz > 0) s.rateHz = o->rate_hz;
+    s.maxMasks = o->max_masks > 0 ? o->max_masks : 0;
+    return s;
+}
+int cofusion_image_reader_open(const cofusion_image_options* opt, cofusion_image_reader** out, cofusion_image_info* info)
+{
+    if (!opt || !out || !opt->color_dir) { g_err = "cofusion_image_reader_open: bad arguments"; return -1; }
+    cofusion_image_reader* r = nullptr;
+    GUARD(r = new cofusion_image_reader(image_options(opt)));
+    if (!r->r.ok()) { g_err = r->r.error(); delete r; return -1; }
+    if (info) {
+        const imageio::SequenceLayout& l = r->r.layout();
+        *info = cofusion_image_info{r->r.width(), r->r.height(), l.numFrames, l.startIndex, l.hasMasks ? 1 : 0, l.maxMasks};
+    }
+    *out = r;
+    return 0;
+}
+int cofusion_image_reader_next(cofusion_image_reader* r, int64_t* ts, float* depth_m, uint8_t* rgb, uint8_t* mask, int* has_mask)
+{
+    if (!r || !depth_m || !rgb) { g_err = "cofusion_image_reader_next: bad arguments"; return -1; }
+    if (!r->r.hasMore()) return 1;
+    bool ok = false;
+    GUARD(ok = r->r.next(ts, depth_m, rgb, mask, has_mask));
+    if (!ok) { g_err = r->r.error(); return -1; }
+    return 0;
+}
+int cofusion_image_reader_rewind(cofusion_image_reader* r) { if (!r) return -1; r->r.rewind(); return 0; }
+void cofusion_image_reader_close(cofusion_image_reader* r) { delete r; }
+
+struct cofusion_image_player {
+    ImageSequencePlayer p;
+    cofusion_image_player(CoFusion& cf, const imageio::SequenceOptions& o, int w) : p(cf, o, w) {}
+};
+static void fill_info(cofusion_image_info* info, const imageio::SequenceLayout& l, int w, int h)
+{
+    if (info) *info = cofusion_image_info{w, h, l.numFrames, l.startIndex, l.hasMasks ? 1 : 0, l.maxMasks};
+}
+int cofusion_image_player_open(cofusion_handle* h, const cofusion_image_options* opt, int workers, cofusion_image_player** out, cofusion_image_info* info)
+{
+    if (!h || !opt || !opt->color_dir || !out) { g_err = "cofusion_image_player_open: bad arguments"; return -1; }
+    if (h->borrowed) { g_err = "the image player is not available for a sequence of a lock-step group"; return -1; }
+    GUARD(*out = new cofusion_image_player(*h->cf, image_options(opt), workers > 0 ? workers : 4));
+    fill_info(info, (*out)->p.layout(), h->cf->cfg.width, h->cf->cfg.height);
+    return 0;
+}
+int cofusion_image_player_next(cofusion_image_player* p, int64_t* ts, const float** depth_dev, const uint8_t** rgba_dev, const uint8_t** mask_dev)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    bool more = false;
+    GUARD(more = p->p.next(ts, depth_dev, rgba_dev, mask_dev));
+    return more ? 0 : 1;
+}
+int cofusion_image_player_process(cofusion_image_player* p)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    bool more = false;
+    GUARD(more = p->p.process());
+    return more ? 0 : 1;
+}
+int cofusion_image_player_rewind(cofusion_image_player* p)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    GUARD(p->p.rewind());
+    return 0;
+}
+int cofusion_image_player_set_limits(cofusion_image_player* p, int frame_limit)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    p->p.setLimits(frame_limit);
+    return 0;
+}
+int cofusion_image_player_times(cofusion_image_player* p, double* read_s, double* inflate_s, double* unfilter_s, double* parse_s)
+{
+    if (!p) { g_err = "null player"; return -1; }
+    const imageio::DecodeTimes t = p->p.times();
+    if (read_s) *read_s = t.read;
+    if (inflate_s) *inflate_s = t.inflate;
+    if (unfilter_s) *unfilter_s = t.unfilter;
+    if (parse_s) *parse_s = t.parse;
+    return 0;
+}
+void cofusion_image_player_close(cofusion_image_player* p) { delete p; }
+
+struct cofusion_image_prefetcher {
+    std::vector<std::vector<uint8_t>> store;
+    std::vector<ImageSlotMem> mem;
+    ImagePrefetcher* p = nullptr;
+    int width = 0, height = 0, held = -1;
+    ~cofusion_image_prefetcher() { delete p; }
+};
+int cofusion_image_prefetch_open(const cofusion_image_options* opt, int workers, int slots, cofusion_image_prefetcher** out, cofusion_image_info* info)
+{
+    if (!opt || !opt->color_dir || !out || slots < 2 || slots > 64) { g_err = "cofusion_image_prefetch_open: bad arguments"; return -1; }
+    imageio::SequenceLayout lay;
+    int w = 0, h = 0;
+    {
+        imageio::ImageSequenceReader probe(image_options(opt));
+        if (!probe.ok()) { g_err = probe.error(); return -1; }
+        lay = probe.layout(); w = probe.width(); h = probe.height();
+    }
+    auto* q = new cofusion_image_prefetcher();
+    q->width = w; q->height = h;
+    const size_t N = (size_t)w * h, blocks = (size_t)CF_JPEG_MAX_BLOCKS(w, h);
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t offCoef = 512, offRgb = offCoef + blocks * 128, offColor = offRgb + up(N * 3), colorBytes = (1 + 4 * (size_t)w) * h,
+                 offDepth = offColor + up(colorBytes), depthBytes = 16 * N, offMask = offDepth + up(depthBytes), maskBytes = (1 + (size_t)w) * h,
+                 offPal = offMask + up(maskBytes), offBlocks = offPal + 768, total = offBlocks + (size_t)h * sizeof(cf_exr_block);
+    for (int s = 0; s < slots; s++) {
+        q->store.emplace_back(total);
+        uint8_t* b = q->store.back().data();
+        ImageSlotMem m;
+        m.frame = cf_frame_slot{reinterpret_cast<cf_jpeg_header*>(b), reinterpret_cast<int16_t*>(b + offCoef), blocks, nullptr, b + offRgb};
+        m.image.color = b + offColor; m.image.color_bytes = colorBytes; m.image.depth = b + offDepth; m.image.depth_bytes = depthBytes;
+        m.image.mask = b + offMask; m.image.mask_bytes = maskBytes; m.image.palette = b + offPal;
+        m.image.blocks = reinterpret_cast<cf_exr_block*>(b + offBlocks); m.image.max_blocks = (uint32_t)h;
+        q->mem.push_back(m);
+    }
+    q->p = new ImagePrefetcher(lay, w, h, q->mem, workers > 0 ? workers : 4);
+    fill_info(info, lay, w, h);
+    *out = q;
+    return 0;
+}
+int cofusion_image_prefetch_next(cofusion_image_prefetcher* q, int64_t* ts, float* depth_m, uint8_t* rgba, uint8_t* mask, int* has_mask)
+{
+    if (!q || !depth_m || !rgba) { g_err = "cofusion_image_prefetch_next: bad arguments"; return -1; }
+    if (q->held >= 0) { q->p->release(q->held); q->held = -1; }
+    if (!q->p->hasMore()) return 1;
+    ImageFrame f;
+    if (!q->p->next(&f)) { g_err = q->p->error(); return -1; }
+    q->held = f.slot;
+    const ImageSlotMem& m = q->mem[(size_t)f.slot];
+    const cf_image_desc& d = f.desc;
+    const size_t N = (size_t)q->width * q->height;
+    imageio::PngInfo pi;
+    pi.width = d.width; pi.height = d.height;
+    // the device's kernels, stated on the host
+    if (d.color_kind == CF_IMAGE_PNG) {
+        pi.bitDepth = 8; pi.colorType = d.png_color_type; pi.bpp = pi.colorType == 2 ? 3 : (pi.colorType == 6 ? 4 : 1); pi.paletteEntries = d.png_palette_entries;
+        imageio::pngColorFinishHost(pi, m.image.color, m.image.palette, d.flip_colors != 0, rgba);
+    } else {
+        std::vector<uint8_t> rgb;
+        const uint8_t* src = m.frame.rgb;
+        if (d.color_kind == CF_IMAGE_JPEG) { rgb.resize(N * 3); jpegFinishHost(m.frame.header, m.frame.coef, rgb.data()); src = rgb.data(); }
+        for (size_t k = 0; k < N; k++) {
+            rgba[4 * k + 0] = src[3 * k + (d.flip_colors ? 2 : 0)]; rgba[4 * k + 1] = src[3 * k + 1];
+            rgba[4 * k + 2] = src[3 * k + (d.flip_colors ? 0 : 2)]; rgba[4 * k + 3] = 255;
+        }
+    }
+    if (d.depth_kind == CF_IMAGE_PNG) {
+        pi.bitDepth = 16; pi.colorType = 0; pi.bpp = 2;
+        imageio::pngDepthFinishHost(pi, m.image.depth, d.depth_scale, depth_m);
+    } else {
+        imageio::ExrInfo x;
+        x.width = d.width; x.height = d.height; x.linesPerBlock = d.exr_lines_per_block; x.blocks = d.exr_blocks; x.lineBytes = d.exr_line_bytes;
+        x.chanOffset = d.exr_chan_offset; x.chanHalf = d.exr_chan_half;
+        imageio::exrFinishHost(x, m.image.depth, m.image.blocks, depth_m);
+    }
+    if (has_mask) *has_mask = d.mask_kind != CF_IMAGE_NONE;
+    if (mask && d.mask_kind == CF_IMAGE_PNG) { pi.bitDepth = 8; pi.colorType = 0; pi.bpp = 1; imageio::pngMaskFinishHost(pi, m.image.mask, mask); }
+    else if (mask && d.mask_kind == CF_IMAGE_RAW) memcpy(mask, m.image.mask, N);
+    if (ts) *ts = f.timestamp;
+    return 0;
+}
+int cofusion_image_prefetch_rewind(cofusion_image_prefetcher* q) { if (!q) return -1; q->held = -1; q->p->rewind(); return 0; }
+void cofusion_image_prefetch_close(cofusion_image_prefetcher* q) { delete q; }
+
+static imageio::PngInfo png_info(const cofusion_png_info* i)
+{
+    imageio::PngInfo p;
+    p.width = i->width; p.height = i->height; p.bitDepth = i->bit_depth; p.colorType = i->color_type; p.bpp = i->bpp; p.paletteEntries = i->palette_entries;
+    return p;
+}
+int cofusion_png_decode(const uint8_t* data, uint64_t size, int role, cofusion_png_info* info, uint8_t* scan, uint64_t cap, uint8_t* palette)
+{
+    if (!data || !info || !scan || role < 0 || role > 2 || (role == 0 && !palette)) { g_err = "cofusion_png_decode: bad arguments"; return -1; }
+    imageio::PngInfo p;
+    std::string e;
+    GUARD(e = imageio::pngDecode(data, (size_t)size, (imageio::Role)role, &p, scan, (size_t)cap, palette));
+    if (!e.empty()) { g_err = e; return -1; }
+    *info = cofusion_png_info{p.width, p.height, p.bitDepth, p.colorType, p.bpp, p.paletteEntries};
+    return 0;
+}
+int cofusion_png_finish_host(const cofusion_png_info* info, int role, const uint8_t* scan, const uint8_t* palette, int flip, float depth_scale, void* out)
+{
+    if (!info || !scan || !out || role < 0 || role > 2 || info->width < 1 || info->height < 1) { g_err = "cofusion_png_finish_host: bad arguments"; return -1; }
+    const imageio::PngInfo p = png_info(info);
+    const bool colour = p.bitDepth == 8 && ((p.colorType == 0 && p.bpp == 1) || (p.colorType == 2 && p.bpp == 3) || (p.colorType == 6 && p.bpp == 4) ||
+                                            (p.colorType == 3 && p.bpp == 1 && palette && p.paletteEntries >= 1 && p.paletteEntries <= 256));
+    if (role == 0 ? !colour : (p.colorType != 0 || p.bitDepth != (role == 1 ? 16 : 8) || p.bpp != (role == 1 ? 2 : 1))) {
+        g_err = "cofusion_png_finish_host: the description does not fit the role";
+        return -1;
+    }
+    if (role == 0) imageio::pngColorFinishHost(p, scan, palette, flip != 0, static_cast<uint8_t*>(out));
+    else if (role == 1) imageio::pngDepthFinishHost(p, scan, depth_scale, static_cast<float*>(out));
+    else imageio::pngMaskFinishHost(p, scan, static_cast<uint8_t*>(out));
+    return 0;
+}
+int cofusion_exr_decode(const uint8_t* data, uint64_t size, cofusion_exr_info* info, uint8_t* raw, uint64_t cap, cf_exr_block* blocks, uint64_t max_blocks)
+{
+    if (!data || !info || !raw || !blocks) { g_err = "cofusion_exr_decode: bad arguments"; return -1; }
+    imageio::ExrInfo x;
+    std::string e;
+    GUARD(e = imageio::exrDecode(data, (size_t)size, &x, raw, (size_t)cap, blocks, (size_t)max_blocks));
+    if (!e.empty()) { g_err = e; return -1; }
+    *info = cofusion_exr_info{x.width, x.height, x.compression, x.linesPerBlock, x.blocks, x.lineBytes, x.chanOffset, x.chanHalf};
+    return 0;
+}
+int cofusion_exr_finish_host(const cofusion_exr_info* info, const uint8_t* raw, const cf_exr_block* blocks, float* depth)
+{
+    if (!info || !raw || !blocks || !depth) { g_err = "cofusion_exr_finish_host: bad arguments"; return -1; }
+    imageio::ExrInfo x;
+    x.width = info->width; x.height = info->height; x.compression = info->compression; x.linesPerBlock = info->lines_per_block; x.blocks = info->blocks;
+    x.lineBytes = info->line_bytes; x.chanOffset = info->chan_offset; x.chanHalf = info->chan_half;
+    // the table decides addresses: check it as cf_frame_decoder_submit_images does
+    const int sample = x.chanHalf ? 2 : 4;
+    bool ok = x.width >= 1 && x.height >= 1 && x.blocks >= 1 && x.lineBytes >= 1 && x.chanOffset >= 0 &&
+              (int64_t)x.chanOffset + (int64_t)x.width * sample <= x.lineBytes;
+    for (int i = 0; ok && i < x.blocks; i++) {
+        const cf_exr_block& b = blocks[i];
+        ok = b.bytes >= (uint32_t)x.lineBytes && b.bytes % (uint32_t)x.lineBytes == 0 && b.offset == (uint64_t)b.first_line * x.lineBytes &&
+             (uint64_t)b.first_line + b.bytes / (uint32_t)x.lineBytes <= (uint64_t)x.height;
+    }
+    if (!ok) { g_err = "cofusion_exr_finish_host: the block table does not describe a frame of this size"; return -1; }
+    GUARD(imageio::exrFinishHost(x, raw, blocks, depth));
+    return 0;
+}
+int cofusion_ppm_decode(const uint8_t* data, uint64_t size, int* width, int* height, uint64_t* pixel_offset)
+{
+    if (!data || !width || !height || !pixel_offset) { g_err = "cofusion_ppm_decode: bad arguments"; return -1; }
+    const uint8_t* px = nullptr;
+    const std::string e = imageio::ppmDecode(data, (size_t)size, width, height, &px);
+    if (!e.empty()) { g_err = e; return -1; }
+    *pixel_offset = (uint64_t)(px - data);
+    return 0;
+}
 
 }  // extern "C"

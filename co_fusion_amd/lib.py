@@ -35,6 +35,7 @@ SYMBOLS = [
     "cf_ferns_table", "cf_ferns_create", "cf_ferns_destroy", "cf_ferns_get_table", "cf_ferns_encode", "cf_ferns_search", "cf_ferns_append", "cf_ferns_add_async",
     "cf_ferns_relocalise", "cf_ferns_count", "cf_ferns_download", "cf_ferns_last_search",
     "cf_frame_decoder_create", "cf_frame_decoder_destroy", "cf_frame_decoder_slot", "cf_frame_decoder_submit", "cf_frame_decoder_acquire", "cf_frame_decoder_timing",
+    "cf_frame_decoder_enable_images", "cf_frame_decoder_image_slot", "cf_frame_decoder_submit_images", "cf_frame_decoder_acquire_mask", "cf_frame_decoder_image_timing",
 ]
 
 
@@ -62,6 +63,11 @@ HOST_SYMBOLS = [
     "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_relocalisation", "cofusion_reloc_stats",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",
+    "cofusion_image_reader_open", "cofusion_image_reader_next", "cofusion_image_reader_rewind", "cofusion_image_reader_close",
+    "cofusion_image_player_open", "cofusion_image_player_next", "cofusion_image_player_process", "cofusion_image_player_rewind", "cofusion_image_player_set_limits",
+    "cofusion_image_player_times", "cofusion_image_player_close",
+    "cofusion_image_prefetch_open", "cofusion_image_prefetch_next", "cofusion_image_prefetch_rewind", "cofusion_image_prefetch_close",
+    "cofusion_png_decode", "cofusion_png_finish_host", "cofusion_exr_decode", "cofusion_exr_finish_host", "cofusion_ppm_decode",
 ]
 _host = None
 

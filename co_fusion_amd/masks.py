@@ -1,5 +1,5 @@
 """Label masks from files: binary PGM (P5, maxval <= 255), one of the mask formats the reference accepts for its pre-processed
-segmentation input (Mask####.png / .pgm).  PNG is not read here: the project has no PNG reader."""
+segmentation input (Mask####.png / .pgm).  read_mask also takes 8-bit grey PNG, through the host library's reader (images.py)."""
 from __future__ import annotations
 
 import os
@@ -46,6 +46,17 @@ def parse_pgm(data: bytes) -> np.ndarray:
 def read_pgm(path: str) -> np.ndarray:
     with open(path, "rb") as f:
         return parse_pgm(f.read())
+
+
+def read_mask(path: str) -> np.ndarray:
+    """a label mask by its extension: .pgm (parse_pgm) or .png (8-bit grey, images.read_mask_png: the host library's PNG reader)"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".pgm":
+        return read_pgm(path)
+    if ext == ".png":
+        from . import images
+        return images.read_mask_png(path)
+    raise ValueError(f"{path}: label masks are .pgm or .png files")
 
 
 def mask_path(directory: str, index: int, prefix: str = "Mask", index_width: int = 4) -> str:

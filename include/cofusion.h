@@ -233,6 +233,75 @@ int cofusion_klg_prefetch_next(cofusion_klg_prefetcher *p, int64_t *timestamp, i
 int cofusion_klg_prefetch_rewind(cofusion_klg_prefetcher *p);
 void cofusion_klg_prefetch_close(cofusion_klg_prefetcher *p);
 
+/* Image-sequence datasets (host/ImageIO.h; GUI/Tools/ImageLogReader.cpp): a directory of colour .jpg/.png/.ppm, depth
+ * .exr/.png and optional mask .png/.pgm files, <prefix><index, zero-padded to index_width><ext>.  Host-only code, usable without a GPU.
+ * Empty depth_dir / mask_dir: the colour directory; directories that overlap without distinct prefixes take "Color", "Depth", "Mask".
+ * Colour and depth counts must agree, and mask counts with them where masks exist.  start_index < 0: the first of 0, 1 that exists.
+ * flip_colors 0 delivers the file's R, G, B (what the reference's reader hands on), 1 reverses them.  depth_scale turns 16-bit PNG depth
+ * into metres with one f32 product (<= 0: the reference's 0.0006f; 0.001 for millimetre data, 0.0002 for TUM's 5000 per metre); EXR depth
+ * is passed on as the file has it.  rate_hz <= 0: 24; timestamp = int64(f32(frame) * 1000.0f / rate_hz). */
+typedef struct {
+    const char *color_dir, *depth_dir, *mask_dir;
+    const char *color_prefix, *depth_prefix, *mask_prefix;   /* each nullable = "" */
+    int32_t index_width, start_index, flip_colors;
+    float depth_scale, rate_hz;
+    int32_t max_masks;   /* > 0: masks are read for the first so many frames only (the reference's maxMasks, which its own count rule
+                          * keeps at the frame count); 0: for every frame that has a mask file */
+} cofusion_image_options;
+typedef struct { int32_t width, height, num_frames, start_index, has_masks, max_masks; } cofusion_image_info;
+/* The serial reader: every file is read and decoded on the calling thread.  _next: depth_m [H*W], rgb [H*W*3], mask [H*W] (nullable);
+ * *has_mask 0 for a frame without one (masks stop after max_masks frames).  0, 1 at the end, -1 on error (the message names the file). */
+typedef struct cofusion_image_reader cofusion_image_reader;
+int cofusion_image_reader_open(const cofusion_image_options *opt, cofusion_image_reader **out, cofusion_image_info *info);
+int cofusion_image_reader_next(cofusion_image_reader *r, int64_t *timestamp, float *depth_m, uint8_t *rgb, uint8_t *mask, int *has_mask);
+int cofusion_image_reader_rewind(cofusion_image_reader *r);
+void cofusion_image_reader_close(cofusion_image_reader *r);
+/* The image player (host/ImagePlayer.h), the counterpart of cofusion_klg_player_* for a directory: worker threads read
+ * the files ahead (read, inflate, PNG unfilter, JPEG entropy decoding) into the pinned slots of a cf_frame_decoder with images enabled,
+ * the device finishes the frames (csrc/image_decode.hip), and they go into cofusion_process_frame_device_masked where the frame has a
+ * mask, into cofusion_process_frame_device otherwise -- the frames cofusion_image_reader_next delivers, byte for byte.  The set's frames
+ * must have the instance's size.  workers 1..16 (<= 0: 4).  Refused for world > 1 and for a sequence handle of a lock-step group; close
+ * the player before its instance.  _next / _process: 0, 1 at the end of the set, -1 on error (a frame that cannot be decoded fails at
+ * its position, with a message that names the file; the frames before it are played).  _next: the frame's device buffers (depth f32
+ * [H*W], rgba u8x4 [H*W], mask u8 [H*W] or NULL), complete or ordered on the instance's stream as device_frames_complete says, intact
+ * until the next call on this player.  _set_limits: frame_limit >= 0 plays at most so many frames.  _times: seconds the workers spent
+ * so far, all workers summed: reading files, inside zlib's inflate(), in the PNG unfilter loop, and in the rest of the parsers (chunk
+ * walk, CRC-32, headers, copies of raw EXR blocks). */
+typedef struct cofusion_image_player cofusion_image_player;
+int cofusion_image_player_open(cofusion_handle *h, const cofusion_image_options *opt, int workers, cofusion_image_player **out,
+                               cofusion_image_info *info);
+int cofusion_image_player_next(cofusion_image_player *p, int64_t *timestamp, const float **depth_dev, const uint8_t **rgba_dev,
+                               const uint8_t **mask_dev);
+int cofusion_image_player_process(cofusion_image_player *p);
+int cofusion_image_player_rewind(cofusion_image_player *p);
+int cofusion_image_player_set_limits(cofusion_image_player *p, int frame_limit);
+int cofusion_image_player_times(cofusion_image_player *p, double *read_s, double *inflate_s, double *unfilter_s, double *parse_s);
+void cofusion_image_player_close(cofusion_image_player *p);
+/* Test access to the host half of the player, usable without a GPU: the prefetcher over slots from malloc.  _next delivers the next
+ * frame in order, FINISHED ON THE HOST by the host statements of the device's kernels, into the caller's buffers (depth_m [H*W], rgba
+ * [H*W*4], mask [H*W] nullable; *has_mask): what the player's device frames must equal.  0, 1 at the end, -1 on error. */
+typedef struct cofusion_image_prefetcher cofusion_image_prefetcher;
+int cofusion_image_prefetch_open(const cofusion_image_options *opt, int workers, int slots, cofusion_image_prefetcher **out,
+                                 cofusion_image_info *info);
+int cofusion_image_prefetch_next(cofusion_image_prefetcher *p, int64_t *timestamp, float *depth_m, uint8_t *rgba, uint8_t *mask, int *has_mask);
+int cofusion_image_prefetch_rewind(cofusion_image_prefetcher *p);
+void cofusion_image_prefetch_close(cofusion_image_prefetcher *p);
+/* The parsers alone.  role: 0 colour (8-bit grey / RGB / palette / RGBA), 1 depth (16-bit grey), 2 mask (8-bit grey).
+ * _png_decode: non-interlaced PNG -> unfiltered scanlines in file layout (row stride 1 + bpp * width, 16-bit big-endian) in scan[cap],
+ * the palette (768 bytes, nullable unless colour) beside it.  _exr_decode: single-part scanline OpenEXR (NONE / ZIPS / ZIP; HALF /
+ * FLOAT) -> the inflated blocks in raw[cap] and their table (max_blocks >= height always suffices).  _ppm_decode: binary P6 -> where the
+ * pixels start.  The _finish_host entries are the host statements of csrc/image_decode.hip: role 0 -> out = rgba u8x4, 1 -> f32
+ * depth, 2 -> u8 mask.  0, or -1 with the reason in cofusion_last_error(). */
+typedef struct { int32_t width, height, bit_depth, color_type, bpp, palette_entries; } cofusion_png_info;
+typedef struct { int32_t width, height, compression, lines_per_block, blocks, line_bytes, chan_offset, chan_half; } cofusion_exr_info;
+int cofusion_png_decode(const uint8_t *data, uint64_t size, int role, cofusion_png_info *info, uint8_t *scan, uint64_t cap, uint8_t *palette);
+int cofusion_png_finish_host(const cofusion_png_info *info, int role, const uint8_t *scan, const uint8_t *palette, int flip_colors,
+                             float depth_scale, void *out);
+int cofusion_exr_decode(const uint8_t *data, uint64_t size, cofusion_exr_info *info, uint8_t *raw, uint64_t cap, cf_exr_block *blocks,
+                        uint64_t max_blocks);
+int cofusion_exr_finish_host(const cofusion_exr_info *info, const uint8_t *raw, const cf_exr_block *blocks, float *depth);
+int cofusion_ppm_decode(const uint8_t *data, uint64_t size, int *width, int *height, uint64_t *pixel_offset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -729,6 +729,54 @@ int cf_frame_decoder_acquire(cf_frame_decoder *dec, int slot, int complete, cons
  * diagnostics mode that adds event pairs to every submit); reading waits for the decoder's stream and resets the sums */
 int cf_frame_decoder_timing(cf_frame_decoder *dec, int on, double *idct_ms, double *finish_ms, uint64_t *frames);
 
+/* ---- image-sequence frames on the same decoder (csrc/image_decode.hip) ----
+ * Frames of a directory dataset (PNG / OpenEXR / JPEG / PPM / PGM files): host threads read, inflate and PNG-unfilter into the image
+ * staging of a slot (host/ImageIO.cpp), the device turns that into the same output frame cf_frame_decoder_acquire hands out, plus a
+ * u8 label mask.  Opt-in: a decoder on which cf_frame_decoder_enable_images was never called allocates nothing for it. */
+#define CF_IMAGE_NONE 0   /* colour: RGBA = 0, 0, 0, 255; depth: 0; mask: the frame has none */
+#define CF_IMAGE_PNG 1    /* unfiltered scanlines in file layout: row stride 1 + bytes_per_pixel * width (the filter byte stays),
+                           * 16-bit samples big-endian.  colour: 8-bit grey / RGB / palette / RGBA; depth: 16-bit grey; mask: 8-bit grey */
+#define CF_IMAGE_EXR 2    /* depth only: inflated blocks in cf_image_slot.depth + the table in cf_image_slot.blocks */
+#define CF_IMAGE_JPEG 3   /* colour only: header + coef of cf_frame_decoder_slot (the .klg path's kernels; R, G, B unless flip_colors) */
+#define CF_IMAGE_RAW 4    /* colour: 3 B/px in cf_frame_slot.rgb (PPM; R, G, B unless flip_colors); mask: 1 B/px in cf_image_slot.mask (PGM) */
+/* one block of scanlines of an OpenEXR file as it lies in cf_image_slot.depth.  stored_raw: the file kept the block uncompressed
+ * (deflate did not shrink it): the bytes are the pixels, with neither predictor nor interleave to undo */
+typedef struct { uint32_t offset, bytes, stored_raw, first_line; } cf_exr_block;
+typedef struct {
+    int32_t width, height;            /* 1..max of the decoder */
+    int32_t color_kind, depth_kind, mask_kind;   /* CF_IMAGE_* */
+    int32_t flip_colors;              /* store B, G, R instead of the file's R, G, B */
+    int32_t png_color_type;           /* colour PNG: 0 grey, 2 RGB, 3 palette, 6 RGBA */
+    int32_t png_palette_entries;      /* colour type 3: 1..256 entries of 3 bytes in cf_image_slot.palette */
+    float depth_scale;                /* 16-bit PNG depth: metres = f32(u16) * depth_scale, one f32 product */
+    int32_t exr_blocks;               /* entries of cf_image_slot.blocks */
+    int32_t exr_lines_per_block;      /* 1 (NONE, ZIPS) or 16 (ZIP) */
+    int32_t exr_line_bytes;           /* all channels of one scanline */
+    int32_t exr_chan_offset;          /* where the depth channel's run of `width` samples starts inside a scanline */
+    int32_t exr_chan_half;            /* 1: HALF, 0: FLOAT */
+} cf_image_desc;
+typedef struct {                      /* pinned host staging of one slot, beside cf_frame_slot's */
+    uint8_t *color;  uint64_t color_bytes;    /* (1 + 4 * max_w) * max_h */
+    uint8_t *depth;  uint64_t depth_bytes;    /* 16 * max_w * max_h: a PNG's (1 + 2w) * h, or up to four FLOAT channels of an EXR */
+    uint8_t *mask;   uint64_t mask_bytes;     /* (1 + max_w) * max_h */
+    uint8_t *palette;                         /* 768 */
+    cf_exr_block *blocks;  uint32_t max_blocks;   /* max_h */
+} cf_image_slot;
+/* allocates, once, the image staging of every slot (pinned), its device mirror and a u8 mask frame per slot */
+int cf_frame_decoder_enable_images(cf_frame_decoder *dec);
+int cf_frame_decoder_image_slot(cf_frame_decoder *dec, int slot, cf_image_slot *out);
+/* cf_frame_decoder_submit for an image frame: same stream, event and ordering rules.  Everything the kernels index with (row strides,
+ * the block table, the channel's place) is checked against the slot's sizes first; nothing is launched on an inconsistent frame. */
+int cf_frame_decoder_submit_images(cf_frame_decoder *dec, int slot, const cf_image_desc *desc);
+/* the mask frame (u8 [H*W]) of the slot's last frame, ordered like cf_frame_decoder_acquire; *mask_dev is
+ * NULL where the slot's last frame had no mask (a .klg frame submitted with cf_frame_decoder_submit has none) */
+int cf_frame_decoder_acquire_mask(cf_frame_decoder *dec, int slot, int complete, const uint8_t **mask_dev);
+/* Device-event durations of the two image kernels, accumulated over the image frames submitted while cf_frame_decoder_timing is on
+ * (the same diagnostics mode: the slot's event pairs lie around exr_depth_kernel and around png_finish_kernel, every copy in front
+ * of them): the sums in milliseconds and how many frames launched each kernel.  Reading waits for the decoder's stream and resets
+ * the sums; the .klg sums of cf_frame_decoder_timing are kept apart and count no image frame. */
+int cf_frame_decoder_image_timing(cf_frame_decoder *dec, double *exr_ms, uint64_t *exr_frames, double *finish_ms, uint64_t *finish_frames);
+
 /* micro-benchmark of the ICP reduction on the state of the last tracking call (level 0..2) */
 int cf_odom_bench_icp(cf_odom *od, int level, int iters, float *avg_us);
 

@@ -13,7 +13,18 @@ worker threads and finishes the frames on the device (klg.KlgPlayer) instead of 
 same frames, the same outputs.  --mask-dir feeds the reference's pre-processed segmentation (one label mask per frame, <prefix><index>.pgm,
 binary PGM with maxval <= 255; the numbering starts at 0 or 1, whichever file exists) instead of running the motion segmentation: with the
 serial reader through the host entry, with --player through player iteration and the masked device entry (mask uploaded, frame on the
-device).  A frame without a mask file runs the motion segmentation."""
+device).  A frame without a mask file runs the motion segmentation.  Masks may be .pgm or 8-bit grey .png files.
+
+The positional `log` may also be a DIRECTORY of image files as the reference's `-dir` reads them (co_fusion_amd/images.py:
+colour <prefix><index>.jpg/.png/.ppm, depth .exr/.png, masks .png/.pgm):
+
+    python tools/run_klg.py car4/ out/ [--depth-dir DIR --mask-dir DIR] [--color-prefix Color --depth-prefix Depth --mask-prefix Mask]
+                            [--index-width 4] [--start-index N] [--depth-scale 0.001]
+
+The frame size is the first colour file's (--width / --height are ignored); the files are read by the serial reader
+(images.ImageSequenceReader) and the frames go through the host entry, masks included where the set has them.  With --player worker
+threads read, inflate and unfilter ahead and the device finishes the frames (images.ImageSequencePlayer): the same frames, the same
+outputs."""
 import argparse
 import os
 import sys
@@ -44,14 +55,36 @@ def main():
     ap.add_argument("--fern-seed", type=int, default=0)
     ap.add_argument("--player", action="store_true", help="threaded prefetch + JPEG finished on the device (default: the serial reader)")
     ap.add_argument("--workers", type=int, default=4, help="host threads of --player (1..16)")
-    ap.add_argument("--mask-dir", default=None, help="directory of per-frame label masks (binary PGM)")
+    ap.add_argument("--mask-dir", default=None, help="directory of per-frame label masks (binary PGM or 8-bit grey PNG)")
+    ap.add_argument("--depth-dir", default=None, help="image directory: where the depth files are (default: the colour directory)")
+    ap.add_argument("--color-prefix", default=None, help="image directory: colour files are <prefix><index>.jpg/.png/.ppm")
+    ap.add_argument("--depth-prefix", default=None, help="image directory: depth files are <prefix><index>.exr/.png")
+    ap.add_argument("--start-index", type=int, default=-1, help="image directory: index of the first frame (default: 0 or 1, whichever exists)")
+    ap.add_argument("--depth-scale", type=float, default=0.0,
+                    help="image directory, 16-bit PNG depth: metres per unit (default: the reference's 0.0006; 0.001 for millimetre data, "
+                         "0.0002 for TUM's 5000 units per metre)")
     ap.add_argument("--mask-prefix", default="Mask")
     ap.add_argument("--index-width", type=int, default=4)
     a = ap.parse_args()
     from co_fusion_amd import facade, klg
     os.makedirs(a.outdir, exist_ok=True)
     prefix = a.outdir.rstrip("/") + "/"
-    log = None if a.player else klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
+    images_dir = os.path.isdir(a.log)
+    if images_dir:
+        from co_fusion_amd import images
+        # No prefix given: all three go in empty, and the reader applies the reference's rule ("Color" / "Depth" / "Mask" where the
+        # directories overlap, every file of its own directory otherwise).  Any prefix given: all three as given (--mask-prefix
+        # defaults to "Mask").
+        given = a.color_prefix is not None or a.depth_prefix is not None or a.mask_prefix != "Mask"
+        prefixes = (a.color_prefix or "", a.depth_prefix or "", a.mask_prefix) if given else ("", "", "")
+        where = (a.log, a.depth_dir or "", a.mask_dir or "") + prefixes
+        how_read = dict(index_width=a.index_width, start_index=a.start_index, flip_colors=a.flip_colors, depth_scale=a.depth_scale)
+        log = images.ImageSequenceReader(*where, **how_read)   # (with --player: the directory rules and the frame size)
+        a.width, a.height = log.width, log.height
+        if log.has_masks and a.static:
+            raise SystemExit("a dataset with masks needs the multi-model mode (no --static)")
+    else:
+        log = None if a.player else klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
     cf = facade.CoFusion(a.width, a.height, a.fx, a.fy, a.cx, a.cy, max_surfels=a.max_surfels, enable_multiple_models=int(not a.static),
                          enable_pose_logging=1, reloc=int(a.relocalise))
     if a.relocalise:
@@ -62,21 +95,31 @@ def main():
         cf.set_export_views(prefix, labels=a.export_labels, normals=a.export_normals, viewport=a.export_viewport)
     n, t0 = 0, time.perf_counter()
     mask_of = None
-    if a.mask_dir:
+    if a.mask_dir and not images_dir:
         from co_fusion_amd import masks
         if a.static:
             raise SystemExit("--mask-dir needs the multi-model mode (no --static)")
-        start = 0 if os.path.exists(masks.mask_path(a.mask_dir, 0, a.mask_prefix, a.index_width)) else 1
+        def find(i):
+            pgm = masks.mask_path(a.mask_dir, i, a.mask_prefix, a.index_width)
+            return next((p for p in (pgm, pgm[:-4] + ".png") if os.path.exists(p)), None)
+
+        start = 0 if find(0) else 1
 
         def mask_of(i):
-            path = masks.mask_path(a.mask_dir, i + start, a.mask_prefix, a.index_width)
-            if not os.path.exists(path):
+            path = find(i + start)
+            if path is None:
                 return None
-            m = masks.read_pgm(path)
+            m = masks.read_mask(path)
             if m.shape != (a.height, a.width):
                 raise SystemExit(f"{path}: {m.shape[1]}x{m.shape[0]}, the log is {a.width}x{a.height}")
             return m
-    if a.player and mask_of:
+    if a.player and images_dir:
+        log.close()
+        log = images.ImageSequencePlayer(cf, *where, workers=a.workers, **how_read)
+        log.set_limits(frame_limit=a.frames if a.frames > 0 else -1)
+        n = log.play()
+        log.close()
+    elif a.player and mask_of:
         import torch
         log = klg.KlgPlayer(cf, a.log, flip_colors=a.flip_colors, workers=a.workers)
         log.set_limits(frame_limit=a.frames if a.frames > 0 else -1)
@@ -91,6 +134,12 @@ def main():
         log.set_limits(frame_limit=a.frames if a.frames > 0 else -1)
         n = log.play()
         log.close()
+    elif images_dir:
+        for ts, depth, rgb, mask in log:
+            cf.process_frame(depth, rgb, mask=mask, timestamp=ts)
+            n += 1
+            if 0 < a.frames <= n:
+                break
     else:
         for ts, depth, rgb in log:
             cf.process_frame(depth, rgb, mask=mask_of(n) if mask_of else None, timestamp=ts)
@@ -98,7 +147,7 @@ def main():
             if 0 < a.frames <= n:
                 break
     dt = time.perf_counter() - t0
-    how = f"log player, {a.workers} workers" if a.player else "incl. log decoding and upload"
+    how = f"{'image' if images_dir else 'log'} player, {a.workers} workers" if a.player else ("incl. file decoding and upload" if images_dir else "incl. log decoding and upload")
     print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s {how}), {cf.num_models} active models")
     if a.relocalise:
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
