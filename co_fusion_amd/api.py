@@ -624,3 +624,71 @@ class FrameDecoder:
             self.close()
         except Exception:
             pass
+
+
+class PngBand(C.Structure):
+    _fields_ = [("offset", C.c_uint32), ("bytes", C.c_uint32), ("adler", C.c_uint32), ("stream_bytes", C.c_uint32)]
+
+
+class PngStream(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("rows_per_band", C.c_int32), ("bands", C.c_int32),
+                ("table", C.POINTER(PngBand)), ("data", C.POINTER(C.c_uint8)), ("data_bytes", C.c_uint64)]
+
+
+PNG_LABELS = 1
+
+
+class PngEncoder:
+    """cf_png_encoder (csrc/png_encode.hip): a device image (torch CUDA u8 [H, W] or [H, W, 4]) becomes the bands of a PNG data stream
+    in a pinned slot.  `submit` enqueues on the context's stream without a host wait; `acquire` waits for the slot and returns the
+    stream's description plus the bands as bytes objects with their (adler, stream_bytes) -- the host's part (chunk framing, CRC) is
+    host/ExportWriter.cpp's, or the caller's."""
+
+    def __init__(self, ctx: Context, max_w, max_h, slots=2, rows_per_band=8):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.lib.cf_png_encoder_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        self.lib.cf_png_encoder_destroy.argtypes = [C.c_void_p]
+        self.lib.cf_png_encoder_destroy.restype = None
+        self.lib.cf_png_encoder_submit.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        self.lib.cf_png_encoder_acquire.argtypes = [C.c_void_p, C.c_int, C.POINTER(PngStream)]
+        self.lib.cf_png_encoder_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        self.h = C.c_void_p()
+        ctx._check(self.lib.cf_png_encoder_create(ctx.h, int(max_w), int(max_h), int(slots), int(rows_per_band), C.byref(self.h)))
+
+    def submit(self, s, image, flags=0):
+        if image.dtype != torch.uint8 or not image.is_cuda or not image.is_contiguous() or image.dim() not in (2, 3):
+            raise CofusionError("PngEncoder.submit: a contiguous CUDA uint8 tensor [H, W] or [H, W, 4] is expected")
+        channels = 1 if image.dim() == 2 else int(image.shape[2])
+        self.submit_ptr(s, image.data_ptr(), int(image.shape[1]), int(image.shape[0]), channels, flags)
+
+    def submit_ptr(self, s, ptr, width, height, channels, flags=0):
+        self.ctx._check(self.lib.cf_png_encoder_submit(self.h, int(s), C.c_void_p(ptr), int(width), int(height), int(channels), int(flags)))
+
+    def acquire(self, s):
+        """(PngStream, [(bytes of the band, adler, stream_bytes)])"""
+        st = PngStream()
+        self.ctx._check(self.lib.cf_png_encoder_acquire(self.h, int(s), C.byref(st)))
+        bands = []
+        for k in range(st.bands):
+            b = st.table[k]
+            if b.offset + b.bytes > st.data_bytes:
+                raise CofusionError("PngEncoder.acquire: a band lies outside the slot")
+            bands.append((C.string_at(C.addressof(st.data.contents) + b.offset, b.bytes), int(b.adler), int(b.stream_bytes)))
+        return st, bands
+
+    def timing(self, on=True):
+        """(kernel ms, images) from device events accumulated while timing was on; resets the sums"""
+        a, n = C.c_double(), C.c_uint64()
+        self.ctx._check(self.lib.cf_png_encoder_timing(self.h, int(bool(on)), C.byref(a), C.byref(n)))
+        return a.value, n.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cf_png_encoder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

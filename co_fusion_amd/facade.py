@@ -251,6 +251,24 @@ class CoFusion:
         which = (1 if labels else 0) | (2 if normals else 0) | (4 if viewport else 0)
         self._check(self.lib.cofusion_set_export_views(self.h, str(prefix or "").encode(), which))
 
+    def set_export_async(self, on=True, workers=2, slots=8):
+        """the per-frame exports (set_export_segmentation, set_export_views) through the device PNG encoder and `workers` (1..8)
+        writer threads: same file names, numbering and pixels, no read-back or zlib on the frame thread.  The frame loop waits only
+        when all `slots` (2..16) are busy; a failed write raises from the next process_frame* or from export_flush."""
+        self._check(self.lib.cofusion_set_export_async(self.h, int(bool(on)), int(workers), int(slots)))
+
+    def export_flush(self):
+        """returns when every exported file submitted so far is closed"""
+        self._check(self.lib.cofusion_export_flush(self.h))
+
+    def export_stats(self, timing=False):
+        """dict(images, bytes, stalls, device_ms, device_images) of the asynchronous exports; timing: measure the encoding kernel with
+        device events from here on (device_ms / device_images cover the images since the last call)"""
+        im, by, stl, n = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ms = C.c_double()
+        self._check(self.lib.cofusion_export_stats(self.h, C.byref(im), C.byref(by), C.byref(stl), C.byref(ms), C.byref(n), int(bool(timing))))
+        return dict(images=im.value, bytes=by.value, stalls=stl.value, device_ms=ms.value, device_images=n.value)
+
     def export_poses(self, prefix):
         """CoFusion::exportPoses: <prefix>poses-<id>.txt per logged model (needs enable_pose_logging=1)"""
         n = self.lib.cofusion_export_poses(self.h, str(prefix).encode())

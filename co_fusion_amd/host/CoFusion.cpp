@@ -2,6 +2,7 @@
 // Core/Model/Model.cpp:319-406 and Core/Segmentation/Segmentation.cpp:59-706 on top of the C-ABI.
 // Compiled with -ffp-contract=off: the host arithmetic here is mirrored by the CPU oracle.
 #include "CoFusion.h"
+#include "ExportWriter.h"
 
 #include <algorithm>
 #include <chrono>
@@ -635,6 +636,7 @@ CoFusion::CoFusion(const Config& c, cf_ctx* shared, int sequenceIndex)
 
 CoFusion::~CoFusion()
 {
+    exportWriter.reset();   // writes what is in flight
     pool.reset();
     releaseRenderer();
     if (ferns) cf_ferns_destroy(ferns);
@@ -908,6 +910,7 @@ void CoFusion::exchangeTracking()
 //   frameEnd     clock, pose log
 void CoFusion::frameBegin(const FrameData& frame, const Mat4f* inPose, float weightMultiplier, bool bootstrap)
 {
+    if (exportWriter) exportWriter->check();   // a write of an earlier frame's export that failed is reported here
     st = FrameStage{};
     st.frame = &frame; st.inPose = inPose; st.weightMultiplier = weightMultiplier; st.bootstrap = bootstrap;
     if (frame.mask_dev && !(frame.rgba_dev && frame.depth_dev)) throw std::runtime_error("processFrame: a device mask comes with a device-resident frame");
@@ -1066,7 +1069,10 @@ void CoFusion::frameCollect()
             if (segOnDevice) seg = labelGenerator->finishCRF();
             else if (st.masksOnDevice) seg = labelGenerator->finishMasks();
             else seg = labelGenerator->performSegmentationGT(models, frame, getNextModelID(), allowNew, mask_dev);   // a host mask (frame.mask)
-            if (!exportSegmentationPrefix.empty()) {  // CoFusion.cpp:235-240: labels > 254 (rejected) are written as 0
+            if (!exportSegmentationPrefix.empty() && exportWriter) {   // (setExportAsync: the same image, encoded on the device)
+                exportWriter->submit(exportSegmentationPrefix + "Segmentation" + std::to_string(tick) + ".png", mask_dev, cfg.width, cfg.height, 1,
+                                     CF_PNG_LABELS);
+            } else if (!exportSegmentationPrefix.empty()) {  // CoFusion.cpp:235-240: labels > 254 (rejected) are written as 0
                 std::vector<uint8_t> labels(N);
                 check(ctx, cf_memcpy_d2h(ctx, labels.data(), mask_dev, N), "mask readback");
                 for (auto& v : labels) if (v > 254) v = 0;

@@ -241,6 +241,8 @@ class Segmentation {
     cf_seg_params deviceParams() const;   // (the group compares the sequences' settings: one batched chain per distinct set)
 };
 
+class ExportWriter;   // ExportWriter.h
+
 class CoFusion {
   public:
     struct Config {
@@ -313,6 +315,15 @@ class CoFusion {
     // which: 1 labels | 2 normals | 4 viewport; 0 switches it off.  One rasterisation feeds all three.
     enum { ExportLabels = 1, ExportNormals = 2, ExportViewport = 4 };
     void setExportViews(const std::string& prefix, int which);
+    // The per-frame exports (Segmentation<n>.png and the views) through the device PNG encoder and writer threads (ExportWriter.h,
+    // DESIGN.md 4.12) instead of a read-back and zlib on the calling thread: same file names, numbering and pixels, another (valid)
+    // PNG encoding.  Off by default.  The frame loop never waits for a file unless all `slots` (2..16) are busy; a failed write is
+    // thrown by the next frame or by exportFlush.  workers: 1..8 writer threads.  Switching it off writes what is in flight first.
+    void setExportAsync(bool on, int workers = 2, int slots = 8);
+    void exportFlush();   // returns when every submitted file is closed (a no-op without setExportAsync)
+    // images and bytes written, submits that found every slot busy; timing: the encoder's device events from here on (the sums are
+    // those since the last call).  All zero without setExportAsync.
+    void exportStats(uint64_t* images, uint64_t* bytes, uint64_t* stalls, double* deviceMs, uint64_t* deviceImages, bool timing);
     // the collective of the model-parallel mode (cfg.world > 1); must be set before the first frame
     void setAllreduce(int (*fn)(int64_t*, uint64_t, void*), void* user) { dist.allreduce_i64 = fn; dist.user = user; }
     void setAllreduceDevice(int (*fn)(int64_t*, uint64_t, void*, void*), void* user) { dist.allreduce_dev = fn; dist.user_dev = user; }
@@ -437,6 +448,7 @@ class CoFusion {
     void ensureRenderer(int w, int h);
     void releaseRenderer();
     void exportViews(int frameTick);
+    std::unique_ptr<ExportWriter> exportWriter;   // setExportAsync
     bool useLanes = true;  // per-model auxiliary streams
     std::shared_ptr<EnqueuePool> pool;                      // Config::enqueueThreads helpers
     void modelPasses(Model& model, bool fuse, float weightMultiplier, bool lost);

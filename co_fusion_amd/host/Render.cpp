@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "CoFusion.h"
+#include "ExportWriter.h"
 
 namespace cofusion {
 
@@ -98,6 +99,28 @@ void CoFusion::setExportViews(const std::string& prefix, int which)
     exportViewsWhich = prefix.empty() ? 0 : which;
 }
 
+void CoFusion::setExportAsync(bool on, int workers, int slots)
+{
+    if (exportWriter) { std::unique_ptr<ExportWriter> old = std::move(exportWriter); old->flush(); }   // (off, whatever the flush reports)
+    if (on) exportWriter.reset(new ExportWriter(ctx, cfg.width, cfg.height, workers, slots));
+}
+
+void CoFusion::exportFlush()
+{
+    if (exportWriter) exportWriter->flush();
+}
+
+void CoFusion::exportStats(uint64_t* images, uint64_t* bytes, uint64_t* stalls, double* deviceMs, uint64_t* deviceImages, bool timing)
+{
+    ExportWriter::Stats s;
+    if (exportWriter) s = exportWriter->stats(timing);
+    if (images) *images = s.images;
+    if (bytes) *bytes = s.bytes;
+    if (stalls) *stalls = s.stalls;
+    if (deviceMs) *deviceMs = s.deviceMs;
+    if (deviceImages) *deviceImages = s.deviceImages;
+}
+
 // after a processed frame: one rasterisation from the current camera feeds the requested colour images
 void CoFusion::exportViews(int frameTick)
 {
@@ -114,8 +137,14 @@ void CoFusion::exportViews(int frameTick)
         }
     renderScene(nullptr, CF_RENDER_COLOUR, CF_RENDER_LABEL, 0, outs, n);
     const size_t frame = (size_t)cfg.width * cfg.height * 4;
-    std::vector<uint8_t> host(frame);
     int j = 0;
+    if (exportWriter) {   // setExportAsync: encoded on the device, in stream order behind the rasterisation; nothing is read back here
+        for (auto& k : kinds)
+            if (exportViewsWhich & k.bit)
+                exportWriter->submit(exportViewsPrefix + k.name + std::to_string(frameTick) + ".png", outs[j++].dst, cfg.width, cfg.height, 4, 0);
+        return;
+    }
+    std::vector<uint8_t> host(frame);
     for (auto& k : kinds) {
         if (!(exportViewsWhich & k.bit)) continue;
         rcheck(ctx, cf_memcpy_d2h(ctx, host.data(), outs[j++].dst, frame), "exported view readback");

@@ -338,6 +338,24 @@ int cofusion_set_export_views(cofusion_handle* h, const char* prefix, int which)
     GUARD(h->cf->setExportViews(prefix ? prefix : "", which));
     return 0;
 }
+int cofusion_set_export_async(cofusion_handle* h, int on, int workers, int slots)
+{
+    if (!h) { g_err = "cofusion_set_export_async: no instance"; return -1; }
+    GUARD(h->cf->setExportAsync(on != 0, workers, slots));
+    return 0;
+}
+int cofusion_export_flush(cofusion_handle* h)
+{
+    if (!h) { g_err = "cofusion_export_flush: no instance"; return -1; }
+    GUARD(h->cf->exportFlush());
+    return 0;
+}
+int cofusion_export_stats(cofusion_handle* h, uint64_t* images, uint64_t* bytes, uint64_t* stalls, double* device_ms, uint64_t* device_images, int timing)
+{
+    if (!h) { g_err = "cofusion_export_stats: no instance"; return -1; }
+    GUARD(h->cf->exportStats(images, bytes, stalls, device_ms, device_images, timing != 0));
+    return 0;
+}
 int cofusion_save_ply(cofusion_handle* h, const char* prefix)
 {
     try { const int n = h->cf->savePly(prefix ? prefix : ""); if (n < 0) g_err = "savePly: cannot write"; return n; }

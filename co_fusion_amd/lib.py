@@ -36,6 +36,7 @@ SYMBOLS = [
     "cf_ferns_relocalise", "cf_ferns_count", "cf_ferns_download", "cf_ferns_last_search",
     "cf_frame_decoder_create", "cf_frame_decoder_destroy", "cf_frame_decoder_slot", "cf_frame_decoder_submit", "cf_frame_decoder_acquire", "cf_frame_decoder_timing",
     "cf_frame_decoder_enable_images", "cf_frame_decoder_image_slot", "cf_frame_decoder_submit_images", "cf_frame_decoder_acquire_mask", "cf_frame_decoder_image_timing",
+    "cf_png_encoder_create", "cf_png_encoder_destroy", "cf_png_encoder_submit", "cf_png_encoder_acquire", "cf_png_encoder_timing",
 ]
 
 
@@ -60,7 +61,7 @@ HOST_SYMBOLS = [
     "cofusion_model_download", "cofusion_model_icp_stats", "cofusion_model_cull_box", "cofusion_model_level0_visited", "cofusion_model_tracking_inputs", "cofusion_mask_device", "cofusion_context", "cofusion_set_crf", "cofusion_set_seg_early",
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
-    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_relocalisation", "cofusion_reloc_stats",
+    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",
     "cofusion_image_reader_open", "cofusion_image_reader_next", "cofusion_image_reader_rewind", "cofusion_image_reader_close",

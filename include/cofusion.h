@@ -185,6 +185,18 @@ int cofusion_render_device(cofusion_handle *h, const cf_render_view *view, int b
  * in label colour), <prefix>Normals<n>.png (normals) and / or <prefix>Viewport<n>.png (colour) -- RGBA PNG from the current camera,
  * <n> the frame's number as in Segmentation<n>.png.  which: 1 labels | 2 normals | 4 viewport; 0 or an empty prefix: off. */
 int cofusion_set_export_views(cofusion_handle *h, const char *export_dir_prefix, int which);
+/* The per-frame exports above through the device PNG encoder (cf_png_encoder, include/cofusion_hip.h) and `workers` (1..8) writer
+ * threads instead of a read-back and zlib on the calling thread: same file names, numbering and pixels.  Off by default.  The frame
+ * loop waits for a file only when all `slots` (2..16) are busy -- nothing is dropped; a failed write is reported by the next
+ * cofusion_process_frame* or by cofusion_export_flush.  on = 0 writes what is in flight and returns to the synchronous exports. */
+int cofusion_set_export_async(cofusion_handle *h, int on, int workers, int slots);
+/* returns when every file submitted so far is closed */
+int cofusion_export_flush(cofusion_handle *h);
+/* images and bytes written, submits that found every slot busy (each nullable).  device_ms / device_images: the encoding kernel's
+ * device-event time over the images submitted since the last call while timing was on; timing: that diagnostics mode from here on.
+ * Waits for the files in flight. */
+int cofusion_export_stats(cofusion_handle *h, uint64_t *images, uint64_t *bytes, uint64_t *stalls, double *device_ms, uint64_t *device_images,
+                          int timing);
 
 /* .klg RGB-D logs (GUI/Tools/KlgLogReader.cpp:22-87): u16-mm depth raw or zlib, 8-bit x3 colour raw (JPEG frames are
  * rejected: no libjpeg in this build).  depth_m [H*W] metres, rgb [H*W*3]. */

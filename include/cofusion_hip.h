@@ -777,6 +777,41 @@ int cf_frame_decoder_acquire_mask(cf_frame_decoder *dec, int slot, int complete,
  * the sums; the .klg sums of cf_frame_decoder_timing are kept apart and count no image frame. */
 int cf_frame_decoder_image_timing(cf_frame_decoder *dec, double *exr_ms, uint64_t *exr_frames, double *finish_ms, uint64_t *finish_frames);
 
+/* ---- PNG encoder of the per-frame exports (csrc/png_encode.hip) ----
+ * A device image (8-bit grey or RGBA8) becomes the bands of a complete PNG data stream -- adaptive row filtering, then deflate with
+ * the fixed code over runs of equal bytes, or a stored block where that is shorter -- in a pinned slot; the host adds the chunk
+ * framing and the CRC (host/ExportWriter.cpp).  The stream is a function of the pixels, channels, rows_per_band and flags alone. */
+#define CF_PNG_LABELS 1     /* grey only: a byte > 254 is encoded as 0 (the rejected label of Segmentation<n>.png) */
+typedef struct {
+    uint32_t offset;        /* of the band's bytes in cf_png_stream.data */
+    uint32_t bytes;         /* of the encoded band: whole deflate blocks, ending on a byte */
+    uint32_t adler;         /* Adler-32 of the band's filtered scanlines alone ... */
+    uint32_t stream_bytes;  /* ... and their length: (1 + channels * width) * rows of the band */
+} cf_png_band;
+typedef struct {
+    int32_t width, height, channels, rows_per_band, bands;
+    const cf_png_band *table;   /* bands entries, in the pinned slot */
+    const uint8_t *data;        /* the pinned slot's band area */
+    uint64_t data_bytes;        /* its extent: every offset + bytes lies inside */
+} cf_png_stream;
+typedef struct cf_png_encoder cf_png_encoder;
+/* slots: 2..16; rows_per_band >= 1 with (1 + 4 * max_w) * rows_per_band <= 65535 (a band is one stored block at most) and a band pair
+ * that fits the LDS.  Owns the pinned slots, their device mirrors, a copy stream and one event per slot; nothing is allocated per
+ * image.  Any max_w, max_h >= 1. */
+int cf_png_encoder_create(cf_ctx *ctx, int max_w, int max_h, int slots, int rows_per_band, cf_png_encoder **out);
+void cf_png_encoder_destroy(cf_png_encoder *enc);
+/* Encodes src_dev (height rows of width * channels bytes, channels 1 or 4) into the slot without a host wait.  The kernel is launched
+ * on the context's stream: it is ordered after what that stream holds at the call, and work enqueued there after the return may
+ * overwrite src_dev.  The copy to the pinned slot runs on the encoder's stream behind it; the slot's event follows the copy.  Sizes
+ * beyond the encoder's, other channel counts, unknown flags or CF_PNG_LABELS on RGBA: CF_EINVAL, nothing is launched. */
+int cf_png_encoder_submit(cf_png_encoder *enc, int slot, const void *src_dev, int width, int height, int channels, int flags);
+/* The host blocks on the slot's event.  The band table and the bytes stay intact until the slot's next submit.  May be called from
+ * another thread than the one that submits. */
+int cf_png_encoder_acquire(cf_png_encoder *enc, int slot, cf_png_stream *out);
+/* accumulated device-event duration of the encoding kernel over the submits while timing is on (a diagnostics mode that adds an event
+ * pair to every submit); reading waits for the slots submitted so far and resets the sums.  Call it from the submitting thread. */
+int cf_png_encoder_timing(cf_png_encoder *enc, int on, double *kernel_ms, uint64_t *images);
+
 /* micro-benchmark of the ICP reduction on the state of the last tracking call (level 0..2) */
 int cf_odom_bench_icp(cf_odom *od, int level, int iters, float *avg_us);
 

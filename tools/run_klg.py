@@ -4,11 +4,13 @@ does head-less, GUI/MainController.cpp):
 
     python tools/run_klg.py seq.klg out/ [--static] [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240]
                             [--frames N] [--flip-colors] [--export-segmentation]
-                            [--export-labels] [--export-normals] [--export-viewport] [--player [--workers N]]
+                            [--export-labels] [--export-normals] [--export-viewport] [--export-async [--export-workers N]]
+                            [--player [--workers N]]
                             [--mask-dir DIR [--mask-prefix Mask --index-width 4]]
 
 Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png, out/Labels<tick>.png, out/Normals<tick>.png,
-out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s.  --player reads the log ahead on
+out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s.  --export-async encodes those PNGs on
+the device and writes them from --export-workers threads (the same names and pixels; flushed before the rate is reported).  --player reads the log ahead on
 worker threads and finishes the frames on the device (klg.KlgPlayer) instead of decoding each frame in front of its processing: the
 same frames, the same outputs.  --mask-dir feeds the reference's pre-processed segmentation (one label mask per frame, <prefix><index>.pgm,
 binary PGM with maxval <= 255; the numbering starts at 0 or 1, whichever file exists) instead of running the motion segmentation: with the
@@ -47,6 +49,8 @@ def main():
     ap.add_argument("--export-labels", action="store_true", help="Labels<n>.png: background in colour, objects in label colour (-el)")
     ap.add_argument("--export-normals", action="store_true", help="Normals<n>.png (-en)")
     ap.add_argument("--export-viewport", action="store_true", help="Viewport<n>.png: every model in colour (-ev)")
+    ap.add_argument("--export-async", action="store_true", help="the per-frame PNG exports through the device encoder and writer threads")
+    ap.add_argument("--export-workers", type=int, default=2, help="writer threads of --export-async (1..8)")
     ap.add_argument("--max-surfels", type=int, default=3072 * 3072)
     ap.add_argument("--relocalise", action="store_true", help="failure detection (-rl) with the fern keyframe database: a lost camera recovers")
     ap.add_argument("--fern-threshold", type=float, default=0.3095, help="a frame becomes a keyframe when it differs more than this from every keyframe")
@@ -93,6 +97,8 @@ def main():
         cf.set_export_segmentation(prefix)
     if a.export_labels or a.export_normals or a.export_viewport:
         cf.set_export_views(prefix, labels=a.export_labels, normals=a.export_normals, viewport=a.export_viewport)
+    if a.export_async:
+        cf.set_export_async(True, workers=a.export_workers)
     n, t0 = 0, time.perf_counter()
     mask_of = None
     if a.mask_dir and not images_dir:
@@ -146,11 +152,16 @@ def main():
             n += 1
             if 0 < a.frames <= n:
                 break
+    if a.export_async:
+        cf.export_flush()   # the rate below includes every file
     dt = time.perf_counter() - t0
     how = f"{'image' if images_dir else 'log'} player, {a.workers} workers" if a.player else ("incl. file decoding and upload" if images_dir else "incl. log decoding and upload")
     print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s {how}), {cf.num_models} active models")
     if a.relocalise:
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
+    if a.export_async:
+        s = cf.export_stats()
+        print(f"asynchronous exports: {s['images']} files, {s['bytes']} bytes, {s['stalls']} submits waited for a slot")
     print(f"exported {cf.export_poses(prefix)} pose file(s), {cf.save_ply(prefix)} PLY cloud(s) to {prefix}")
     cf.close()
 
