@@ -42,6 +42,22 @@ class TrackStats(C.Structure):
                 ("lastA", C.c_double * 36), ("lastb", C.c_double * 6), ("so3_iterations", C.c_int), ("fault", C.c_int), ("cull_box", C.c_int * 4)]
 
 
+class GnState(C.Structure):
+    """cf_gn_state: the words of a tracker's device-resident state the Gauss-Newton solve reads and writes"""
+    _fields_ = [("intr", Cam), ("width", C.c_int32), ("height", C.c_int32), ("icp", C.c_int32), ("rgb", C.c_int32),
+                ("rgbOnly", C.c_int32), ("icpWeight", C.c_float), ("Rprev", C.c_float * 9), ("tprev", C.c_float * 3),
+                ("Rprev_inv", C.c_float * 9), ("Rcurr", C.c_float * 9), ("tcurr", C.c_float * 3), ("resultRt", C.c_double * 16),
+                ("krkInv", C.c_float * 9), ("kt", C.c_float * 3), ("lastRGBError", C.c_float), ("level_done", C.c_int32),
+                ("solves", C.c_int32), ("residual", C.c_float * 2), ("cull_z", C.c_float * 2), ("pose_inv", C.c_float * 16),
+                ("stats", TrackStats)]
+
+
+class GnSystem(C.Structure):
+    """cf_gn_system: one system of cf_gn_solve_step (grouped sums [64][32], state, pinned-host twin, the derived hot block)"""
+    _fields_ = [("icp_acc", C.c_int64 * (64 * 32)), ("rgb_acc", C.c_int64 * (64 * 32)), ("state", GnState), ("twin", GnState),
+                ("hot", C.c_uint32 * 48)]
+
+
 class Profile(C.Structure):
     _fields_ = [("icp_ms_total", C.c_double), ("icp_launches", C.c_uint64), ("icp_bytes", C.c_uint64),
                 ("surfel_ms_total", C.c_double), ("surfel_calls", C.c_uint64), ("surfel_bytes", C.c_uint64)]
@@ -258,6 +274,14 @@ class Context:
                                          A, b, res, sums))
         return (np.array(A, np.float32).reshape(3, 3), np.array(b, np.float32), np.array(res, np.float32),
                 np.array(sums, np.int64))
+
+    def gn_solve_step(self, systems, next_level, last_of_level, icp_fix=32):
+        """cf_gn_solve_step: the per-iteration Gauss-Newton solve as the schedule launches it, one workgroup per system.  systems: a
+        ctypes array of 1..16 GnSystem (updated in place) or a sequence of them (copied); returns the array with state, twin, hot
+        block and both accumulators as the kernel left them"""
+        arr = systems if isinstance(systems, C.Array) else (GnSystem * len(systems))(*systems)
+        self._check(self.lib.cf_gn_solve_step(self.h, len(arr), arr, int(next_level), int(bool(last_of_level)), int(icp_fix)))
+        return arr
 
     def set_icp_launch(self, threads, ppt):
         self._check(self.lib.cf_set_icp_launch(self.h, threads, ppt))

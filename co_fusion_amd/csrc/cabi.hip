@@ -563,6 +563,76 @@ int cf_so3_step(cf_ctx* ctx, const uint8_t* last_image, const uint8_t* next_imag
     return CF_OK;
 }
 
+// The solve of one Gauss-Newton iteration on its own: gn_solve_kernel as the schedule launches it (launch_gn_solve), on temporary
+// device states filled from the caller's words.
+namespace {
+void gn_state_to_dev(const cf_gn_state& g, OdomDev* h)   // (configuration words included: used for states and twins alike)
+{
+    h->intr = g.intr; h->width = g.width; h->height = g.height; h->icp = g.icp; h->rgb = g.rgb; h->rgbOnly = g.rgbOnly; h->icpWeight = g.icpWeight;
+    memcpy(h->Rprev, g.Rprev, 36); memcpy(h->tprev, g.tprev, 12); memcpy(h->Rprev_inv, g.Rprev_inv, 36); memcpy(h->Rcurr, g.Rcurr, 36); memcpy(h->tcurr, g.tcurr, 12);
+    memcpy(h->resultRt, g.resultRt, sizeof(g.resultRt)); memcpy(h->krkInv, g.krkInv, 36); memcpy(h->kt, g.kt, 12);
+    h->lastRGBError = g.lastRGBError; h->level_done = g.level_done; h->solves = g.solves; memcpy(h->residual, g.residual, 8);
+    memcpy(h->cull_z, g.cull_z, 8); memcpy(h->pose_inv, g.pose_inv, sizeof(g.pose_inv)); h->stats = g.stats;
+}
+void gn_state_from_dev(const OdomDev* h, cf_gn_state* g)  // every word back, the configuration the solve must leave alone included
+{
+    g->intr = h->intr; g->width = h->width; g->height = h->height; g->icp = h->icp; g->rgb = h->rgb; g->rgbOnly = h->rgbOnly; g->icpWeight = h->icpWeight;
+    memcpy(g->Rprev, h->Rprev, 36); memcpy(g->tprev, h->tprev, 12); memcpy(g->Rprev_inv, h->Rprev_inv, 36); memcpy(g->Rcurr, h->Rcurr, 36); memcpy(g->tcurr, h->tcurr, 12);
+    memcpy(g->resultRt, h->resultRt, sizeof(g->resultRt)); memcpy(g->krkInv, h->krkInv, 36); memcpy(g->kt, h->kt, 12);
+    g->lastRGBError = h->lastRGBError; g->level_done = h->level_done; g->solves = h->solves; memcpy(g->residual, h->residual, 8);
+    memcpy(g->cull_z, h->cull_z, 8); memcpy(g->pose_inv, h->pose_inv, sizeof(g->pose_inv)); g->stats = h->stats;
+}
+struct GnStepBuffers {   // temporaries of one cf_gn_solve_step call
+    hipStream_t stream = nullptr;
+    OdomDev* d_states = nullptr; unsigned long long* d_acc = nullptr; OdomDev* h_twins = nullptr;
+    // (an entry that fails half way returns with copies and the launch still enqueued: nothing they touch is released before the stream is idle)
+    ~GnStepBuffers() { (void)hipStreamSynchronize(stream); (void)hipFree(d_states); (void)hipFree(d_acc); if (h_twins) (void)hipHostFree(h_twins); }
+};
+}  // namespace
+
+int cf_gn_solve_step(cf_ctx* ctx, int n, cf_gn_system* systems, int next_level, int last_of_level, int icp_fix)
+{
+    if (!ctx || !systems || n < 1 || n > kMaxBatch || next_level < -1 || next_level > 2 || (icp_fix != -1 && icp_fix != CF_FIX_ICP)) return CF_EINVAL;
+    constexpr size_t kAccWords = (size_t)kGroups * 32;
+    static_assert(sizeof(systems->icp_acc) == kAccWords * 8 && sizeof(systems->hot) == sizeof(GnHot), "cf_gn_system mirrors the accumulators and the hot block");
+    std::vector<OdomDev> h((size_t)n);   // (declared in front of buf: destroyed behind its synchronisation)
+    GnStepBuffers buf;
+    buf.stream = ctx->stream;
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_states), sizeof(OdomDev) * n));
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_acc), 8 * kAccWords * 2 * n));
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&buf.h_twins), sizeof(OdomDev) * n, hipHostMallocCoherent));  // the solve stores into them
+    GnArgs gn{};
+    gn.icp_gram = icp_fix < 0 ? 1 : 0;
+    gn.slot_px = ctx->icp_launch.threads * 4;
+    for (int k = 0; k < n; k++) {
+        OdomDev* s = &h[(size_t)k];
+        memset(s, 0, sizeof(*s));
+        gn_state_to_dev(systems[k].state, s);
+        s->icp_acc = buf.d_acc + kAccWords * 2 * k; s->rgb_acc = s->icp_acc + kAccWords;
+        refresh_hot(s);
+        memset(&buf.h_twins[k], 0, sizeof(OdomDev));
+        gn_state_to_dev(systems[k].twin, &buf.h_twins[k]);
+        gn.od[k] = buf.d_states + k; gn.icp_acc[k] = s->icp_acc; gn.rgb_acc[k] = s->rgb_acc; gn.od_host[k] = &buf.h_twins[k];
+        HIPCHK(ctx, hipMemcpyAsync(s->icp_acc, systems[k].icp_acc, 8 * kAccWords, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(s->rgb_acc, systems[k].rgb_acc, 8 * kAccWords, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(buf.d_states, h.data(), sizeof(OdomDev) * n, hipMemcpyHostToDevice, ctx->stream));
+    launch_gn_solve(ctx->stream, gn, n, next_level, last_of_level);
+    LAUNCHCHK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), buf.d_states, sizeof(OdomDev) * n, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < n; k++) {
+        HIPCHK(ctx, hipMemcpyAsync(systems[k].icp_acc, gn.icp_acc[k], 8 * kAccWords, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(systems[k].rgb_acc, gn.rgb_acc[k], 8 * kAccWords, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) {
+        gn_state_from_dev(&h[(size_t)k], &systems[k].state);
+        gn_state_from_dev(&buf.h_twins[k], &systems[k].twin);
+        memcpy(systems[k].hot, &h[(size_t)k].hot, sizeof(GnHot));
+    }
+    return CF_OK;
+}
+
 // ----------------------------------------------------------------------- RGBDOdometry ----
 int cf_odom_create(cf_ctx* ctx, cf_odom** out)
 {

@@ -316,6 +316,8 @@ void launch_rgb_cand(hipStream_t s, const int16_t* dIdx, const int16_t* dIdy, co
                      const uint8_t* next_image, float min_scale, int cols, int rows, uint8_t* cand);
 void launch_so3_step(hipStream_t s, const uint8_t* last_image, const uint8_t* next_image, const float basis[9],
                      const float kinv[9], const float krlr[9], int cols, int rows, unsigned long long* out16);
+// the per-iteration solve on its own (cf_gn_solve_step): gn_solve_kernel as the schedule launches it, one workgroup per system of `gn`
+void launch_gn_solve(hipStream_t s, const GnArgs& gn, int n, int next_level, int last_of_level);
 
 struct ProfSink {  // hipEvent pairs recorded around every ICP-reduce launch when enabled
     hipEvent_t* events; int capacity; int used; uint64_t bytes; uint64_t launches; int enabled;

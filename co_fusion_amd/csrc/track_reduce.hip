@@ -1104,6 +1104,10 @@ void launch_rgb_step(hipStream_t s, const RgbArgs& ra, int n)
     const int N = ra.cols * ra.rows;
     rgb_step_kernel<<<dim3((N + 255) / 256, n), 256, 0, s>>>(ra);
 }
+void launch_gn_solve(hipStream_t s, const GnArgs& gn, int n, int next_level, int last_of_level)
+{
+    gn_solve_kernel<<<n, 256, 0, s>>>(gn, next_level, last_of_level ? 1 : 0);
+}
 void launch_acc_total(hipStream_t s, const unsigned long long* acc, unsigned long long* out)
 {
     acc_total_kernel<<<1, 64, 0, s>>>(acc, out);

@@ -253,6 +253,40 @@ int cf_odom_fetch_result(cf_odom *od, float trans[3], float rot[9], cf_track_sta
  * statistics: partial-pivot LU inverse of the 6x6 normal matrix, row-major f64 [36], on the host (the caller already holds lastA).
  * A singular lastA gives inf / NaN entries, as Eigen's does. */
 int cf_odom_get_covariance(const cf_track_stats *stats, double cov[36]);
+
+/* The per-iteration Gauss-Newton solve on its own (a stand-alone step like cf_icp_step / cf_rgb_step / cf_so3_step): the kernel the
+ * tracking schedule launches behind every {ICP reduction, RGB step}, given sums and a state the caller wrote by hand.
+ * cf_gn_state: the words of the device-resident tracker state the solve reads and writes (RGBDOdometry.cpp:371-467 keeps them in
+ * host locals).  In and out are the same struct: a returned state can be handed straight to the next call. */
+typedef struct {
+    cf_cam intr;                      /* level-0 intrinsics: K of `next_level` is derived from them */
+    int32_t width, height;
+    int32_t icp, rgb, rgbOnly;
+    float icpWeight;
+    float Rprev[9], tprev[3], Rprev_inv[9], Rcurr[9], tcurr[3];
+    double resultRt[16];
+    float krkInv[9], kt[3];
+    float lastRGBError;
+    int32_t level_done, solves;
+    float residual[2];
+    float cull_z[2];
+    float pose_inv[16];
+    cf_track_stats stats;
+} cf_gn_state;
+typedef struct {
+    int64_t icp_acc[64 * 32];         /* in: the grouped ICP sums [64 groups][32 words] (words 29 / 30 of the group totals: RGB count, sigma);
+                                       * out: as the kernel left them */
+    int64_t rgb_acc[64 * 32];         /* ... and the grouped RGB sums */
+    cf_gn_state state;                /* in: the state before the solve; out: read back from the device */
+    cf_gn_state twin;                 /* in: what the tracker's pinned host copy holds before; out: what it holds afterwards (the solve that ends
+                                       * a schedule, next_level < 0, publishes its result there; configuration words are never written) */
+    uint32_t hot[48];                 /* out: the derived block the per-iteration launches read pose and flags from */
+} cf_gn_system;
+/* One launch of `n` workgroups (1 <= n <= 16), system k in workgroup k, each on a temporary device state (screen-box culling off).
+ * next_level: pyramid level of the NEXT iteration (2, 1, 0; -1: the schedule ends, the divergence guard and the inverse pose are
+ * evaluated); last_of_level: the iteration ends its level (re-arms the RGB-only stop rule); icp_fix: fraction bits of the ICP sums
+ * (CF_FIX_ICP), or -1 for the Gram form's per-word bits.  Synchronous.  n out of range or a null pointer: CF_EINVAL, nothing enqueued. */
+int cf_gn_solve_step(cf_ctx *ctx, int n, cf_gn_system *systems, int next_level, int last_of_level, int icp_fix);
 /* pixels the level-0 {ICP reduction || RGB residual} launch of the last fetched tracking call visited for this tracker: the 64-pixel
  * runs inside its final screen box and the record slots between its first and last RGB candidate (the whole image for a tracker
  * that is not culled) -- the physical byte count of a roofline figure, as opposed to SURVEY 8(d)'s every-pixel-to-every-tracker */

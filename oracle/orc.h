@@ -139,6 +139,46 @@ typedef struct {
 /* trans[3]/rot[9] (row-major) in-out; err_surface nullable [H*W] */
 void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], float rot[9], const orc_track_opts *opts,
                                              float *icp_err_surface, orc_track_stats *stats);
+/* The algebra of ONE Gauss-Newton iteration of that loop (RGBDOdometry.cpp:371-467) as a function: the totals of the ICP and RGB sums
+ * -> A, b (f32) -> f64 combine -> LDL^T -> SE(3) update -> f32 pose, then what the following iteration starts from (krkInv, kt for
+ * `next_level`) or, where the schedule ends (next_level < 0), the divergence guard.  orc_odom_get_incremental_transformation calls it
+ * once per iteration.  State in and out are the same struct.
+ * The function is cut the way the device cuts the loop, not the way the reference's text reads: krkInv / kt of an iteration are formed
+ * at the end of the one before it, the guard is part of the last step, and an iteration that the stop rule has ended still counts
+ * (`solves`).  stats.last_rgb_error follows the device as well: a step leaves it alone unless it is active, whereas the reference
+ * resets it to FLT_MAX at the start of every level (RGBDOdometry.cpp:344) -- the oracle's loop does that reset itself.  The two differ
+ * only if the stop rule fires at the first iteration of a level, which needs tmpError = inf, i.e. a count of 0 under a non-zero sigma;
+ * the residual pass cannot produce that. */
+typedef struct {
+    orc_cam intr;                     /* level 0 */
+    int32_t width, height;
+    int32_t icp, rgb, rgbOnly;
+    float icpWeight;
+    float Rprev[9], tprev[3], Rcurr[9], tcurr[3];
+    double resultRt[16];
+    float krkInv[9], kt[3];
+    float lastRGBError;               /* the stop rule's memory: FLT_MAX at the start of a level */
+    int32_t level_done, solves;       /* the stop rule fired in this level: the remaining iterations of the level leave the pose alone */
+    float residual[2];
+    orc_track_stats stats;
+} orc_gn_state;
+typedef struct {
+    int32_t pivot[6], tie[6], zero[6]; /* per LDL^T step: the row chosen, two or more remaining diagonals tied for the maximum, pivot taken as zero */
+    double theta;                      /* norm of the rotation part of the update */
+    double result[6];                  /* the solution of the 6x6 system as the LDL^T left it */
+    int32_t active, identity, stop, guard; /* a system was solved; theta below epsilon: identity rotation; the RGB-only stop rule fired; the guard reset the pose */
+} orc_gn_trace;
+/* icp_tot / rgb_tot: the 32 totals of either accumulator (icp_tot[29], [30]: the RGB residual's count and sigma); icp_fix: fraction bits
+ * of the ICP totals, or -1 for the Gram form's per-word bits; trace nullable */
+void orc_gn_solve_step(orc_gn_state *s, const int64_t icp_tot[32], const int64_t rgb_tot[32], int next_level, int last_of_level,
+                       int icp_fix, orc_gn_trace *trace);
+/* the host algebra of the reference-order mode (ORC_ICP_ARITH_REFERENCE): the left-looking pivoted LDL^T solve, N <= 6, row-major */
+void eig_ldlt_solve_d(int N, const double *A, const double *b, double *x);
+void eig_ldlt_solve_f(int N, const float *A, const float *b, float *x);
+/* ... its general 4x4 inverse (cofactors of 3x3 minors, determinant along the first row) */
+void eig_inv44d(const double m[16], double o[16]);
+/* ... and OdometryProvider::rodrigues with the C library's cos / sin, as that mode calls it */
+void orc_ref_rodrigues(const double w[3], double R[9]);
 /* RGBDOdometry::getCovariance (RGBDOdometry.cpp:479): lastA.cast<double>().lu().inverse(), row-major 6x6 in and out */
 void orc_covariance(const double lastA[36], double cov[36]);
 /* test access to internal pyramids: which = 0 vmap_curr,1 nmap_curr,2 vmap_g_prev,3 nmap_g_prev (planar f32),

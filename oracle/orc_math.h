@@ -267,8 +267,11 @@ static inline void orc_inv44_affine_d(const double a[16], double o[16])
 /* Symmetric solve A x = b via LDL^T with diagonal pivoting; zero pivots give a
  * zero solution component (the behaviour of Eigen's ldlt().solve(), which the
  * reference relies on when a model has no inliers: RGBDOdometry.cpp:435). */
+/* The optional trace (orc_gn_solve_step) records, for every step k, the pivot row chosen, whether two or more of the remaining
+ * diagonals tied for the maximum, and whether the pivot was treated as zero. */
+typedef struct { int32_t pivot[6], tie[6], zero[6]; } orc_ldlt_trace;
 #define ORC_LDLT(T, NAME, TINY)                                                              \
-    static inline void NAME(int n, const T *Ain, const T *b, T *x)                           \
+    static inline void NAME(int n, const T *Ain, const T *b, T *x, orc_ldlt_trace *tr)       \
     {                                                                                        \
         T A[36], y[6], d[6];                                                                 \
         int perm[6];                                                                         \
@@ -281,6 +284,11 @@ static inline void orc_inv44_affine_d(const double a[16], double o[16])
                 T v = A[i * n + i] < 0 ? -A[i * n + i] : A[i * n + i];                       \
                 if (v > best) { best = v; p = i; }                                           \
             }                                                                                \
+            if (tr) {                                                                        \
+                int ties = 0;                                                                \
+                for (int i = k; i < n; i++) { T v = A[i * n + i] < 0 ? -A[i * n + i] : A[i * n + i]; if (v == best) ties++; } \
+                tr->pivot[k] = p; tr->tie[k] = ties > 1;                                     \
+            }                                                                                \
             if (p != k) { /* symmetric swap of rows/cols k and p (full storage) */          \
                 for (int j = 0; j < n; j++) { T t = A[k * n + j]; A[k * n + j] = A[p * n + j]; A[p * n + j] = t; } \
                 for (int i = 0; i < n; i++) { T t = A[i * n + k]; A[i * n + k] = A[i * n + p]; A[i * n + p] = t; } \
@@ -289,6 +297,7 @@ static inline void orc_inv44_affine_d(const double a[16], double o[16])
             T akk = A[k * n + k];                                                            \
             d[k] = akk;                                                                      \
             T aabs = akk < 0 ? -akk : akk;                                                   \
+            if (tr) tr->zero[k] = !(aabs > (T)TINY);                                         \
             if (aabs > (T)TINY) {                                                            \
                 for (int i = k + 1; i < n; i++) A[i * n + k] = A[i * n + k] / akk;           \
                 for (int i = k + 1; i < n; i++)                                              \

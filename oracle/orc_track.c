@@ -327,9 +327,8 @@ static void se3_accumulate_gram(const float row[7], int found, int64_t sums[ORC_
     sums[28] += 1;
 }
 
-void orc_icp_sums_to_host(const int64_t sums[ORC_SE3_WORDS], float A[36], float b[6], float residual[2])
+static void gram_sums_to_host(const int64_t sums[ORC_SE3_WORDS], float A[36], float b[6], float residual[2])
 {
-    if (g_icp_arith != ORC_ICP_ARITH_GRAM) { orc_se3_sums_to_host(sums, ORC_FIX_ICP, A, b, residual); return; }
     int shift = 0;
     for (int i = 0; i < 6; ++i)
         for (int j = i; j < 7; ++j) {
@@ -339,6 +338,11 @@ void orc_icp_sums_to_host(const int64_t sums[ORC_SE3_WORDS], float A[36], float 
         }
     residual[0] = (float)orc_fix_to_double(sums[27], 2 * orc_gram_bits[6]);
     residual[1] = (float)sums[28];
+}
+void orc_icp_sums_to_host(const int64_t sums[ORC_SE3_WORDS], float A[36], float b[6], float residual[2])
+{
+    if (g_icp_arith != ORC_ICP_ARITH_GRAM) orc_se3_sums_to_host(sums, ORC_FIX_ICP, A, b, residual);
+    else gram_sums_to_host(sums, A, b, residual);
 }
 
 static void se3_accumulate(const float row[7], int found, int F, int64_t sums[ORC_SE3_WORDS])
@@ -831,7 +835,7 @@ static double eig_minor3(const double m[16], int r, int c)
            M_(ri[0], ci[2]) * (M_(ri[1], ci[0]) * M_(ri[2], ci[1]) - M_(ri[1], ci[1]) * M_(ri[2], ci[0]));
 #undef M_
 }
-static void eig_inv44d(const double m[16], double o[16])
+void eig_inv44d(const double m[16], double o[16])
 {
     double cofm[4][4];
     for (int r = 0; r < 4; r++)
@@ -845,7 +849,7 @@ static void eig_inv44d(const double m[16], double o[16])
 /* Matrix::ldlt().solve() of the stand-in: unblocked LEFT-looking LDL^T on the lower triangle with diagonal pivoting (first maximum
  * wins), solve = P, L^-1, D^-1 (|d| <= 1 / max -> 0), L^-T, P^T */
 #define EIG_LDLT_SOLVE(T, NAME, TMAX)                                                                              \
-    static void NAME(int N, const T *Ain, const T *b, T *x)                                                        \
+    void NAME(int N, const T *Ain, const T *b, T *x)                                                               \
     {                                                                                                              \
         T a[36], y[6], temp[6];                                                                                    \
         int tr[6];                                                                                                 \
@@ -896,6 +900,8 @@ static void ref_rodrigues(const double src[3], double R[9])
         for (int k = 0; k < 9; k++) R[k] = c * I[k] + c1 * rrt[k] + s * r_x[k];
     }
 }
+
+void orc_ref_rodrigues(const double w[3], double R[9]) { ref_rodrigues(w, R); }
 
 /* reduce.cu:481-498 / 1158-1175: the 29 / 11 f32 totals -> A, b, residual */
 static void ref_unpack29(const float h[29], float A[36], float b[6], float residual[2])
@@ -1084,6 +1090,102 @@ static void odom_track_reference_order(orc_odometry *o, float trans[3], float ro
     memcpy(trans, tcurr, 12); memcpy(rot, Rcurr, 36);
 }
 
+/* what an iteration at `level` starts from (RGBDOdometry.cpp:330-345): Rt = resultRt^-1, krkInv = K R K^-1, kt = K t */
+static void gn_prepare_iteration(orc_gn_state *s, int level)
+{
+    double K[9], Kinv[9], Rt[16];
+    k_matrix(cam_level(s->intr, level), K);
+    orc_inv33d(K, Kinv);
+    orc_inv44_affine_d(s->resultRt, Rt);
+    double R[9] = {Rt[0], Rt[1], Rt[2], Rt[4], Rt[5], Rt[6], Rt[8], Rt[9], Rt[10]};
+    double tmp[9], KRK[9];
+    orc_mul33d(K, R, tmp); orc_mul33d(tmp, Kinv, KRK);
+    for (int k = 0; k < 9; k++) s->krkInv[k] = (float)KRK[k];
+    double tv[3] = {Rt[3], Rt[7], Rt[11]};
+    for (int r = 0; r < 3; r++) s->kt[r] = (float)(K[r * 3 + 0] * tv[0] + K[r * 3 + 1] * tv[1] + K[r * 3 + 2] * tv[2]);
+}
+
+/* One iteration's host algebra, RGBDOdometry.cpp:371-467 (orc.h) */
+void orc_gn_solve_step(orc_gn_state *s, const int64_t icp_tot[32], const int64_t rgb_tot[32], int next_level, int last_of_level,
+                       int icp_fix, orc_gn_trace *trace)
+{
+    orc_gn_trace local; if (!trace) trace = &local;
+    memset(trace, 0, sizeof(*trace));
+    orc_track_stats *st = &s->stats;
+    const int icp = s->icp != 0, rgb = s->rgb != 0, rgbOnly = s->rgbOnly != 0;
+    const int rgbSize = (int)icp_tot[29], sigma = (int)icp_tot[30];   /* the reference's two `int` totals */
+    int active = !s->level_done, stop = 0;
+    const float tmpError = (float)(sqrt((double)sigma) / rgbSize); /* sqrt(int)->double, / int, -> float */
+    float sigmaVal = (tmpError == 0) ? 1 : (float)rgbSize;         /* (sic) the COUNT, :374 */
+    if (active && rgbOnly && tmpError > s->lastRGBError) { stop = 1; active = 0; }   /* `break`, :385 */
+    if (rgbOnly) sigmaVal = -1;
+    if (active) {
+        s->lastRGBError = tmpError;
+        st->last_rgb_error = tmpError; st->last_rgb_count = (float)rgbSize;
+
+        float A_icp[36], b_icp[6], A_rgbd[36], b_rgbd[6];
+        memset(A_icp, 0, sizeof(A_icp)); memset(b_icp, 0, sizeof(b_icp));
+        memset(A_rgbd, 0, sizeof(A_rgbd)); memset(b_rgbd, 0, sizeof(b_rgbd));
+        if (icp) {
+            if (icp_fix >= 0) orc_se3_sums_to_host(icp_tot, icp_fix, A_icp, b_icp, s->residual);
+            else gram_sums_to_host(icp_tot, A_icp, b_icp, s->residual);
+        }
+        st->last_icp_error = sqrtf(s->residual[0]) / s->residual[1];
+        st->last_icp_count = s->residual[1];
+        if (rgb) {
+            float dummy[2];
+            orc_se3_sums_to_host(rgb_tot, orc_rgb_fix_bits(sigmaVal), A_rgbd, b_rgbd, dummy);
+        }
+        double lastA[36], lastb[6], result[6];
+        if (icp && rgb) {
+            double w = s->icpWeight;
+            for (int k = 0; k < 36; k++) lastA[k] = (double)A_rgbd[k] + w * w * (double)A_icp[k];
+            for (int k = 0; k < 6; k++) lastb[k] = (double)b_rgbd[k] + w * (double)b_icp[k];
+        } else if (icp) {
+            for (int k = 0; k < 36; k++) lastA[k] = A_icp[k];
+            for (int k = 0; k < 6; k++) lastb[k] = b_icp[k];
+        } else {
+            for (int k = 0; k < 36; k++) lastA[k] = A_rgbd[k];
+            for (int k = 0; k < 6; k++) lastb[k] = b_rgbd[k];
+        }
+        orc_ldlt_trace lt;
+        orc_ldlt_d(6, lastA, lastb, result, &lt);
+        memcpy(trace->pivot, lt.pivot, sizeof(lt.pivot)); memcpy(trace->tie, lt.tie, sizeof(lt.tie)); memcpy(trace->zero, lt.zero, sizeof(lt.zero));
+        memcpy(st->lastA, lastA, sizeof(lastA)); memcpy(st->lastb, lastb, sizeof(lastb));
+        memcpy(trace->result, result, sizeof(result));
+
+        /* OdometryProvider::computeUpdateSE3, OdometryProvider.h:69-89 */
+        double upd[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, Rr[9], nrt[16];
+        double rvec[3] = {result[3], result[4], result[5]};
+        trace->theta = sqrt(rvec[0] * rvec[0] + rvec[1] * rvec[1] + rvec[2] * rvec[2]);
+        trace->identity = !(trace->theta >= 2.2204460492503131e-16);
+        orc_rodrigues(rvec, Rr);
+        for (int r = 0; r < 3; r++) { upd[r * 4 + 0] = Rr[r * 3 + 0]; upd[r * 4 + 1] = Rr[r * 3 + 1]; upd[r * 4 + 2] = Rr[r * 3 + 2]; upd[r * 4 + 3] = result[r]; }
+        orc_mul44d(upd, s->resultRt, nrt);
+        memcpy(s->resultRt, nrt, sizeof(nrt));
+        /* rgbOdom (Isometry3f) = float(resultRt); currentT = [Rprev|tprev] * rgbOdom^-1 with the
+         * isometry inverse [R^T | -R^T t], RGBDOdometry.cpp:452-460 */
+        const double *resultRt = s->resultRt;
+        const float *Rprev = s->Rprev, *tprev = s->tprev;
+        float Ro[9], to[3];
+        for (int r = 0; r < 3; r++) { Ro[r * 3 + 0] = (float)resultRt[r * 4 + 0]; Ro[r * 3 + 1] = (float)resultRt[r * 4 + 1]; Ro[r * 3 + 2] = (float)resultRt[r * 4 + 2]; to[r] = (float)resultRt[r * 4 + 3]; }
+        float Rinv[9] = {Ro[0], Ro[3], Ro[6], Ro[1], Ro[4], Ro[7], Ro[2], Ro[5], Ro[8]};
+        float tinv[3];
+        for (int r = 0; r < 3; r++) tinv[r] = -(Rinv[r * 3 + 0] * to[0] + Rinv[r * 3 + 1] * to[1] + Rinv[r * 3 + 2] * to[2]);
+        orc_mul33f(Rprev, Rinv, s->Rcurr);
+        for (int r = 0; r < 3; r++) s->tcurr[r] = (Rprev[r * 3 + 0] * tinv[0] + Rprev[r * 3 + 1] * tinv[1] + Rprev[r * 3 + 2] * tinv[2]) + tprev[r];
+    }
+    if (next_level >= 0) gn_prepare_iteration(s, next_level);
+    else if (rgb) { /* divergence guard :464-467 */
+        float d[3] = {s->tcurr[0] - s->tprev[0], s->tcurr[1] - s->tprev[1], s->tcurr[2] - s->tprev[2]};
+        if ((double)sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) > 0.3) { memcpy(s->Rcurr, s->Rprev, 36); memcpy(s->tcurr, s->tprev, 12); trace->guard = 1; }
+    }
+    if (stop) s->level_done = 1;
+    if (last_of_level) { s->level_done = 0; s->lastRGBError = FLT_MAX; }   /* the next level starts over (:369) */
+    s->solves += 1;
+    trace->active = active; trace->stop = stop;
+}
+
 /* RGBDOdometry::getIncrementalTransformation, RGBDOdometry.cpp:217-477 */
 void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], float rot[9], const orc_track_opts *opts,
                                              float *icp_err_surface, orc_track_stats *st)
@@ -1135,7 +1237,7 @@ void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], fl
             lastError = st->last_so3_error; lastCount = st->last_so3_count;
             memcpy(lastResultR, resultR, sizeof(resultR));
             float delta[3];
-            orc_ldlt_f(3, jtj, jtr, delta);
+            orc_ldlt_f(3, jtj, jtr, delta, 0);
             double dd[3] = {delta[0], delta[1], delta[2]}, rotUpdate[9];
             orc_rodrigues(dd, rotUpdate);
             float ru[9], nr[9];
@@ -1159,97 +1261,54 @@ void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], fl
         for (int x = 0; x < 3; x++)
             for (int y = 0; y < 3; y++) resultRt[x * 4 + y] = resultR[x * 3 + y];
 
-    float residual[2] = {0, 0}; /* reference leaves this uninitialised when !icp (:401) */
+    /* the state one iteration hands to the next (orc_gn_solve_step); residual: the reference leaves it uninitialised when !icp (:401) */
+    orc_gn_state gs;
+    memset(&gs, 0, sizeof(gs));
+    gs.intr = o->intr; gs.width = o->width; gs.height = o->height; gs.icp = icp; gs.rgb = rgb; gs.rgbOnly = rgbOnly; gs.icpWeight = icpWeight;
+    memcpy(gs.Rprev, Rprev, 36); memcpy(gs.tprev, tprev, 12); memcpy(gs.Rcurr, Rcurr, 36); memcpy(gs.tcurr, tcurr, 12);
+    memcpy(gs.resultRt, resultRt, sizeof(resultRt));
+    gs.stats = *st;
+    const int icp_fix = g_icp_arith == ORC_ICP_ARITH_GRAM ? -1 : ORC_FIX_ICP;
+    int first = 1;
 
     for (int i = ORC_NUM_PYRS - 1; i >= 0; i--) {
         const int cols = o->width >> i, rows = o->height >> i;
         const orc_cam il = cam_level(o->intr, i);
         if (rgb) orc_project_cloud(o->lastDepth[i], cols, rows, il, o->cloud[i]);
-        double K[9], Kinv[9];
-        k_matrix(il, K);
-        orc_inv33d(K, Kinv);
-        st->last_rgb_error = FLT_MAX;
+        gs.lastRGBError = FLT_MAX; gs.level_done = 0;
+        gs.stats.last_rgb_error = FLT_MAX;   /* (:344: the statistic is the stop rule's memory in the reference) */
+        if (first && iterations[i] > 0) { gn_prepare_iteration(&gs, i); first = 0; }
 
         for (int j = 0; j < iterations[i]; j++) {
-            double Rt[16];
-            orc_inv44_affine_d(resultRt, Rt);
-            double R[9] = {Rt[0], Rt[1], Rt[2], Rt[4], Rt[5], Rt[6], Rt[8], Rt[9], Rt[10]};
-            double tmp[9], KRK[9];
-            orc_mul33d(K, R, tmp); orc_mul33d(tmp, Kinv, KRK);
-            float krkInv[9];
-            for (int k = 0; k < 9; k++) krkInv[k] = (float)KRK[k];
-            double tv[3] = {Rt[3], Rt[7], Rt[11]};
-            float kt[3];
-            for (int r = 0; r < 3; r++) kt[r] = (float)(K[r * 3 + 0] * tv[0] + K[r * 3 + 1] * tv[1] + K[r * 3 + 2] * tv[2]);
-
-            int sigma = 0, rgbSize = 0;
-            if (rgb) {
-                float minScale = (float)(pow(o->minGrad[i], 2.0) / pow(o->sobelScale, 2.0));
-                orc_rgb_residual(minScale, o->dIdx[i], o->dIdy[i], o->lastDepth[i], o->nextDepth[i], o->lastImage[i],
-                                 o->nextImage[i], o->corres[i], o->maxDepthDeltaRGB, kt, krkInv, cols, rows, &sigma, &rgbSize);
+            const int last_of_level = j == iterations[i] - 1;
+            int next_level = i;
+            if (last_of_level) next_level = i - 1;   /* (a level without iterations has none above it: 4/5/10 or 0/0/10) */
+            int64_t icp_sums[32], rgb_sums[32];
+            memset(icp_sums, 0, sizeof(icp_sums)); memset(rgb_sums, 0, sizeof(rgb_sums));
+            if (!gs.level_done) {   /* (`break` of the RGB-only stop rule, :385: the rest of the level computes nothing) */
+                int sigma = 0, rgbSize = 0;
+                if (rgb) {
+                    float minScale = (float)(pow(o->minGrad[i], 2.0) / pow(o->sobelScale, 2.0));
+                    orc_rgb_residual(minScale, o->dIdx[i], o->dIdy[i], o->lastDepth[i], o->nextDepth[i], o->lastImage[i],
+                                     o->nextImage[i], o->corres[i], o->maxDepthDeltaRGB, gs.kt, gs.krkInv, cols, rows, &sigma, &rgbSize);
+                }
+                float tmpError = (float)(sqrt((double)sigma) / rgbSize); /* sqrt(int)->double, / int, -> float */
+                float sigmaVal = (tmpError == 0) ? 1 : (float)rgbSize;   /* (sic) the COUNT, :374 */
+                if (rgbOnly) sigmaVal = -1;
+                if (icp)
+                    orc_icp_step(gs.Rcurr, gs.tcurr, o->vmaps_curr[i], o->nmaps_curr[i], Rprev_inv, tprev, il, o->vmaps_g_prev[i],
+                                 o->nmaps_g_prev[i], o->distThres, o->angleThres, cols, rows, icp_sums,
+                                 (i == 0 && last_of_level) ? icp_err_surface : 0);
+                if (rgb && !(rgbOnly && tmpError > gs.lastRGBError))
+                    orc_rgb_step(o->corres[i], sigmaVal, o->cloud[i], il.fx, il.fy, o->dIdx[i], o->dIdy[i], o->sobelScale,
+                                 cols, rows, rgb_sums);
+                icp_sums[29] = rgbSize; icp_sums[30] = sigma;   /* where the residual pass leaves its two totals */
             }
-            float tmpError = (float)(sqrt((double)sigma) / rgbSize); /* sqrt(int)->double, / int, -> float */
-            float sigmaVal = (tmpError == 0) ? 1 : (float)rgbSize;   /* (sic) the COUNT, :374 */
-            if (rgbOnly && tmpError > st->last_rgb_error) break;
-            st->last_rgb_error = tmpError; st->last_rgb_count = (float)rgbSize;
-            if (rgbOnly) sigmaVal = -1;
-
-            float A_icp[36], b_icp[6], A_rgbd[36], b_rgbd[6];
-            memset(A_icp, 0, sizeof(A_icp)); memset(b_icp, 0, sizeof(b_icp));
-            memset(A_rgbd, 0, sizeof(A_rgbd)); memset(b_rgbd, 0, sizeof(b_rgbd));
-            if (icp) {
-                int64_t sums[ORC_SE3_WORDS];
-                orc_icp_step(Rcurr, tcurr, o->vmaps_curr[i], o->nmaps_curr[i], Rprev_inv, tprev, il, o->vmaps_g_prev[i],
-                             o->nmaps_g_prev[i], o->distThres, o->angleThres, cols, rows, sums,
-                             (i == 0 && j == iterations[i] - 1) ? icp_err_surface : 0);
-                orc_icp_sums_to_host(sums, A_icp, b_icp, residual);
-            }
-            st->last_icp_error = sqrtf(residual[0]) / residual[1];
-            st->last_icp_count = residual[1];
-            if (rgb) {
-                int64_t sums[ORC_SE3_WORDS]; float dummy[2];
-                orc_rgb_step(o->corres[i], sigmaVal, o->cloud[i], il.fx, il.fy, o->dIdx[i], o->dIdy[i], o->sobelScale,
-                             cols, rows, sums);
-                orc_se3_sums_to_host(sums, orc_rgb_fix_bits(sigmaVal), A_rgbd, b_rgbd, dummy);
-            }
-            double lastA[36], lastb[6], result[6];
-            if (icp && rgb) {
-                double w = icpWeight;
-                for (int k = 0; k < 36; k++) lastA[k] = (double)A_rgbd[k] + w * w * (double)A_icp[k];
-                for (int k = 0; k < 6; k++) lastb[k] = (double)b_rgbd[k] + w * (double)b_icp[k];
-            } else if (icp) {
-                for (int k = 0; k < 36; k++) lastA[k] = A_icp[k];
-                for (int k = 0; k < 6; k++) lastb[k] = b_icp[k];
-            } else {
-                for (int k = 0; k < 36; k++) lastA[k] = A_rgbd[k];
-                for (int k = 0; k < 6; k++) lastb[k] = b_rgbd[k];
-            }
-            orc_ldlt_d(6, lastA, lastb, result);
-            memcpy(st->lastA, lastA, sizeof(lastA)); memcpy(st->lastb, lastb, sizeof(lastb));
-
-            /* OdometryProvider::computeUpdateSE3, OdometryProvider.h:69-89 */
-            double upd[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, Rr[9], nrt[16];
-            double rvec[3] = {result[3], result[4], result[5]};
-            orc_rodrigues(rvec, Rr);
-            for (int r = 0; r < 3; r++) { upd[r * 4 + 0] = Rr[r * 3 + 0]; upd[r * 4 + 1] = Rr[r * 3 + 1]; upd[r * 4 + 2] = Rr[r * 3 + 2]; upd[r * 4 + 3] = result[r]; }
-            orc_mul44d(upd, resultRt, nrt);
-            memcpy(resultRt, nrt, sizeof(nrt));
-            /* rgbOdom (Isometry3f) = float(resultRt); currentT = [Rprev|tprev] * rgbOdom^-1 with the
-             * isometry inverse [R^T | -R^T t], RGBDOdometry.cpp:452-460 */
-            float Ro[9], to[3];
-            for (int r = 0; r < 3; r++) { Ro[r * 3 + 0] = (float)resultRt[r * 4 + 0]; Ro[r * 3 + 1] = (float)resultRt[r * 4 + 1]; Ro[r * 3 + 2] = (float)resultRt[r * 4 + 2]; to[r] = (float)resultRt[r * 4 + 3]; }
-            float Rinv[9] = {Ro[0], Ro[3], Ro[6], Ro[1], Ro[4], Ro[7], Ro[2], Ro[5], Ro[8]};
-            float tinv[3];
-            for (int r = 0; r < 3; r++) tinv[r] = -(Rinv[r * 3 + 0] * to[0] + Rinv[r * 3 + 1] * to[1] + Rinv[r * 3 + 2] * to[2]);
-            orc_mul33f(Rprev, Rinv, Rcurr);
-            for (int r = 0; r < 3; r++) tcurr[r] = (Rprev[r * 3 + 0] * tinv[0] + Rprev[r * 3 + 1] * tinv[1] + Rprev[r * 3 + 2] * tinv[2]) + tprev[r];
+            orc_gn_solve_step(&gs, icp_sums, rgb_sums, next_level, last_of_level, icp_fix, 0);
         }
     }
-
-    if (rgb) { /* divergence guard :464-467 */
-        float d[3] = {tcurr[0] - tprev[0], tcurr[1] - tprev[1], tcurr[2] - tprev[2]};
-        if ((double)sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) > 0.3) { memcpy(Rcurr, Rprev, 36); memcpy(tcurr, tprev, 12); }
-    }
+    memcpy(Rcurr, gs.Rcurr, 36); memcpy(tcurr, gs.tcurr, 12);
+    *st = gs.stats;
     if (opts->so3) /* :469-473 */
         for (int i = 0; i < ORC_NUM_PYRS; i++) { uint8_t *t = o->lastNextImage[i]; o->lastNextImage[i] = o->nextImage[i]; o->nextImage[i] = t; }
     memcpy(trans, tcurr, 12); memcpy(rot, Rcurr, 36);

@@ -358,3 +358,60 @@ def so3_step_ref_order(last_image, next_image, basis, kinv, krlr, threads=160, b
                 A[i, j] = A[j, i] = out[k]
             k += 1
     return A, b, out[9:11].copy()
+
+
+# ---------------------------------------------------------------- one Gauss-Newton solve (orc_gn_solve_step) ----
+class GnState(C.Structure):
+    """orc_gn_state (oracle/orc.h): what one iteration of the tracking loop hands to the next"""
+    _fields_ = [("intr", Cam), ("width", C.c_int32), ("height", C.c_int32), ("icp", C.c_int32), ("rgb", C.c_int32),
+                ("rgbOnly", C.c_int32), ("icpWeight", C.c_float), ("Rprev", C.c_float * 9), ("tprev", C.c_float * 3),
+                ("Rcurr", C.c_float * 9), ("tcurr", C.c_float * 3), ("resultRt", C.c_double * 16), ("krkInv", C.c_float * 9),
+                ("kt", C.c_float * 3), ("lastRGBError", C.c_float), ("level_done", C.c_int32), ("solves", C.c_int32),
+                ("residual", C.c_float * 2), ("stats", TrackStats)]
+
+
+class GnTrace(C.Structure):
+    _fields_ = [("pivot", C.c_int32 * 6), ("tie", C.c_int32 * 6), ("zero", C.c_int32 * 6), ("theta", C.c_double), ("result", C.c_double * 6),
+                ("active", C.c_int32), ("identity", C.c_int32), ("stop", C.c_int32), ("guard", C.c_int32)]
+
+
+lib.orc_gn_solve_step.restype = None
+lib.orc_gn_solve_step.argtypes = [C.POINTER(GnState), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(GnTrace)]
+
+
+def gn_solve_step(state, icp_tot, rgb_tot, next_level, last_of_level, icp_fix=32):
+    """One iteration's algebra on a COPY of `state` (GnState): the 32 totals of either accumulator (int64) -> (state after, GnTrace)."""
+    out = GnState.from_buffer_copy(state)
+    tr = GnTrace()
+    a = np.ascontiguousarray(icp_tot, np.int64); b = np.ascontiguousarray(rgb_tot, np.int64)
+    assert a.shape == (32,) and b.shape == (32,)
+    lib.orc_gn_solve_step(C.byref(out), P(a), P(b), int(next_level), int(bool(last_of_level)), int(icp_fix), C.byref(tr))
+    return out, tr
+
+
+def inverse_pose(pose):
+    out = np.empty(16, np.float32)
+    lib.orc_inverse_pose(P(f32(pose).reshape(16)), P(out))
+    return out.reshape(4, 4)
+
+
+def eig_ldlt_solve(A, b):
+    """the reference-order mode's left-looking pivoted LDL^T solve (float64 or float32 by A's dtype)"""
+    A = np.ascontiguousarray(A); n = A.shape[0]
+    assert A.dtype in (np.float64, np.float32) and A.shape == (n, n) and n <= 6
+    b = np.ascontiguousarray(b, A.dtype); x = np.empty(n, A.dtype)
+    (lib.eig_ldlt_solve_d if A.dtype == np.float64 else lib.eig_ldlt_solve_f)(n, P(A), P(b), P(x))
+    return x
+
+
+def ref_rodrigues(w):
+    R = np.empty(9, np.float64)
+    lib.orc_ref_rodrigues(P(np.ascontiguousarray(w, np.float64)), P(R))
+    return R.reshape(3, 3)
+
+
+def eig_inv44(m):
+    """the reference-order mode's general 4x4 inverse (float64)"""
+    o = np.empty(16, np.float64)
+    lib.eig_inv44d(P(np.ascontiguousarray(m, np.float64).reshape(16)), P(o))
+    return o.reshape(4, 4)
