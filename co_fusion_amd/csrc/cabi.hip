@@ -83,6 +83,10 @@ void cf_destroy(cf_ctx* ctx)
     (void)hipHostFree(ctx->h_scratch_state); (void)hipHostFree(ctx->h_out);
     if (ctx->d_ref) (void)hipFree(ctx->d_ref);
     if (ctx->h_ref) (void)hipHostFree(ctx->h_ref);
+    if (ctx->d_redetect_bits) (void)hipFree(ctx->d_redetect_bits);
+    if (ctx->d_redetect_counts) (void)hipFree(ctx->d_redetect_counts);
+    if (ctx->h_redetect_counts) (void)hipHostFree(ctx->h_redetect_counts);
+    for (hipEvent_t e : ctx->redetect_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->prof.events) {
         for (int i = 0; i < ctx->prof.capacity; i++) (void)hipEventDestroy(ctx->prof.events[i]);
         delete[] ctx->prof.events;

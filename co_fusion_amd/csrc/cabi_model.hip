@@ -686,6 +686,70 @@ int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
     return CF_OK;
 }
 
+// Re-detection score (see the header; kernels in redetect.hip).  The frame's one extra host wait of a frame with a new label and a candidate.
+int cf_redetect_score(cf_ctx* ctx, const cf_redetect_candidate* cands, int n, const cf_redetect_frame* f, cf_redetect_counts* counts, uint32_t* label_pixels)
+{
+    if (!ctx || !cands || !f || !counts || n <= 0 || n > kRedetectBatch) return CF_EINVAL;
+    if (!f->depth || !f->label || f->cols <= 0 || f->rows <= 0 || (long long)f->cols * f->rows > 0x7fffffffLL) return CF_EINVAL;
+    hipStream_t s = ctx->cur();
+    const unsigned words = (unsigned)(((long long)f->cols * f->rows + 31) / 32);
+    const size_t n_counts = (size_t)kRedetectBatch * kRedetectWords + 1;
+    if (!ctx->d_redetect_counts) {
+        if (int r = dmalloc(ctx, &ctx->d_redetect_counts, n_counts)) return r;
+        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_redetect_counts), n_counts * sizeof(unsigned)));
+    }
+    if (words > ctx->redetect_words) {   // (a larger image than any before: bitmaps of the new size, zeroed)
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        if (ctx->d_redetect_bits) (void)hipFree(ctx->d_redetect_bits);
+        ctx->d_redetect_bits = nullptr; ctx->redetect_words = 0;
+        if (int r = dmalloc(ctx, &ctx->d_redetect_bits, (size_t)kRedetectBatch * words)) return r;
+        ctx->redetect_words = words;
+    }
+    RedetectCand rc[kRedetectBatch];
+    for (int k = 0; k < n; k++) {
+        cf_model* m = cands[k].model;
+        if (!m || m->ctx != ctx) return CF_EINVAL;
+        uint32_t nb = 0;
+        if (int r = count_bound(m, &nb)) return r;
+        rc[k].surfels = m->buf[m->target]; rc[k].count = m->d_count; rc[k].count_bound = nb; rc[k].theta = cands[k].conf_threshold;
+        inv44f(cands[k].pose, rc[k].t_inv);
+    }
+    RedetectFrame rf{f->depth, f->label, f->cols, f->rows, f->cam, f->new_label, f->depth_cutoff, f->depth_tol};
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[0], s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_redetect_counts, 0, n_counts * sizeof(unsigned), s));
+    // (the bitmaps are laid out with the words of THIS call: any prefix of the zeroed allocation)
+    launch_redetect_score(s, rc, n, rf, ctx->d_redetect_bits, words, ctx->d_redetect_counts);
+    LAUNCHCHK(ctx);
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[1], s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_redetect_counts, ctx->d_redetect_counts, n_counts * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventElapsedTime(&ctx->redetect_last_ms, ctx->redetect_ev[0], ctx->redetect_ev[1]));
+    for (int k = 0; k < n; k++) {
+        const unsigned* w = ctx->h_redetect_counts + (size_t)k * kRedetectWords;
+        counts[k] = cf_redetect_counts{w[0], w[1], w[2], w[3], w[4], w[5]};
+    }
+    if (label_pixels) *label_pixels = ctx->h_redetect_counts[(size_t)kRedetectBatch * kRedetectWords];
+    return CF_OK;
+}
+
+int cf_redetect_timing(cf_ctx* ctx, int on, float* last_ms)
+{
+    if (!ctx) return CF_EINVAL;
+    if (on) for (hipEvent_t& e : ctx->redetect_ev) if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    ctx->redetect_timing = on != 0;
+    if (last_ms) *last_ms = ctx->redetect_last_ms;
+    return CF_OK;
+}
+
+int cf_relabel(cf_ctx* ctx, uint8_t* label_dev, uint64_t n, int from, int to)
+{
+    if (!ctx || !label_dev || from < 0 || from > 255 || to < 0 || to > 255 || (reinterpret_cast<uintptr_t>(label_dev) & 15u)) return CF_EINVAL;
+    if (from == to || n == 0) return CF_OK;
+    launch_relabel(ctx->cur(), label_dev, n, (unsigned)from, (unsigned)to);
+    LAUNCHCHK(ctx);
+    return CF_OK;
+}
+
 // Model::computeFusionWeight (Model.cpp:391-406) + Model::rodrigues2 (Model.cpp:817-865); host math.
 // The JacobiSVD re-orthonormalisation of rodrigues2 is the identity for rotation products.
 float cf_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier)

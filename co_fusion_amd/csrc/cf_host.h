@@ -67,6 +67,11 @@ struct cf_ctx {
     hipEvent_t surf_events[kSurfEvents]{};
     int surf_used = 0; unsigned surf_calls_seen = 0;
     double surf_ms_accum = 0; uint64_t surf_calls = 0, surf_bytes = 0;
+    // cf_redetect_score (created at first use): the candidates' pixel bitmaps [kRedetectBatch][redetect_words] -- zero between calls, the
+    // finishing kernel clears what it counts --, the counters and their pinned read-back
+    unsigned* d_redetect_bits = nullptr; unsigned redetect_words = 0;
+    unsigned* d_redetect_counts = nullptr; unsigned* h_redetect_counts = nullptr;
+    bool redetect_timing = false; hipEvent_t redetect_ev[2]{}; float redetect_last_ms = 0.f;   // cf_redetect_timing
     void set_error(const std::string& m);
 };
 extern "C" int cf_wait_stream(cf_ctx* ctx);   // the frame's host wait (cabi.hip)

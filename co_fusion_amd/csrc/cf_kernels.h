@@ -453,4 +453,20 @@ void launch_clean(hipStream_t s, const float* surfels, const unsigned* count, co
                   const SurfelCleanArgs& h, float* staged, unsigned* flags);
 void launch_set_count(hipStream_t s, unsigned* out, unsigned v);
 
+// ---- re-detection launchers (redetect.hip) ----
+constexpr int kRedetectBatch = 16;   // candidates per score launch (their arguments travel in the kernel-argument segment)
+constexpr int kRedetectWords = 8;    // u32 per candidate: projected, occluded, seen_through, agree, agree_on_label, covered, 2 pad
+struct RedetectCand {    // one inactive map under its hypothesis pose
+    const float* surfels; const unsigned* count; unsigned count_bound;   // the device count, clamped to the host's bound
+    float theta;         // the model's confidence threshold: surfels below it take no part
+    float t_inv[16];     // inverse of the hypothesis pose (inv44f on the host, as the index pass)
+};
+struct RedetectFrame {   // what the candidates are scored against
+    const float* depth; const uint8_t* label; int cols, rows; cf_cam cam; int new_label; float cutoff, tol;
+};
+// score + finish: counts [kRedetectBatch * kRedetectWords + 1] (the last word: pixels with label == new_label) must be zero on entry, the
+// bitmaps ([n][words], words = (cols * rows + 31) / 32) are zero on entry and are left zero
+void launch_redetect_score(hipStream_t s, const RedetectCand* cands, int n, const RedetectFrame& f, unsigned* bits, unsigned words, unsigned* counts);
+void launch_relabel(hipStream_t s, uint8_t* label /* 16-byte aligned */, unsigned long long n, unsigned from, unsigned to);
+
 }  // namespace cf

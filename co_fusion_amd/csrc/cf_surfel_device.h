@@ -97,6 +97,19 @@ __device__ __forceinline__ f3 xform_dir(const Mat4& T, f3 p)
               T.m[8] * p.x + T.m[9] * p.y + T.m[10] * p.z};
 }
 
+// index_map.vert:38-63 without its time window: a surfel position into the camera of t_inv, onto its pixel q.  Shared by the index pass
+// (surfel.hip: index_project) and the re-detection score (redetect.hip), which must land every surfel on the same pixel.
+__device__ __forceinline__ bool surfel_project(const float4 pc, const Mat4& t_inv, cf_cam cam, int cols, int rows, float maxDepth, f3& ph, int& q)
+{
+    ph = xform_point(t_inv, f3{pc.x, pc.y, pc.z});
+    if (ph.z > maxDepth || ph.z < 0) return false;
+    const float u = ((cam.fx * ph.x) / ph.z) + cam.cx, v = ((cam.fy * ph.y) / ph.z) + cam.cy;
+    if (!(u >= 0.0f && v >= 0.0f && u < (float)cols && v < (float)rows)) return false;
+    if (!(ph.z < maxDepth)) return false;  // depth buffer cleared to 1.0, GL_LESS
+    q = (int)floorf(v) * cols + (int)floorf(u);
+    return true;
+}
+
 // LINEAR RGBA32F fetch, clamp to edge
 __device__ __forceinline__ float4 tex4_linear(const float4* __restrict__ img, int cols, int rows, float u, float v)
 {

@@ -310,13 +310,8 @@ __global__ void __launch_bounds__(kB) init_kernel(const float4* __restrict__ raw
 __device__ __forceinline__ bool index_project(const float4 pc, const float4 ct, const Mat4& t_inv, cf_cam cam, int cols, int rows,
                                               float maxDepth, int time, int timeDelta, f3& ph, int& q)
 {
-    ph = xform_point(t_inv, f3{pc.x, pc.y, pc.z});
-    if (ph.z > maxDepth || ph.z < 0 || (float)time - ct.w > (float)timeDelta) return false;
-    const float u = ((cam.fx * ph.x) / ph.z) + cam.cx, v = ((cam.fy * ph.y) / ph.z) + cam.cy;
-    if (!(u >= 0.0f && v >= 0.0f && u < (float)cols && v < (float)rows)) return false;
-    if (!(ph.z < maxDepth)) return false;  // depth buffer cleared to 1.0, GL_LESS
-    q = (int)floorf(v) * cols + (int)floorf(u);
-    return true;
+    if ((float)time - ct.w > (float)timeDelta) return false;
+    return surfel_project(pc, t_inv, cam, cols, rows, maxDepth, ph, q);   // (cf_surfel_device.h)
 }
 
 struct IndexArgs {   // predictIndices of one model (both kernels)

@@ -23,6 +23,12 @@ class Config(C.Structure):
                 ("colocate_background", C.c_int), ("reloc", C.c_int), ("early_index_maps", C.c_int)]
 
 
+class RedetectCandidate(C.Structure):
+    """cofusion_redetect_candidate (include/cofusion.h)"""
+    _fields_ = [("id", C.c_uint), ("projected", C.c_uint32), ("occluded", C.c_uint32), ("seen_through", C.c_uint32), ("agree", C.c_uint32),
+                ("agree_on_label", C.c_uint32), ("covered", C.c_uint32), ("fit", C.c_float), ("cover", C.c_float), ("eligible", C.c_int)]
+
+
 class CoFusionError(RuntimeError):
     pass
 
@@ -352,6 +358,37 @@ class CoFusion:
         k = C.c_int(); c = C.c_int(); r = C.c_int(); f = C.c_int()
         self._check(self.lib.cofusion_reloc_stats(self.h, C.byref(k), C.byref(c), C.byref(r), C.byref(f)))
         return dict(keyframes=k.value, last_closest=c.value, recoveries=r.value, database_full=bool(f.value))
+
+    def set_redetection(self, on=True, min_fit=0.5, min_cover=0.044, depth_tol=0.10, max_candidates=8, keep_min_surfels=4000,
+                        keep_conf_threshold=0.3):
+        """Re-detection of inactive object models (cofusion_set_redetection): a frame with a new label scores the most
+        recent `max_candidates` kept models, each where it would be had it not moved in the world, before anything is spawned; a
+        candidate with fit >= min_fit and cover >= min_cover comes back with its old id and map.  keep_*: the rule by which a
+        deactivated model is kept at all.  Off by default; world == 1 only; works on a sequence of a CoFusionGroup."""
+        f = C.c_float
+        self._check(self.lib.cofusion_set_redetection(self.h, int(bool(on)), f(min_fit), f(min_cover), f(depth_tol), int(max_candidates),
+                                                      int(keep_min_surfels), f(keep_conf_threshold)))
+
+    def redetect_stats(self):
+        a = C.c_int(); r = C.c_int(); i = C.c_int()
+        self._check(self.lib.cofusion_redetect_stats(self.h, C.byref(a), C.byref(r), C.byref(i)))
+        return dict(attempts=a.value, reactivations=r.value, last_id=i.value)
+
+    def redetect_last(self):
+        """the last attempt: dict(label_pixels, winner (position or -1), candidates=[dict(id, projected, occluded, seen_through, agree,
+        agree_on_label, covered, fit, cover, eligible)] in list order)"""
+        cap = 16
+        out = (RedetectCandidate * cap)()
+        n = C.c_int(); px = C.c_uint32(); w = C.c_int()
+        self._check(self.lib.cofusion_redetect_last(self.h, out, cap, C.byref(n), C.byref(px), C.byref(w)))
+        cands = [{k: getattr(out[q], k) for k, _ in RedetectCandidate._fields_} for q in range(min(n.value, cap))]
+        for c in cands:
+            c["eligible"] = bool(c["eligible"])
+        return dict(label_pixels=px.value, winner=w.value, candidates=cands)
+
+    @property
+    def num_inactive_models(self):
+        return self.lib.cofusion_num_inactive_models(self.h)
 
     def model_info(self, index):
         mid = C.c_uint(); cnt = C.c_uint(); conf = C.c_float(); pose = (C.c_float * 16)()

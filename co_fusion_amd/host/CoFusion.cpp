@@ -433,6 +433,7 @@ SegmentationResult Segmentation::finishMasks()
     int value = -1;
     check(ctx, cf_seg_new_mask_value(seg, &value), "cf_seg_new_mask_value");
     if (value >= 0) gtMapping[value & 255] = pendingNextId;   // Segmentation.cpp:80: the function-static mapping of the reference
+    lastNewValue = value;
     return resultRows(r, false);
 }
 
@@ -454,6 +455,7 @@ SegmentationResult Segmentation::finishCRF()
     SegmentationResult result = resultRows(r, true);
     result.depthRange = r.depth_range;
     result.lowMap = std::move(lowMap);
+    lastNewValue = -1;
     return result;
 }
 
@@ -470,11 +472,12 @@ SegmentationResult Segmentation::performSegmentationGT(ModelList& models, const 
     int mIndex = 0;
     for (auto& m : models) modelIdToIndex[m->getID() & 255] = mIndex++;
     modelIdToIndex[nextModelID] = mIndex;
+    lastNewValue = -1;
     for (size_t i = 0; i < N; i++) {
         const uint8_t vIn = frame.mask[i];
         if (vIn) {
             if (gtMapping[vIn] != 0) { full[i] = gtMapping[vIn]; outIds[full[i]]++; }
-            else if (allowNew && !result.hasNewLabel) { full[i] = nextModelID; gtMapping[vIn] = nextModelID; result.hasNewLabel = true; outIds[full[i]]++; }
+            else if (allowNew && !result.hasNewLabel) { full[i] = nextModelID; gtMapping[vIn] = nextModelID; lastNewValue = vIn; result.hasNewLabel = true; outIds[full[i]]++; }
         } else outIds[0]++;
     }
     int idx = 0;
@@ -684,7 +687,81 @@ ModelList::iterator CoFusion::inactivateModel(ModelList::iterator it)
     dist.sum(&count, 1);
     if (!enableSmartModelDelete || ((unsigned)count >= modelKeepMinSurfels && m->getConfidenceThreshold() > modelKeepConfThreshold))
         inactiveModels.push_back(m);
+    if (redetect.on) {
+        // where the object stood in the world, in the convention of the pose log (frameEnd): G * M^-1
+        m->worldPoseAtDeactivation = globalModel->getPose() * m->getPose().inverse();
+        // label masks: the value that stood for this model may propose a label again (otherwise it points at a dead id for good)
+        labelGenerator->forgetModel((unsigned char)m->getID());
+    }
     return --models.erase(it);
+}
+
+void CoFusion::setRedetection(bool on, float minFit, float minCover, float depthTol, int maxCandidates, unsigned keepMinSurfels, float keepConfThreshold)
+{
+    if (on && dist.active()) throw std::runtime_error("setRedetection: re-detection is a single-process option (world == 1): a model-parallel instance keeps a model's map on one rank only");
+    if (on && (maxCandidates < 1 || maxCandidates > 16)) throw std::runtime_error("setRedetection: 1..16 candidates");
+    if (on && !(depthTol >= 0.f)) throw std::runtime_error("setRedetection: the depth tolerance must not be negative");
+    redetect.on = on; redetect.minFit = minFit; redetect.minCover = minCover; redetect.depthTol = depthTol; redetect.maxCandidates = maxCandidates;
+    modelKeepMinSurfels = keepMinSurfels; modelKeepConfThreshold = keepConfThreshold;
+    redetectSt = RedetectStats{}; redetectCands.clear(); redetectLabelPixels = 0; redetectWinner = -1;
+}
+
+// The body the reference removed (CoFusion.cpp:599-602).  Hypothesis: the object has not moved in the world since it was deactivated.
+// Its world pose then was O = G_d * M_d^-1 (inactivateModel), now it is G_now * M_now^-1, so M_now = O^-1 * G_now.  The candidates --
+// the most recent maxCandidates inactive models -- are scored in ONE launch against the frame's raw depth and its label image, which
+// holds `newLabel` where the segmentation saw something new (cf_redetect_score: the frame's one extra host wait); the decision is
+// taken here: fit and cover at or above their thresholds, the largest agree_on_label wins, ties go to the earlier list position.
+ModelPointer CoFusion::redetectModels(unsigned char newLabel)
+{
+    std::vector<ModelList::iterator> cand;
+    {
+        size_t skip = inactiveModels.size() > (size_t)redetect.maxCandidates ? inactiveModels.size() - (size_t)redetect.maxCandidates : 0;
+        for (auto it = inactiveModels.begin(); it != inactiveModels.end(); ++it) {
+            if (skip) { skip--; continue; }
+            bool idInUse = false;   // (ids wrap after 255 spawns: an active model may carry a kept model's id by now)
+            for (auto& a : models) idInUse = idInUse || a->getID() == (*it)->getID();
+            if ((*it)->isOwned() && !idInUse) cand.push_back(it);
+        }
+    }
+    redetectCands.clear(); redetectLabelPixels = 0; redetectWinner = -1;
+    if (cand.empty()) return nullptr;
+    redetectSt.attempts++;
+    const Mat4f& G = globalModel->getPose();
+    std::vector<cf_redetect_candidate> in(cand.size());
+    std::vector<Mat4f> hyp(cand.size());
+    for (size_t k = 0; k < cand.size(); k++) {
+        Model& m = **cand[k];
+        hyp[k] = m.worldPoseAtDeactivation.inverse() * G;
+        in[k].model = m.model; memcpy(in[k].pose, hyp[k].m, sizeof(in[k].pose)); in[k].conf_threshold = m.getConfidenceThreshold();
+    }
+    cf_redetect_frame f{};
+    f.depth = curDepth; f.label = mask_dev; f.cols = cfg.width; f.rows = cfg.height; f.cam = cf_cam{cfg.fx, cfg.fy, cfg.cx, cfg.cy};
+    f.new_label = (int)newLabel; f.depth_cutoff = maxDepthProcessed; f.depth_tol = redetect.depthTol;
+    std::vector<cf_redetect_counts> counts(cand.size());
+    check(ctx, cf_redetect_score(ctx, in.data(), (int)in.size(), &f, counts.data(), &redetectLabelPixels), "cf_redetect_score");
+    for (size_t k = 0; k < cand.size(); k++) {
+        RedetectCandidate r{};
+        r.id = (*cand[k])->getID(); r.counts = counts[k];
+        const uint32_t seen = counts[k].agree + counts[k].seen_through;
+        r.fit = seen ? (float)counts[k].agree_on_label / (float)seen : 0.f;
+        r.cover = redetectLabelPixels ? (float)counts[k].covered / (float)redetectLabelPixels : 0.f;
+        r.eligible = seen != 0 && redetectLabelPixels != 0 && r.fit >= redetect.minFit && r.cover >= redetect.minCover;
+        if (r.eligible && (redetectWinner < 0 || counts[k].agree_on_label > counts[(size_t)redetectWinner].agree_on_label)) redetectWinner = (int)k;
+        redetectCands.push_back(r);
+    }
+    if (redetectWinner < 0) return nullptr;
+    ModelPointer m = *cand[(size_t)redetectWinner];
+    inactiveModels.erase(cand[(size_t)redetectWinner]);
+    m->overridePose(hyp[(size_t)redetectWinner]);
+    m->resetUnseenCount();
+    m->predictOnlyThisFrame = true;
+    // the tracker starts over as a spawned model's does (spawnObjectModel); the end-of-frame prediction gives it its model maps
+    check(ctx, cf_odom_init_first_rgb(m->getFrameOdometry(), curRgba), "initFirstRGB");
+    // every later consumer of this frame's label image -- the other models' fusion, exports, the caller -- sees the old id
+    check(ctx, cf_relabel(ctx, mask_dev, (uint64_t)cfg.width * cfg.height, (int)newLabel, (int)m->getID()), "cf_relabel");
+    labelGenerator->remapNewValue((unsigned char)m->getID());
+    redetectSt.reactivations++; redetectSt.lastId = (int)m->getID();
+    return m;
 }
 
 void CoFusion::predict(bool lastOfFrame)
@@ -730,7 +807,7 @@ void CoFusion::frameFuseCollect(std::vector<cf_model_pass>& items)
     for (auto& m : models) {
         cf_model_pass it{};
         it.model = m->model; it.pose = m->pose.m; it.rgba = curRgba; it.mask = mask_dev; it.depth_raw = curDepth; it.depth_filtered = depthFiltered_dev;
-        it.do_fuse = st.fuseNow ? 1 : 0; it.time = tick;
+        it.do_fuse = (st.fuseNow && !m->predictOnlyThisFrame) ? 1 : 0; it.time = tick;   // (a model reactivated in this frame: prediction only)
         it.fuse_max_depth = maxDepthProcessed < m->getMaxDepth() ? maxDepthProcessed : m->getMaxDepth();  // std::min(depthCutoff, maxDepth), Model.cpp:443
         it.weighting = m->computeFusionWeight(st.weightMultiplier); it.mask_id = (int)m->getID(); it.conf_threshold = m->getConfidenceThreshold();
         items.push_back(it);
@@ -758,7 +835,7 @@ void CoFusion::fuseAndPredict(bool fuse, float weightMultiplier, bool lost, bool
     const bool overlap = (models.size() > 1 || !join) && useLanes;
     if (!overlap) {
         check(ctx, cf_join(ctx), "cf_join");  // (an index map enqueued on a lane before a deactivation left one model: order the stream after it)
-        for (auto& model : models) modelPasses(*model, fuse, weightMultiplier, lost);
+        for (auto& model : models) modelPasses(*model, fuse && !model->predictOnlyThisFrame, weightMultiplier, lost);
         return;
     }
     std::vector<Model*> list;
@@ -771,7 +848,7 @@ void CoFusion::fuseAndPredict(bool fuse, float weightMultiplier, bool lost, bool
         for (int i = 0; i < n; i++) {
             // a model whose first index map is already queued on a lane continues on that lane (stream order is the dependency)
             check(ctx, cf_fork(ctx, (laneOffset + i) % lanes), "cf_fork");
-            modelPasses(*list[i], fuse, weightMultiplier, lost);
+            modelPasses(*list[i], fuse && !list[i]->predictOnlyThisFrame, weightMultiplier, lost);
         }
         if (join) check(ctx, cf_join(ctx), "cf_join");
         else check(ctx, cf_main(ctx), "cf_main");
@@ -785,7 +862,7 @@ void CoFusion::fuseAndPredict(bool fuse, float weightMultiplier, bool lost, bool
         pool->run(n, [&](int i) {
             Unbind u{ctx};
             check(ctx, cf_thread_lane(ctx, i % lanes), "cf_thread_lane");
-            modelPasses(*list[i], fuse, weightMultiplier, lost);
+            modelPasses(*list[i], fuse && !list[i]->predictOnlyThisFrame, weightMultiplier, lost);
         });
     } catch (...) { failed = std::current_exception(); }
     check(ctx, cf_join(ctx), "cf_join");
@@ -1069,6 +1146,10 @@ void CoFusion::frameCollect()
             if (segOnDevice) seg = labelGenerator->finishCRF();
             else if (st.masksOnDevice) seg = labelGenerator->finishMasks();
             else seg = labelGenerator->performSegmentationGT(models, frame, getNextModelID(), allowNew, mask_dev);   // a host mask (frame.mask)
+            // setRedetection: does a kept inactive model explain the new label?  Then it comes back instead of a spawn (no id is consumed).
+            // Ahead of the export below: an accepted model rewrites the label image to its old id
+            ModelPointer back;
+            if (seg.hasNewLabel && redetect.on && !inactiveModels.empty()) back = redetectModels(getNextModelID());
             if (!exportSegmentationPrefix.empty() && exportWriter) {   // (setExportAsync: the same image, encoded on the device)
                 exportWriter->submit(exportSegmentationPrefix + "Segmentation" + std::to_string(tick) + ".png", mask_dev, cfg.width, cfg.height, 1,
                                      CF_PNG_LABELS);
@@ -1078,7 +1159,10 @@ void CoFusion::frameCollect()
                 for (auto& v : labels) if (v > 254) v = 0;
                 writePngGray8(exportSegmentationPrefix + "Segmentation" + std::to_string(tick) + ".png", labels.data(), cfg.width, cfg.height);
             }
-            if (seg.hasNewLabel) {
+            if (back) {
+                spawnOffset = 0;
+                back->setMaxDepth(getMaxDepth(seg.modelData.back()));
+            } else if (seg.hasNewLabel) {
                 spawnObjectModel();
                 spawnOffset = 0;
                 newModel->setMaxDepth(getMaxDepth(seg.modelData.back()));
@@ -1087,7 +1171,8 @@ void CoFusion::frameCollect()
                 auto it = models.begin();
                 for (unsigned i = 1; i < models.size(); i++) (*++it)->setMaxDepth(getMaxDepth(seg.modelData[i]));
             }
-            if (seg.hasNewLabel) {
+            if (back) models.push_back(back);   // (where a spawned model goes; its map is left alone this frame: Model::predictOnlyThisFrame)
+            else if (seg.hasNewLabel) {
                 newModel->predictIndices(tick, maxDepthProcessed, cfg.timeDelta);
                 newModel->fuse(tick, curRgba, mask_dev, curDepth, depthFiltered_dev, maxDepthProcessed, 100);
                 newModel->clean(tick, cfg.timeDelta, maxDepthProcessed, depthFiltered_dev, mask_dev, cfg.outlierCoefficient);
@@ -1135,6 +1220,7 @@ void CoFusion::frameEnd()
     phaseTimes().frames++;
     if (!lost) tick++;
     moveNewModelToList();
+    for (auto& model : models) model->predictOnlyThisFrame = false;
 
     bool first = true;
     for (auto& model : models) {  // pose log, CoFusion.cpp:502-520

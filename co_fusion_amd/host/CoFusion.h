@@ -149,6 +149,10 @@ class Model {
     const float* vertexConfProjection() const;
     cf_track_stats lastStats{};
     bool isOwned() const { return owned; }
+    // re-detection (CoFusion::setRedetection): the object's pose in the world, G * M^-1 as in the pose log, when it was deactivated ...
+    Mat4f worldPoseAtDeactivation = Mat4f::identity();
+    // ... and, one frame long, "reactivated in this frame": no index map, fusion or clean-up, the end-of-frame prediction only
+    bool predictOnlyThisFrame = false;
     // split over the ranks (background replica): shard index / count, 0 / 1 when the model lives on one rank
     int shard = 0, shards = 1;
 
@@ -216,6 +220,10 @@ class Segmentation {
     // model-parallel operation: enqueueCRF put every owner's tracked pose behind the sums it all-reduces; after the frame's host wait
     // this hands out [models][18] words (pose row-major, ICP error, ICP inlier count as f32 bit patterns).  false: nothing was published
     bool fetchPublishedPoses(size_t nModels, std::vector<int64_t>& words);
+    // label-mask mode under re-detection: the mask value that proposed this frame's new label is mapped to `id` instead (a reactivated
+    // model keeps its old id); every value that maps to `id` is forgotten (a deactivated model: the value may propose a label again)
+    void remapNewValue(unsigned char id) { if (lastNewValue > 0) gtMapping[lastNewValue & 255] = id; }
+    void forgetModel(unsigned char id) { for (int v = 1; v < 256; v++) if (gtMapping[v] == id) gtMapping[v] = 0; }
     // setters (Segmentation.h:100-120); defaults are the GUI values the reference applies every frame (GUI.h:206-227)
     float unaryWeightError = 75.f, unaryKError = 0.0375f, unaryThresholdNew = 5.5f;
     float weightAppearance = 7.f, weightSmoothness = 2.f;
@@ -233,6 +241,7 @@ class Segmentation {
     bool slicStarted = false;
     int pendingModels = 0;        // models of the segmentation enqueueCRF / enqueueMasks left in flight
     unsigned char pendingNextId = 0;  // the id a new label of the mask job in flight would get
+    int lastNewValue = -1;            // the mask value that proposed the last frame's new label (-1: none, or the motion segmentation)
     bool posesPublished = false;  // ... which carries the owners' poses in its all-reduce
     float* zeroImage = nullptr;   // device zeros [H*W*4] standing in for the ICP error / confidence maps of shadow models
     std::vector<const float*> jobIcp, jobConf;  // collectCRF's arrays
@@ -349,6 +358,27 @@ class CoFusion {
                            uint64_t seed = 0, int capacity = 1024);
     void relocStats(int* keyframes, int* lastClosest, int* recoveries, int* databaseFull);
     bool isGroupSequence() const { return !ownsCtx; }
+    // Re-detection of inactive models (the reference's redetectModels is empty, CoFusion.cpp:599-602).  Off by default;
+    // with it off the frame loop is what it was.  On: a frame whose segmentation reports a new label scores the most recent
+    // `maxCandidates` (1..16) inactive models against the frame (cf_redetect_score), each at the pose it would have now had it not
+    // moved in the world since it was deactivated, BEFORE a model is spawned.  fit = agree_on_label / (agree + seen_through) >= minFit
+    // and cover = covered / label_pixels >= minCover make a candidate eligible; the one with the largest agree_on_label (ties: the
+    // earlier in the list) is reactivated with its old id, map, confidence threshold and pose log instead of a spawn.  One more host
+    // wait in such a frame.  keepMinSurfels / keepConfThreshold: the rule by which a deactivated model is kept at all (4000 / 0.3).
+    // Single process only (throws for a model-parallel instance); works for a sequence of a lock-step group.
+    void setRedetection(bool on, float minFit = 0.5f, float minCover = 0.044f, float depthTol = 0.10f, int maxCandidates = 8,
+                        unsigned keepMinSurfels = 4000, float keepConfThreshold = 0.3f);
+    struct RedetectCandidate { unsigned id; cf_redetect_counts counts; float fit, cover; bool eligible; };
+    struct RedetectStats { int attempts = 0, reactivations = 0, lastId = -1; };
+    const RedetectStats& redetectStats() const { return redetectSt; }
+    // the candidates of the last attempt in list order, the number of pixels its new label had, the position of the winner (-1: none)
+    const std::vector<RedetectCandidate>& redetectLast(uint32_t* labelPixels = nullptr, int* winner = nullptr) const
+    {
+        if (labelPixels) *labelPixels = redetectLabelPixels;
+        if (winner) *winner = redetectWinner;
+        return redetectCands;
+    }
+    size_t numInactiveModels() const { return inactiveModels.size(); }
     // The motion-CRF chain's tracking-independent half beside the tracking launches (Segmentation::startEarly).  On by default; off
     // leaves the whole chain behind the tracker -- the same results bit for bit, for A/B measurements and parity tests.
     void setSegEarly(bool on) { segEarly = on; }
@@ -395,6 +425,14 @@ class CoFusion {
     int markBase = 0;   // this sequence's four event slots of the context (cf_mark)
     void trackCollect(TrackBatch& batch, const float* const depthPyr[3]);
     void spawnObjectModel();
+    // CoFusion::redetectModels (the name the reference left empty): scores the candidates against the current frame, whose label image
+    // holds `newLabel`; returns the accepted model, taken out of inactiveModels with its hypothesis pose set, or null
+    ModelPointer redetectModels(unsigned char newLabel);
+    struct { bool on = false; float minFit = 0.5f, minCover = 0.044f, depthTol = 0.10f; int maxCandidates = 8; } redetect;
+    RedetectStats redetectSt;
+    std::vector<RedetectCandidate> redetectCands;
+    uint32_t redetectLabelPixels = 0;
+    int redetectWinner = -1;
     void moveNewModelToList();
     ModelList::iterator inactivateModel(ModelList::iterator it);
     unsigned char getNextModelID(bool assign = false);

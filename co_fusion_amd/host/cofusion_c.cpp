@@ -125,6 +125,37 @@ int cofusion_set_relocalisation(cofusion_handle* h, int on, int n_ferns, float f
                                    photo_threshold > 0 ? photo_threshold : 115.0f, min_age >= 0 ? min_age : 300, seed, capacity > 0 ? capacity : 1024));
     return 0;
 }
+int cofusion_set_redetection(cofusion_handle* h, int on, float min_fit, float min_cover, float depth_tol, int max_candidates, int keep_min_surfels,
+                             float keep_conf_threshold)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    GUARD(h->cf->setRedetection(on != 0, min_fit >= 0 ? min_fit : 0.5f, min_cover >= 0 ? min_cover : 0.044f, depth_tol >= 0 ? depth_tol : 0.10f,
+                                max_candidates > 0 ? max_candidates : 8, keep_min_surfels >= 0 ? (unsigned)keep_min_surfels : 4000u,
+                                keep_conf_threshold >= 0 ? keep_conf_threshold : 0.3f));
+    return 0;
+}
+int cofusion_redetect_stats(cofusion_handle* h, int* attempts, int* reactivations, int* last_id)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    const CoFusion::RedetectStats& s = h->cf->redetectStats();
+    if (attempts) *attempts = s.attempts;
+    if (reactivations) *reactivations = s.reactivations;
+    if (last_id) *last_id = s.lastId;
+    return 0;
+}
+int cofusion_redetect_last(cofusion_handle* h, cofusion_redetect_candidate* out, int capacity, int* n, uint32_t* label_pixels, int* winner)
+{
+    if (!h || !n) { g_err = "cofusion_redetect_last: bad arguments"; return -1; }
+    const std::vector<CoFusion::RedetectCandidate>& c = h->cf->redetectLast(label_pixels, winner);
+    *n = (int)c.size();
+    for (int k = 0; out && k < capacity && k < (int)c.size(); k++) {
+        const cf_redetect_counts& q = c[(size_t)k].counts;
+        out[k] = cofusion_redetect_candidate{c[(size_t)k].id, q.projected, q.occluded, q.seen_through, q.agree, q.agree_on_label, q.covered,
+                                             c[(size_t)k].fit, c[(size_t)k].cover, c[(size_t)k].eligible ? 1 : 0};
+    }
+    return 0;
+}
+int cofusion_num_inactive_models(cofusion_handle* h) { return h ? (int)h->cf->numInactiveModels() : -1; }
 int cofusion_reloc_stats(cofusion_handle* h, int* keyframes, int* last_closest, int* recoveries, int* database_full)
 {
     if (!h) { g_err = "null handle"; return -1; }

@@ -27,6 +27,7 @@ SYMBOLS = [
     "cf_bilateral", "cf_model_create", "cf_model_destroy", "cf_model_initialise", "cf_model_count",
     "cf_model_predict_indices", "cf_model_index_keys", "cf_model_index_resolve", "cf_model_combined_predict", "cf_model_prefetch_fill_ratio", "cf_model_perform_fill_in", "cf_model_requires_fill_in",
     "cf_model_fuse", "cf_model_clean", "cf_models_frame_passes", "cf_models_preindex", "cf_model_download_map", "cf_model_upload_map", "cf_model_buffer",
+    "cf_redetect_score", "cf_redetect_timing", "cf_relabel",
     "cf_fusion_weight", "cf_seg_create", "cf_seg_destroy", "cf_seg_slic", "cf_seg_crf", "cf_seg_sums", "cf_seg_infer", "cf_seg_early", "cf_seg_run_batch", "cf_seg_fetch", "cf_seg_publish_poses", "cf_seg_fetch_poses",
     "cf_seg_labels", "cf_seg_create_masks", "cf_seg_masks", "cf_seg_masks_batch", "cf_seg_new_mask_value",
     "cf_depth_pyramid", "cf_set_icp_launch", "cf_set_icp_arith", "cf_get_icp_arith", "cf_set_gn_mode", "cf_profile_enable", "cf_profile_read", "cf_odom_bench_icp", "cf_odom_level0_visited", "cf_odom_last_launch_shape",
@@ -62,6 +63,7 @@ HOST_SYMBOLS = [
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
     "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats",
+    "cofusion_set_redetection", "cofusion_redetect_stats", "cofusion_redetect_last", "cofusion_num_inactive_models",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",
     "cofusion_image_reader_open", "cofusion_image_reader_next", "cofusion_image_reader_rewind", "cofusion_image_reader_close",

@@ -88,6 +88,39 @@ int cofusion_set_relocalisation(cofusion_handle *h, int on, int n_ferns, float f
 /* keyframes in the database, the keyframe the last relocalisation accepted (-1: none), lost -> tracked transitions so far, 1 when an
  * append was dropped because the database is full; each nullable.  Waits for the stream. */
 int cofusion_reloc_stats(cofusion_handle *h, int *keyframes, int *last_closest, int *recoveries, int *database_full);
+/* Re-detection of inactive object models (the reference's CoFusion::redetectModels is an empty hook, CoFusion.cpp:599-602).
+ * A model whose label gets no superpixels is deactivated; kept models (surfel count >= keep_min_surfels and confidence threshold >
+ * keep_conf_threshold -- 4000 / 0.3, the reference's rule) wait in a list.  Off (the default) nothing reads that list: an object that
+ * is labelled again is spawned as an empty map under a new id.  On: a frame whose segmentation reports a new label scores the most
+ * recent max_candidates (1..16, default 8) kept models against it before anything is spawned, each at the pose it would have now HAD
+ * IT NOT MOVED IN THE WORLD since it was deactivated (M_now = (G_d M_d^-1)^-1 G_now).  Per candidate (cf_redetect_score, cofusion_hip.h),
+ * over its stable surfels projected into the frame:
+ *     fit   = agree_on_label / (agree + seen_through)     surfels whose depth agrees within depth_tol AND whose pixel has the new label,
+ *                                                         of those the frame could have seen (occluded ones are neutral)
+ *     cover = covered / label_pixels                      distinct pixels of the new label the map explains
+ * A candidate with fit >= min_fit and cover >= min_cover is eligible; the one with the largest agree_on_label (ties: the earlier in the
+ * list) is reactivated -- old id, map, confidence threshold and pose log; no id is consumed; the frame's label image is rewritten to the
+ * old id; with label masks the mask value is mapped to the old id.  In that frame its map is not touched (prediction only); the next
+ * frame's tracker refines the pose, which has to pull it in from anywhere inside depth_tol (default 0.10 m, the tracker's own
+ * correspondence gate).  Nobody eligible: the frame spawns as before.  Costs such a frame one more host wait.
+ * Limits: an object that moved further than the gate while unseen is spawned anew; with a finite time window (not the default open
+ * loop) a map reactivated after more than that many ticks is outside the window of the index pass; refused for world > 1.
+ * Negative min_fit / min_cover / depth_tol / keep_* and max_candidates <= 0 select the defaults (0.5, 0.044, 0.10, 4000, 0.3, 8).  Works
+ * on a sequence handle of a lock-step group.  Calling it resets the statistics. */
+int cofusion_set_redetection(cofusion_handle *h, int on, float min_fit, float min_cover, float depth_tol, int max_candidates,
+                             int keep_min_surfels, float keep_conf_threshold);
+/* frames that scored candidates, reactivations, id of the last reactivated model (-1: none); each nullable */
+int cofusion_redetect_stats(cofusion_handle *h, int *attempts, int *reactivations, int *last_id);
+typedef struct {
+    unsigned id;
+    uint32_t projected, occluded, seen_through, agree, agree_on_label, covered;
+    float fit, cover;
+    int eligible;
+} cofusion_redetect_candidate;
+/* the candidates of the last attempt in list order (at most `capacity` are written, *n is their number), the pixels its new label had and
+ * the position of the accepted candidate (-1: none); out, label_pixels, winner nullable */
+int cofusion_redetect_last(cofusion_handle *h, cofusion_redetect_candidate *out, int capacity, int *n, uint32_t *label_pixels, int *winner);
+int cofusion_num_inactive_models(cofusion_handle *h);
 /* per model (list order, 0 = background): id, surfel count, pose T(model <- camera), confidence threshold */
 int cofusion_model_info(cofusion_handle *h, int index, unsigned *id, unsigned *count, float pose[16], float *conf_threshold);
 int cofusion_model_download(cofusion_handle *h, int index, float *surfels, uint32_t capacity, uint32_t *count);

@@ -440,6 +440,37 @@ int cf_model_upload_map(cf_model *m, const float *host_surfels, uint32_t count);
  *   13  the packed per-texel records cf_models_frame_passes leaves for its clean stage: vertConf | colorTime.z, colorTime.w, index (u32
  *       bits), filtered depth -- 32 bytes per texel (never written by the per-model calls) */
 int cf_model_buffer(cf_model *m, int which, void **dptr, uint64_t *bytes);
+/* Re-detection of inactive models (CoFusion::redetectModels; the reference left the hook empty, CoFusion.cpp:599-602):
+ * how well does a kept map, placed at a hypothesis pose, explain the pixels of a frame that carry a NEW label?  For every surfel i below
+ * the model's count with confidence >= conf_threshold: projected as the index pass projects it (index_map.vert:38-63 without the time
+ * window; rejects z < 0, z >= depth_cutoff, outside the image -- a rejected surfel counts nowhere) onto pixel q -> projected++; d =
+ * depth[q]; !(d > 0) or d > depth_cutoff: nothing more; d < z - depth_tol: occluded++; d > z + depth_tol: seen_through++; otherwise
+ * agree++ and, when label[q] == new_label, agree_on_label++ with pixel q marked.  covered = the number of DISTINCT marked pixels,
+ * label_pixels = pixels with label == new_label.  All counts are exact integers, independent of execution order.
+ * The image (depth f32 metres, 0 = invalid; label u8), its size and its camera are arguments: they need not be the context's.  One launch
+ * scores all candidates (n <= 16), a second one finishes the counts; enqueued on the context's stream, then waited for (the counts
+ * travel through pinned memory).  The models are only read. */
+typedef struct { uint32_t projected, occluded, seen_through, agree, agree_on_label, covered; } cf_redetect_counts;
+typedef struct {
+    cf_model *model;
+    float pose[16];          /* the hypothesis: row-major T(model <- camera), as cf_model_pass::pose */
+    float conf_threshold;
+} cf_redetect_candidate;
+typedef struct {
+    const float *depth;      /* device, [rows * cols] */
+    const uint8_t *label;    /* device, [rows * cols] */
+    int cols, rows;
+    cf_cam cam;
+    int new_label;
+    float depth_cutoff, depth_tol;
+} cf_redetect_frame;
+int cf_redetect_score(cf_ctx *ctx, const cf_redetect_candidate *candidates, int n, const cf_redetect_frame *frame, cf_redetect_counts *counts /* [n] */,
+                      uint32_t *label_pixels);
+/* measurement (tools/redetect_bench.py): on = 1 puts a device event in front of and behind the launches of every cf_redetect_score from
+ * here on (the counters' fill, the score and the finishing launch; not the read-back); last_ms (nullable): what the last call took */
+int cf_redetect_timing(cf_ctx *ctx, int on, float *last_ms);
+/* label_dev[i] == from -> to for i < n, 16 bytes per lane (label_dev: device, 16-byte aligned; from, to: 0..255); enqueued only */
+int cf_relabel(cf_ctx *ctx, uint8_t *label_dev, uint64_t n, int from, int to);
 /* Model::computeFusionWeight (Model.cpp:391-406); pure host math */
 float cf_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier);
 

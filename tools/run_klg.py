@@ -7,6 +7,7 @@ does head-less, GUI/MainController.cpp):
                             [--export-labels] [--export-normals] [--export-viewport] [--export-async [--export-workers N]]
                             [--player [--workers N]]
                             [--mask-dir DIR [--mask-prefix Mask --index-width 4]]
+                            [--redetect [--redetect-fit F --redetect-cover C --redetect-tol T]]
 
 Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png, out/Labels<tick>.png, out/Normals<tick>.png,
 out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s.  --export-async encodes those PNGs on
@@ -57,6 +58,11 @@ def main():
     ap.add_argument("--photo-threshold", type=float, default=115.0)
     ap.add_argument("--fern-min-age", type=int, default=300, help="ticks a keyframe must be old to be matched")
     ap.add_argument("--fern-seed", type=int, default=0)
+    ap.add_argument("--redetect", action="store_true", help="an object that is labelled again resumes its kept inactive model (old id and map) "
+                                                            "where that explains the frame, instead of a new model")
+    ap.add_argument("--redetect-fit", type=float, default=-1.0, help="least agree_on_label / (agree + seen_through) of a candidate (default 0.5)")
+    ap.add_argument("--redetect-cover", type=float, default=-1.0, help="least share of the new label's pixels a candidate must explain (default 0.044)")
+    ap.add_argument("--redetect-tol", type=float, default=-1.0, help="depth agreement in metres (default 0.10, the tracker's gate)")
     ap.add_argument("--player", action="store_true", help="threaded prefetch + JPEG finished on the device (default: the serial reader)")
     ap.add_argument("--workers", type=int, default=4, help="host threads of --player (1..16)")
     ap.add_argument("--mask-dir", default=None, help="directory of per-frame label masks (binary PGM or 8-bit grey PNG)")
@@ -93,6 +99,10 @@ def main():
                          enable_pose_logging=1, reloc=int(a.relocalise))
     if a.relocalise:
         cf.set_relocalisation(True, fern_threshold=a.fern_threshold, photo_threshold=a.photo_threshold, min_age=a.fern_min_age, seed=a.fern_seed)
+    if a.redetect:
+        if a.static:
+            raise SystemExit("--redetect needs the multi-model mode (no --static)")
+        cf.set_redetection(True, min_fit=a.redetect_fit, min_cover=a.redetect_cover, depth_tol=a.redetect_tol)   # (negative: the defaults)
     if a.export_segmentation and not a.static:
         cf.set_export_segmentation(prefix)
     if a.export_labels or a.export_normals or a.export_viewport:
@@ -159,6 +169,8 @@ def main():
     print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s {how}), {cf.num_models} active models")
     if a.relocalise:
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
+    if a.redetect:
+        print(f"re-detection: {cf.redetect_stats()}, {cf.num_inactive_models} inactive model(s) kept")
     if a.export_async:
         s = cf.export_stats()
         print(f"asynchronous exports: {s['images']} files, {s['bytes']} bytes, {s['stalls']} submits waited for a slot")
