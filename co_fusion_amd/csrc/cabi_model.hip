@@ -66,17 +66,7 @@ struct cf_model {
     float inv_fx = 0, inv_fy = 0;
 };
 
-template <typename T>
-static int dmalloc(cf_ctx* ctx, T** p, size_t count)
-{
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    HIPCHK(ctx, hipMemsetAsync(*p, 0, count * sizeof(T), ctx->cur()));
-    return CF_OK;
-}
-
 using cf::inv44f;   // (cf_kernels.h: shared with the device)
-
-static inline cf_cam ctx_cam(const cf_ctx* ctx) { return cf_cam{ctx->cfg.fx, ctx->cfg.fy, ctx->cfg.cx, ctx->cfg.cy}; }
 
 extern "C" {
 

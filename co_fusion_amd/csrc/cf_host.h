@@ -1,6 +1,8 @@
 // cf_host.h -- host-side object definitions behind the opaque C-ABI handles.
 #pragma once
 
+#include <string.h>
+
 #include <mutex>
 #include <string>
 
@@ -74,7 +76,8 @@ struct cf_ctx {
     bool redetect_timing = false; hipEvent_t redetect_ev[2]{}; float redetect_last_ms = 0.f;   // cf_redetect_timing
     void set_error(const std::string& m);
 };
-extern "C" int cf_wait_stream(cf_ctx* ctx);   // the frame's host wait (cabi.hip)
+inline cf_cam ctx_cam(const cf_ctx* ctx) { return cf_cam{ctx->cfg.fx, ctx->cfg.fy, ctx->cfg.cx, ctx->cfg.cy}; }
+extern "C" int cf_wait_stream(cf_ctx* ctx);   // the frame's host wait (cabi_track.hip)
 // A failed HIP call of a C-ABI entry point: its text and the runtime's message become the context's last error, the entry returns CF_EHIP
 #define HIPCHK(ctx, call)                                                                      \
     do {                                                                                       \
@@ -85,6 +88,20 @@ extern "C" int cf_wait_stream(cf_ctx* ctx);   // the frame's host wait (cabi.hip
         }                                                                                      \
     } while (0)
 #define LAUNCHCHK(ctx) HIPCHK(ctx, hipGetLastError())   // behind a chain of launches
+// a zero-filled device array of `count` elements (the fill is enqueued on the calling thread's stream, not waited for)
+template <typename T>
+inline int dmalloc(cf_ctx* ctx, T** p, size_t count)
+{
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
+    HIPCHK(ctx, hipMemsetAsync(*p, 0, count * sizeof(T), ctx->cur()));
+    return CF_OK;
+}
+// clears one [kGroups][32] accumulator of the reductions
+inline int clear_acc(cf_ctx* ctx, unsigned long long* acc)
+{
+    HIPCHK(ctx, hipMemsetAsync(acc, 0, sizeof(unsigned long long) * cf::kGroups * 32, ctx->stream));
+    return CF_OK;
+}
 struct cf_odom;
 namespace cf {
 // the reference-order tracker (track_ref.hip): RGBDOdometry::getIncrementalTransformation for one prepared tracker, host loop included
@@ -96,6 +113,14 @@ int ref_rgb_step(cf_ctx* ctx, const cf_dataterm* corres, float sigma, const floa
                  float sobel_scale, int cols, int rows, float out29[29]);
 int ref_so3_step(cf_ctx* ctx, const uint8_t* last_image, const uint8_t* next_image, const float basis[9], const float kinv[9], const float krlr[9],
                  int cols, int rows, float out11[11]);
+// a 4x4 row-major pose -> its rotation (row-major) and translation
+inline void pose_split(const float pose[16], float R[9], float t[3])
+{
+    for (int i = 0; i < 3; i++) { R[3 * i] = pose[4 * i]; R[3 * i + 1] = pose[4 * i + 1]; R[3 * i + 2] = pose[4 * i + 2]; t[i] = pose[4 * i + 3]; }
+}
+// which of the two terms a tracking call with these options reduces (RGBDOdometry.cpp:221-222)
+struct TrackTerms { bool icp, rgb; };
+inline TrackTerms track_terms(const cf_track_opts* o) { return TrackTerms{!o->rgb_only && o->icp_weight > 0, o->rgb_only || o->icp_weight < 100}; }
 }
 
 // Device-resident RGBDOdometry (Core/Utils/RGBDOdometry.h:78-137)
@@ -112,6 +137,10 @@ struct cf_odom {
     float2* zrange[3]{};              // depth interval of every 64-pixel run of vmap_curr (written with the frame maps, cf_odom_init_icp)
     bool zrange_valid = false;        // cf_odom_init_icp wrote zrange for the current contents of vmap_curr (cleared when a caller takes the map's pointer)
     const float2* ext_zrange[3]{};    // ... of the shared frame maps (cf_odom_share_frame_maps), null when bound without them
+    // the current frame's maps this tracker reduces: the bound / shared ones, else its own (whose intervals count only while valid)
+    const float* cur_vmap(int l) const { return ext_vmap_curr[l] ? ext_vmap_curr[l] : vmap_curr[l]; }
+    const float* cur_nmap(int l) const { return ext_nmap_curr[l] ? ext_nmap_curr[l] : nmap_curr[l]; }
+    const float2* cur_zrange(int l) const { return ext_vmap_curr[l] ? ext_zrange[l] : (zrange_valid ? zrange[l] : nullptr); }
     float* lastDepth[3]{};
     float* nextDepth[3]{};
     // cf_odom_init_models_batch: initRGB takes its depth from the same snapshot of the predicted vertex map as initRGBModel
@@ -126,7 +155,7 @@ struct cf_odom {
     float* cloud[3]{};
     cf_dataterm* corres[3]{};
     uint8_t* cand[3]{};
-    unsigned char* occ = nullptr;    // occupancy map of the model maps (written by model_maps_kernel)
+    unsigned char* occ = nullptr;    // occupancy map of the model maps (written by model_maps_tiled_body)
     bool occ_valid = false;          // the map describes the current model maps
     bool use_occ = false;            // cf_odom_set_culling: occupancy look-up + screen-box culling of the ICP reduction
     unsigned* aabb = nullptr;        // 8 words: bounding-box accumulator of the model maps (OdomDev::aabb_acc)
@@ -136,7 +165,7 @@ struct cf_odom {
     int res_hint[3] = {-1, -1, -1};  // record slots per level between them in the previous tracking call (-1: unknown): sizes the residual launches
     bool box_valid = false;          // the model-map pass of this frame fed the accumulator
     int band_begin = 0, band_end = 0;  // cf_odom_set_band: this rank's rows of the model's reductions (0, 0: all rows)
-    bool band_counts = true;           // this rank adds the residual pass's count / sigma (exactly one rank of a split does)            // cf_odom_set_culling: worth it for models that cover a small part of the image
+    bool band_counts = true;           // this rank adds the residual pass's count / sigma (exactly one rank of a split does)
     unsigned long long* icp_acc = nullptr;
     unsigned long long* rgb_acc = nullptr;
     cf::OdomDev* d_state = nullptr;

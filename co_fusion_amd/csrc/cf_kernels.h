@@ -9,6 +9,13 @@
 
 namespace cf {
 
+// the intrinsics of pyramid level `level` (a float divided by an int, on the host and on the device alike)
+__host__ __device__ __forceinline__ cf_cam cam_level(cf_cam c, int level)
+{  // CameraModel::operator(), types.cuh:94-98
+    const int div = 1 << level;
+    return cf_cam{c.fx / div, c.fy / div, c.cx / div, c.cy / div};
+}
+
 constexpr int kGroups = 64;  // accumulation groups for the grouped integer atomics
 
 // HOT STATE of a tracker (round 5): everything the workgroups of the per-iteration launches read from the device-resident state,
@@ -165,7 +172,7 @@ struct RgbdBatch {
     uint8_t* fan_image[3][kPrepBatch];
     signed char fan_owner[kPrepBatch];
 };
-void launch_model_maps(hipStream_t s, const ModelMapsBatch& b, int n);  // needs cols % 4 == 0 && rows % 4 == 0
+void launch_model_maps(hipStream_t s, const ModelMapsBatch& b, int n);  // needs cols % 16 == 0 && rows % 4 == 0 (cf_create admits no other size)
 void launch_frame_maps(hipStream_t s, FrameMapsArgs a, int W, int H);
 void launch_rgbd_pyramids(hipStream_t s, const RgbdBatch& b, int n_chains, int W, int H, float cutoff);
 void launch_model_maps_and_pyramids(hipStream_t s, const ModelMapsBatch& mb, int n, const RgbdBatch& rb, int n_chains, int W, int H, float cutoff);
@@ -192,7 +199,7 @@ struct IcpLaunch { int threads; int ppt; int gram;   // threads per workgroup, p
                    LaunchShape* const* shape = nullptr; };  // nullable, [n]: where launch_icp_rgbres records what it decided (a few ints per launch)
 
 // stand-alone steps (C-ABI parity with icpStep / computeRgbResidual / rgbStep / so3Step) run the same
-// kernels on a scratch OdomDev prepared by cabi.cpp.
+// kernels on a scratch OdomDev prepared by cabi_steps.hip.
 // ICP kernel arguments (by value, in the kernarg segment): per-model pointers + shared geometry
 constexpr int kMaxBatch = 16;  // trackers per lock-step launch (grid.y): the models of one frame, or of several sequences' frames.
                                // Bounded by the 4 KB kernel-argument segment (IcpArgs + RgbArgs by value: 3.4 KB at 16)
@@ -202,7 +209,7 @@ struct IcpModelArgs {
     const OdomDev* st;                  // device-resident pose + flags
     unsigned long long* acc;            // [kGroups][32] grouped accumulators
     float* err;                         // nullable ICP error surface [rows*cols]
-    const unsigned char* occ;           // nullable: occupancy map of the model maps (model_maps_kernel), 1 byte per 4x4 level-0 block
+    const unsigned char* occ;           // nullable: occupancy map of the model maps (model_maps_tiled_body), 1 byte per 4x4 level-0 block
     int row_begin, row_end;             // row band of THIS model's reduction (row_end == 0: all rows): its share when the model's
                                         // reduction is split over GPUs
     int cull;                           // workgroups / waves outside st->stats.cull_box leave before they load anything

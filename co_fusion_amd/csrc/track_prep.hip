@@ -430,58 +430,10 @@ __device__ __forceinline__ MapVal resize4(const MapVal& a00, const MapVal& a01, 
     return o;
 }
 
-__global__ void __launch_bounds__(64) model_maps_kernel(const ModelMapsBatch b)
-{
-    const ModelMapsArgs& a = b.m[blockIdx.y];  // one tracked model per grid row
-    const int c2 = a.cols >> 2, r2 = a.rows >> 2;
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= c2 * r2) return;
-    bool any_valid = false;  // does this thread's 4x4 block hold any predicted surface?
-    const int Y2 = t / c2, X2 = t - Y2 * c2;
-    const int cols = a.cols, rows = a.rows, N0 = cols * rows, c1 = cols >> 1, N1 = N0 >> 2, N2 = N0 >> 4;
-    const bool alt = a.sel && (float)a.sel[0] / (float)a.sel[1] < a.sel_ratio;
-    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(alt ? a.alt_v4 : a.pred_v4);
-    const float4* __restrict__ n4 = reinterpret_cast<const float4*>(alt ? a.alt_n4 : a.pred_n4);
-    float4* __restrict__ snap = reinterpret_cast<float4*>(a.snapshot);
-    m33 R; for (int k = 0; k < 9; k++) R.m[k] = a.R[k];
-    const f3 tr = {a.t[0], a.t[1], a.t[2]};
-    MapVal v1[4], n1[4];
-#pragma unroll
-    for (int qd = 0; qd < 4; qd++) {  // the four level-1 pixels of this block
-        const int y1 = 2 * Y2 + (qd >> 1), x1 = 2 * X2 + (qd & 1);
-        MapVal v0[4], n0[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            const int yy = 2 * y1 + (s >> 1), xx = 2 * x1 + (s & 1);
-            const int i0 = yy * cols + xx;
-            const float4 vs = v4[i0], ns = n4[i0];
-            snap[i0] = vs;
-            v0[s].have = true; n0[s].have = true;
-            if (!(vs.z == 0)) { v0[s].p = f3{vs.x, vs.y, vs.z}; n0[s].p = f3{ns.x, ns.y, ns.z}; any_valid = true; }
-            else { v0[s].p = f3{qnan(), qnan(), qnan()}; n0[s].p = v0[s].p; }
-            emit_map(a.vmap[0], i0, N0, v0[s], R, tr, true);
-            emit_map(a.nmap[0], i0, N0, n0[s], R, tr, false);
-        }
-        v1[qd] = resize4(v0[0], v0[1], v0[2], v0[3], false);
-        n1[qd] = resize4(n0[0], n0[1], n0[2], n0[3], true);
-        const int i1 = y1 * c1 + x1;
-        emit_map(a.vmap[1], i1, N1, v1[qd], R, tr, true);
-        emit_map(a.nmap[1], i1, N1, n1[qd], R, tr, false);
-    }
-    const MapVal v2 = resize4(v1[0], v1[1], v1[2], v1[3], false);
-    const MapVal n2 = resize4(n1[0], n1[1], n1[2], n1[3], true);
-    const int i2 = Y2 * c2 + X2;
-    emit_map(a.vmap[2], i2, N2, v2, R, tr, true);
-    emit_map(a.nmap[2], i2, N2, n2, R, tr, false);
-    // occupancy map of the prediction, one byte per 4x4 block: the ICP reduction skips the gathers of pixels that project into an
-    // empty block (every level's model-map pixel inside such a block is invalid)
-    if (a.occ) a.occ[t] = any_valid ? 1 : 0;
-}
-
-// The same pass with one lane per level-0 pixel: a wave owns a 16 x 4 tile (rows of 16 float4 = 256 contiguous bytes per load, 64
-// contiguous bytes per planar store), the 2x2 averages of levels 1 and 2 take their four sources from the neighbouring lanes in
-// the order the reference adds them (resize4 is the same function).  16x the parallelism of model_maps_kernel, whose lanes walk
-// a 4x4 block each.  Needs cols % 16 == 0 and rows % 4 == 0.
+// The model maps of every level in one pass, one tracked model per grid row and one lane per level-0 pixel: a wave owns a 16 x 4 tile
+// (rows of 16 float4 = 256 contiguous bytes per load, 64 contiguous bytes per planar store), the 2x2 averages of levels 1 and 2 take
+// their four sources from the neighbouring lanes in the order the reference adds them (resize4).  Needs cols % 16 == 0 and
+// rows % 4 == 0, which cf_create demands of every context.
 __device__ __forceinline__ MapVal lane_mapval(const MapVal& m, int src_lane)
 {
     MapVal o;
@@ -599,26 +551,14 @@ void launch_rgb_prep(hipStream_t s, RgbPrepBatch b, int n, int W, int H)
 }
 void launch_model_maps(hipStream_t s, const ModelMapsBatch& b, int n)
 {
-    const int cols = b.m[0].cols, rows = b.m[0].rows;
-    if (cols % 16 == 0 && rows % 4 == 0) {
-        const int tiles = (cols >> 4) * (rows >> 2);
-        model_maps_tiled_kernel<<<dim3((tiles + 3) / 4, n), 256, 0, s>>>(b);
-        return;
-    }
-    const int t = (cols >> 2) * (rows >> 2);
-    model_maps_kernel<<<dim3((t + 63) / 64, n), 64, 0, s>>>(b);
+    const int tiles = (b.m[0].cols >> 4) * (b.m[0].rows >> 2);
+    model_maps_tiled_kernel<<<dim3((tiles + 3) / 4, n), 256, 0, s>>>(b);
 }
 void launch_model_maps_and_pyramids(hipStream_t s, const ModelMapsBatch& mb, int n, const RgbdBatch& rb, int n_chains, int W, int H, float cutoff)
 {
     static_assert(kBlock == 256, "the fused launch runs both bodies with 256 threads");
-    const int cols = mb.m[0].cols, rows = mb.m[0].rows;
-    if (cols % 16 == 0 && rows % 4 == 0) {
-        const int mm_bx = ((cols >> 4) * (rows >> 2) + 3) / 4, rb_bx = 2 * grid_for(W * H);
-        prep_fused_kernel<<<mm_bx * n + rb_bx * n_chains, 256, 0, s>>>(mb, mm_bx, mm_bx * n, rb, W * H, cutoff, rb_bx);
-    } else {
-        launch_model_maps(s, mb, n);
-        rgbd_base_kernel<<<dim3(2 * grid_for(W * H), n_chains), kBlock, 0, s>>>(rb, W * H, cutoff);
-    }
+    const int mm_bx = ((mb.m[0].cols >> 4) * (mb.m[0].rows >> 2) + 3) / 4, rb_bx = 2 * grid_for(W * H);
+    prep_fused_kernel<<<mm_bx * n + rb_bx * n_chains, 256, 0, s>>>(mb, mm_bx, mm_bx * n, rb, W * H, cutoff, rb_bx);
     for (int i = 0; i + 1 < 3; i++)
         rgbd_pyrdown_kernel<<<dim3(2 * grid_for(((W >> i) / 2) * ((H >> i) / 2)), n_chains), kBlock, 0, s>>>(rb, i, W >> i, H >> i);
 }

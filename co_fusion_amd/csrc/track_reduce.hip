@@ -472,7 +472,7 @@ __device__ __forceinline__ void icp_reduce_body(const IcpArgs& args, const RgbAr
 }
 
 #ifdef CF_ABLATE
-// diagnostics build: per-workgroup begin / end stamps of one launch (CF_ICP_TRACE, cabi.hip) -- [workgroup][4] = begin, end (100 MHz
+// diagnostics build: per-workgroup begin / end stamps of one launch (CF_ICP_TRACE, cabi_track.hip) -- [workgroup][4] = begin, end (100 MHz
 // constant clock), XCC_ID | HW_ID << 8, 0
 __device__ unsigned long long* g_icp_trace = nullptr;
 #endif

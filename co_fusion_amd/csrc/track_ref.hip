@@ -328,8 +328,7 @@ int ref_track(cf_ctx* ctx, cf_odom* od, const float pose[16], const cf_track_opt
     if (int r = ref_scratch(ctx)) return r;
     hipStream_t s = ctx->stream;
     const int W = ctx->cfg.width, H = ctx->cfg.height;
-    const cf_cam intr = {ctx->cfg.fx, ctx->cfg.fy, ctx->cfg.cx, ctx->cfg.cy};
-    auto level_cam = [&](int l) { const int div = 1 << l; return cf_cam{intr.fx / div, intr.fy / div, intr.cx / div, intr.cy / div}; };
+    const cf_cam intr = ctx_cam(ctx);
     float* const d_part = ctx->d_ref;
     float* const d_tot = ctx->d_ref + (size_t)kRefIcpBlocks * kRefStride;        // [3][32]
     int* const d_cnt = reinterpret_cast<int*>(d_tot + 3 * kRefStride);           // [2]
@@ -338,14 +337,13 @@ int ref_track(cf_ctx* ctx, cf_odom* od, const float pose[16], const cf_track_opt
 
     const bool rgbOnly = opts->rgb_only != 0;
     const float icpWeight = opts->icp_weight;
-    const bool icp = !rgbOnly && icpWeight > 0;
-    const bool rgb = rgbOnly || icpWeight < 100;
+    const auto [icp, rgb] = track_terms(opts);
     cf_track_stats st;
     memset(&st, 0, sizeof(st));
     st.cull_box[0] = 0; st.cull_box[1] = 0; st.cull_box[2] = W - 1; st.cull_box[3] = H - 1;
 
-    float Rprev[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-    float tprev[3] = {pose[3], pose[7], pose[11]};
+    float Rprev[9], tprev[3];
+    pose_split(pose, Rprev, tprev);
     float Rcurr[9], tcurr[3];
     memcpy(Rcurr, Rprev, sizeof(Rcurr)); memcpy(tcurr, tprev, sizeof(tcurr));
 
@@ -354,7 +352,7 @@ int ref_track(cf_ctx* ctx, cf_odom* od, const float pose[16], const cf_track_opt
         const int L = 2, cols = W >> L, rows = H >> L;
         float R_lr[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         double K[9], Kinv[9];
-        const cf_cam il = level_cam(L);
+        const cf_cam il = cam_level(intr, L);
         k_matrix(il.fx, il.fy, il.cx, il.cy, K);
         float lastError = FLT_MAX / 2, lastCount = FLT_MAX / 2;
         double lastResultR[9]; memcpy(lastResultR, resultR, sizeof(resultR));
@@ -419,7 +417,7 @@ int ref_track(cf_ctx* ctx, cf_odom* od, const float pose[16], const cf_track_opt
 
     for (int i = 2; i >= 0; i--) {
         const int cols = W >> i, rows = H >> i;
-        const cf_cam il = level_cam(i);
+        const cf_cam il = cam_level(intr, i);
         double K[9], Kinv[9];
         k_matrix(il.fx, il.fy, il.cx, il.cy, K);
         st.last_rgb_error = FLT_MAX;   // lastRGBError = max at the top of every level (:343)
@@ -453,8 +451,7 @@ int ref_track(cf_ctx* ctx, cf_odom* od, const float pose[16], const cf_track_opt
                 memcpy(a.Rcurr.m, Rcurr, 36); memcpy(a.Rprev_inv.m, Rprev_inv, 36);
                 a.tcurr = f3{tcurr[0], tcurr[1], tcurr[2]}; a.tprev = f3{tprev[0], tprev[1], tprev[2]};
                 a.intr = il;
-                a.vc = od->ext_vmap_curr[i] ? od->ext_vmap_curr[i] : od->vmap_curr[i];
-                a.nc = od->ext_nmap_curr[i] ? od->ext_nmap_curr[i] : od->nmap_curr[i];
+                a.vc = od->cur_vmap(i); a.nc = od->cur_nmap(i);
                 a.vp = od->vmap_g_prev[i]; a.np = od->nmap_g_prev[i];
                 a.distThres = od->distThres; a.angleThres = od->angleThres; a.cols = cols; a.rows = rows;
                 a.err = want_err ? err_surface : nullptr;

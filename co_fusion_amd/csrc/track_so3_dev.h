@@ -8,12 +8,6 @@
 
 namespace cf {
 
-__device__ __forceinline__ cf_cam cam_level(cf_cam c, int level)
-{  // CameraModel::operator(), types.cuh:94-98
-    const int div = 1 << level;
-    return cf_cam{c.fx / div, c.fy / div, c.cx / div, c.cy / div};
-}
-
 // ------------------------------------------------------------------------------------------------
 // Screen-box culling.  A pixel of the current frame finds a correspondence only if its vertex, taken into the camera the prediction was
 // rendered from (vcurr_cp = Rprev^-1 (Rcurr vcurr + tcurr - tprev)), projects onto a VALID pixel of the prediction -- i.e. lies inside

@@ -7,8 +7,8 @@ No tolerances: both sides claim the same IEEE operation order; NaN equals NaN.  
 reference writes only the x plane of an invalid pixel.  The scenes (tests/prep_scenes.py) carry the defects that send the kernels down
 their side branches; tests/test_cpu_prep_ref.py holds them to that.
 
-Not reachable through cf_create (it rejects such sizes) and therefore not tested: model_maps_kernel, the untiled fallback, and the
-W % 4 || H % 4 branch of the initialisers.
+cf_create admits only widths that are multiples of 16 and heights that are multiples of 4, so the tiled pass is the only one: the untiled
+fallback kernel and the W % 4 || H % 4 branches of the initialisers, which no context could reach, are gone.
 """
 from dataclasses import dataclass
 from typing import Optional, Tuple

@@ -1,4 +1,4 @@
-"""Summary of a per-workgroup trace of the level-0 {ICP || residual} launch (diagnostics build: CF_ICP_TRACE / CF_ICP_TRACE_OUT, cabi.hip).
+"""Summary of a per-workgroup trace of the level-0 {ICP || residual} launch (diagnostics build: CF_ICP_TRACE / CF_ICP_TRACE_OUT, cabi_track.hip).
 usage: icp_trace_summary.py <trace.txt>"""
 import statistics, sys
 from collections import defaultdict

@@ -1,4 +1,4 @@
-"""Phases of the fused RGB step + solve launch (diagnostics build: CF_STEP_TRACE, cabi.hip): per tracker, when its workgroups begin, finish
+"""Phases of the fused RGB step + solve launch (diagnostics build: CF_STEP_TRACE, cabi_track.hip): per tracker, when its workgroups begin, finish
 their step, have their atomics acknowledged, hold their ticket, and when the solver ends.  usage: step_trace_summary.py <file>"""
 import statistics, sys
 from collections import defaultdict
