@@ -359,6 +359,26 @@ class CoFusion:
         self._check(self.lib.cofusion_reloc_stats(self.h, C.byref(k), C.byref(c), C.byref(r), C.byref(f)))
         return dict(keyframes=k.value, last_closest=c.value, recoveries=r.value, database_full=bool(f.value))
 
+    def deform_background(self, src, dst, src_time, dst_time=None, pin=False, sample_rate=25000):
+        """Loop closure of the background map from caller-supplied constraints (cofusion_deform_background): surface
+        points src [n, 3] seen at ticks src_time [n] belong at dst [n, 3]; pin: every dst also stays where it is (at tick dst_time).
+        The deformation graph is sampled from the map, optimised and, when accepted, applied to every surfel.  -> the optimisation's
+        outcome (co_fusion_amd.deform.RESULT_FIELDS) + nodes"""
+        from . import deform as _deform
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 3); d = np.ascontiguousarray(dst, np.float32).reshape(-1, 3)
+        ts = np.ascontiguousarray(src_time, np.float32).reshape(-1)
+        td = None if dst_time is None else np.ascontiguousarray(dst_time, np.float32).reshape(-1)
+        assert len(s) == len(d) == len(ts) and (td is None or len(td) == len(s))
+        res = _deform.Result(); nodes = C.c_int()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.cofusion_deform_background(self.h, vp(s), vp(d), vp(ts), vp(td), len(s), int(bool(pin)), int(sample_rate), C.byref(res),
+                                                        C.byref(nodes)))
+        out = {k: getattr(res, k) for k in _deform.RESULT_FIELDS}
+        for k in ("optimised", "accepted", "failed"):
+            out[k] = bool(out[k])
+        out["nodes"] = nodes.value
+        return out
+
     def set_redetection(self, on=True, min_fit=0.5, min_cover=0.044, depth_tol=0.10, max_candidates=8, keep_min_surfels=4000,
                         keep_conf_threshold=0.3):
         """Re-detection of inactive object models (cofusion_set_redetection): a frame with a new label scores the most

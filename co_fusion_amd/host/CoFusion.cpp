@@ -643,6 +643,7 @@ CoFusion::~CoFusion()
     pool.reset();
     releaseRenderer();
     if (ferns) cf_ferns_destroy(ferns);
+    if (deform) cf_deform_destroy(deform);
     models.clear(); inactiveModels.clear(); newModel.reset(); globalModel.reset();
     cf_free(ctx, depth_dev);
     for (int b = 0; b < 2; b++) { cf_free(ctx, depthFilteredBuf[b]); cf_free(ctx, depthPyr1Buf[b]); cf_free(ctx, depthPyr2Buf[b]); }
@@ -1317,6 +1318,49 @@ void CoFusion::fernsAfterPredict()
     g.overridePose(p);
     lastFrameRecovery = true;
     fuseAndPredict(false, st.weightMultiplier, lost, true, 0);
+}
+
+// Deformation::addConstraint + Deformation::constrain (fernMatch) + the node branch of copy_unstable.vert for the background map, between
+// frames: the constraints come from the caller.  Everything the closure computes runs in cf_deform_* (csrc/deform.hip).
+int CoFusion::deformBackground(const float* src, const float* dst, const float* srcTime, const float* dstTime, int n, bool pin, int sampleRate,
+                               cf_deform_result* result)
+{
+    if (dist.world > 1) throw std::runtime_error("deformBackground: a single-GPU option, like reloc");
+    if (!ownsCtx) throw std::runtime_error("deformBackground: not available for a sequence of a lock-step group");
+    if (!src || !dst || !srcTime || (pin && !dstTime) || n < 1 || n * (pin ? 2 : 1) > CF_DEFORM_MAX_CONSTRAINTS)
+        throw std::runtime_error("deformBackground: 1..128 constraints (pins included), with their times");
+    if (!curRgba || !depthFiltered_dev) throw std::runtime_error("deformBackground: no frame has been processed yet");
+    if (!deform) check(ctx, cf_deform_create(ctx, &deform), "cf_deform_create");
+    std::vector<float> s, d, t;
+    for (int i = 0; i < n; i++) {
+        s.insert(s.end(), src + 3 * i, src + 3 * i + 3); d.insert(d.end(), dst + 3 * i, dst + 3 * i + 3); t.push_back(srcTime[i]);
+        if (pin) { s.insert(s.end(), dst + 3 * i, dst + 3 * i + 3); d.insert(d.end(), dst + 3 * i, dst + 3 * i + 3); t.push_back(dstTime[i]); }
+    }
+    Model& g = *globalModel;
+    uint32_t count = 0;
+    check(ctx, cf_model_count(g.handle(), &count), "cf_model_count");
+    float* map = static_cast<float*>(const_cast<void*>(mbuf(ctx, g.handle(), 11)));
+    int nodes = 0, stride = 0, monotone = 0;
+    check(ctx, cf_deform_sample(deform, map, count, sampleRate > 0 ? sampleRate : 25000, &nodes, &stride, &monotone), "cf_deform_sample");
+    cf_deform_result res{};
+    if (result) *result = res;
+    if (nodes < 5 || !monotone) return nodes;
+    check(ctx, cf_deform_weights(deform, s.data(), d.data(), t.data(), (int)t.size()), "cf_deform_weights");
+    check(ctx, cf_deform_optimise(deform, nullptr, &res), "cf_deform_optimise");
+    if (result) *result = res;
+    if (!res.accepted) return nodes;
+    cf_deform_reactivate re{};
+    for (int i = 0; i < 16; i++) re.pose[i] = g.getPose().m[i];
+    re.cam = cf_cam{cfg.fx, cfg.fy, cfg.cx, cfg.cy}; re.cols = cfg.width; re.rows = cfg.height; re.max_depth = maxDepthProcessed;
+    // the clock has already moved on from the frame the map was last fused in (frameEnd): the stamp and the prediction are that frame's
+    const int ahead = lost ? 0 : 1;
+    tick -= ahead;
+    re.depth = depthFiltered_dev; re.conf_threshold = g.getConfidenceThreshold(); re.tick = tick;
+    struct Restore { int& t; int a; ~Restore() { t += a; } } restore{tick, ahead};
+    check(ctx, cf_deform_apply(deform, map, count, &re), "cf_deform_apply");
+    fuseAndPredict(false, st.weightMultiplier, lost, true, 0);   // (as the recovery path: the next frame tracks against the corrected map)
+    check(ctx, cf_synchronize(ctx), "cf_synchronize");
+    return nodes;
 }
 
 // The first index maps of the surfel chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) enqueued BEHIND the

@@ -358,6 +358,10 @@ class CoFusion {
                            uint64_t seed = 0, int capacity = 1024);
     void relocStats(int* keyframes, int* lastClosest, int* recoveries, int* databaseFull);
     bool isGroupSequence() const { return !ownsCtx; }
+    // Loop closure of the background map from caller-supplied constraints: sample the deformation graph, weight the
+    // constraint points, optimise, and on acceptance move the map (cf_deform_*) and redo the prediction.  Returns the node count.
+    int deformBackground(const float* src, const float* dst, const float* srcTime, const float* dstTime, int n, bool pin, int sampleRate,
+                         cf_deform_result* result);
     // Re-detection of inactive models (the reference's redetectModels is empty, CoFusion.cpp:599-602).  Off by default;
     // with it off the frame loop is what it was.  On: a frame whose segmentation reports a new label scores the most recent
     // `maxCandidates` (1..16) inactive models against the frame (cf_redetect_score), each at the pose it would have now had it not
@@ -460,6 +464,7 @@ class CoFusion {
     int fernMinAge = 300, fernLastClosest = -1, recoveries = 0;
     bool lastFrameRecovery = false;   // CoFusion.h:363
     void fernsAfterPredict();
+    cf_deform* deform = nullptr;   // deformBackground (created at first use)
     // device frame buffers (CoFusion::textures)
     // filtered depth + its pyramid are double buffered: the filter of frame t+1 runs on an auxiliary stream while the fusion
     // passes of frame t still read frame t's filtered depth (processFrame)

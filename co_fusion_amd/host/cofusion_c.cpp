@@ -163,6 +163,16 @@ int cofusion_reloc_stats(cofusion_handle* h, int* keyframes, int* last_closest, 
     return 0;
 }
 
+int cofusion_deform_background(cofusion_handle* h, const float* src, const float* dst, const float* src_time, const float* dst_time, int n, int pin,
+                               int sample_rate, void* result, int* nodes)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    int got = 0;
+    GUARD(got = h->cf->deformBackground(src, dst, src_time, dst_time, n, pin != 0, sample_rate, static_cast<cf_deform_result*>(result)));
+    if (nodes) *nodes = got;
+    return 0;
+}
+
 static Model* model_at(cofusion_handle* h, int index)
 {
     auto& l = h->cf->getModels();

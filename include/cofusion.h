@@ -88,6 +88,18 @@ int cofusion_set_relocalisation(cofusion_handle *h, int on, int n_ferns, float f
 /* keyframes in the database, the keyframe the last relocalisation accepted (-1: none), lost -> tracked transitions so far, 1 when an
  * append was dropped because the database is full; each nullable.  Waits for the stream. */
 int cofusion_reloc_stats(cofusion_handle *h, int *keyframes, int *last_closest, int *recoveries, int *database_full);
+/* Loop closure of the background map from caller-supplied constraints (Deformation::addConstraint + constrain with
+ * fernMatch): constraint i moves the surface point src[i] (seen at tick src_time[i]) to dst[i]; with pin != 0 every constraint adds
+ * the pin dst[i] -> dst[i] at tick dst_time[i].  The deformation graph is sampled from the background map (every sample_rate-th
+ * surfel; <= 0: 25000), optimised (the reference's thresholds), and -- when the optimisation is accepted -- applied to every surfel of
+ * the map, with the reactivation stamp against the last frame's filtered depth at the current pose; the prediction is then redone as
+ * after a relocalisation.  Object models and poses of past frames are left alone.  src, dst: host [n][3]; src_time, dst_time: host [n]
+ * (dst_time may be NULL without pins); n (2 n with pins) <= 128.  result (nullable): 8 words -- optimised, accepted, failed,
+ * iterations (int32), error and mean constraint error before and after (f32), as cf_deform_result.  nodes (nullable): the node count;
+ * fewer than 5 nodes or a non-monotone sample: nothing is done and optimised = 0.  Needs a processed frame and world == 1; refused for
+ * a sequence handle of a lock-step group.  Waits for the stream. */
+int cofusion_deform_background(cofusion_handle *h, const float *src, const float *dst, const float *src_time, const float *dst_time, int n,
+                               int pin, int sample_rate, void *result, int *nodes);
 /* Re-detection of inactive object models (the reference's CoFusion::redetectModels is an empty hook, CoFusion.cpp:599-602).
  * A model whose label gets no superpixels is deactivated; kept models (surfel count >= keep_min_surfels and confidence threshold >
  * keep_conf_threshold -- 4000 / 0.3, the reference's rule) wait in a list.  Off (the default) nothing reads that list: an object that

@@ -897,6 +897,59 @@ typedef struct {
 int cf_profile_enable(cf_ctx *ctx, int on);
 int cf_profile_read(cf_ctx *ctx, cf_profile *out, int reset);
 
+/* ------------------------------------------------------------- loop closure: deformation graph ---- */
+/* ElasticFusion's deformation graph (Core/Model/Deformation.*, Core/Utils/DeformationGraph.*, the node branch of copy_unstable.vert),
+ * device resident: global closure of ONE surfel map from absolute constraints (DESIGN.md 4.14 states every rule and every order of
+ * operations; tests/deform_ref.py restates them in numpy).  Everything is allocated at creation, for CF_DEFORM_MAX_NODES nodes and
+ * CF_DEFORM_MAX_CONSTRAINTS constraints (pins included): about 24 MB, nearly all of it the band of the normal matrix.  The calls are
+ * rare and synchronous (each waits for the context's stream) except cf_deform_apply and cf_deform_apply_poses, which only enqueue. */
+#define CF_DEFORM_MAX_NODES 1024
+#define CF_DEFORM_MAX_CONSTRAINTS 128
+#define CF_DEFORM_BAND 240          /* band entries per row of A, diagonal included: A_band[i][d] = A[i][i - d] */
+typedef struct cf_deform cf_deform;
+typedef struct {                    /* the reference's figures: 0.06, 3, 1e-2, 1e-3, 1e-5, 10, 3e-4, 0.12 */
+    float min_cons_error; int max_iterations; float min_delta, min_error, min_change, max_first_error, accept_cons_error, accept_error;
+} cf_deform_thresholds;
+typedef struct { float error; double delta_norm; int failed; float mean_cons_error; } cf_deform_step;
+typedef struct {
+    int optimised, accepted, failed, iterations;
+    float error_before, mean_cons_error_before, error, mean_cons_error;
+} cf_deform_result;
+typedef struct {                    /* the reactivation stamp of cf_deform_apply (copy_unstable.vert:318-333) */
+    float pose[16];                 /* the corrected camera pose, row-major T(world <- camera) */
+    cf_cam cam; int cols, rows;
+    float max_depth;
+    const float *depth;             /* device, [rows * cols]: the frame's filtered depth */
+    float conf_threshold;
+    int tick;
+} cf_deform_reactivate;
+int cf_deform_create(cf_ctx *ctx, cf_deform **out);
+void cf_deform_destroy(cf_deform *d);
+void cf_deform_default_thresholds(cf_deform_thresholds *out);
+/* every surfel of map_dev (device, `count` records of 12 f32) whose index is a multiple of stride becomes a node; stride = the smallest
+ * multiple of sample_rate that leaves at most CF_DEFORM_MAX_NODES.  Parameters become the identity.  nodes < 5: there is no graph, and
+ * every later call but sample / set_nodes answers CF_ESTATE.  monotone = 0: node times decrease somewhere (no closure from this graph). */
+int cf_deform_sample(cf_deform *d, const float *map_dev, uint32_t count, int sample_rate, int *nodes, int *stride, int *monotone);
+/* test access: a crafted graph.  nodes_host [n][4] x y z time; params_host [n][12] (3x3 column-major, translation) or NULL: identity */
+int cf_deform_set_nodes(cf_deform *d, const float *nodes_host, const float *params_host, int n);
+/* the constraints (host: src, dst [n][3], src_time [n]; a pin is the constraint dst -> dst at dst's time) and their weight sets */
+int cf_deform_weights(cf_deform *d, const float *src, const float *dst, const float *src_time, int n);
+/* residuals, A = J^T J in band storage and b = -J^T r for the current parameters */
+int cf_deform_assemble(cf_deform *d);
+/* one Gauss-Newton step: assemble, band Cholesky, parameters += delta, the new error.  failed = 1: a pivot <= 0, parameters unchanged */
+int cf_deform_iterate(cf_deform *d, cf_deform_step *out);
+/* optimiseGraphSparse (fernMatch) from the current parameters + the acceptance of Deformation::constrain; th NULL: the defaults */
+int cf_deform_optimise(cf_deform *d, const cf_deform_thresholds *th, cf_deform_result *out);
+/* the map pass over map_dev in place; re NULL: no reactivation stamp.  Enqueued only. */
+int cf_deform_apply(cf_deform *d, float *map_dev, uint32_t count, const cf_deform_reactivate *re);
+/* applyGraphToPoses over device arrays: poses [n][16] row-major, times [n].  Enqueued only. */
+int cf_deform_apply_poses(cf_deform *d, float *poses_dev, const int32_t *times_dev, int n);
+/* test access, host outputs, each nullable: nodes [n][4], params [n][12], edges [n][4], ids and weights [constraints][4] (a NaN weight:
+ * the point does not move), A_band [12 n][CF_DEFORM_BAND] (after cf_deform_iterate: its Cholesky factor), b [12 n] (after
+ * cf_deform_iterate: delta) */
+int cf_deform_download(cf_deform *d, int *n_nodes, int *n_constraints, float *nodes, float *params, int32_t *edges, int32_t *ids, float *weights,
+                       double *A_band, double *b);
+
 #ifdef __cplusplus
 }
 #endif
