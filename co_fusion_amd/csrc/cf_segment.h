@@ -106,6 +106,8 @@ struct cf_segmenter {
     const float* early_depth = nullptr; const uint8_t* early_rgba = nullptr;
     std::vector<const float*> early_vconf;
     float early_scale[3] = {0.f, 0.f, 0.f};
+    // the last inference, for cf_seg_buffer: which of Q0 / Q1 holds its marginals (launch_mean_field's flip), its models and labels
+    int last_flip = 0, last_n = 0, last_L = 0;
     // label-mask branch (segment_masks.hip; cf_seg_masks / cf_seg_masks_batch / cf_seg_new_mask_value)
     unsigned* mask_work = nullptr;       // [2][kMaskWork] first new pixel + histograms: job k works in block k & 1 and leaves the other one reset
     int* h_mask_new = nullptr;           // pinned [1]: the mask value bound to the new label (-1: none), stored by mask_stats_kernel

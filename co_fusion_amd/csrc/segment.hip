@@ -230,7 +230,9 @@ int cf_seg_crf(cf_segmenter* s, const float* unary_host, int L, const float* fea
     memset(&B, 0, sizeof(B));
     B.m[0] = crf_seq(s, L);
     launch_crf_kernel_matrix<6>(st, B, 1, n, true);
-    const float* q = launch_mean_field(st, B, 1, n, iterations, w_smooth, w_app) ? s->Q1 : s->Q0;
+    s->last_flip = launch_mean_field(st, B, 1, n, iterations, w_smooth, w_app);
+    s->last_n = 0; s->last_L = L;
+    const float* q = s->last_flip ? s->Q1 : s->Q0;
     LAUNCHCHK(ctx);
     HIPCHK(ctx, hipMemcpyAsync(Q_host, q, sizeof(float) * n * L, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -384,6 +386,7 @@ static int enqueue_infer(cf_ctx* ctx, const cf_seg_params* P, const SegJob* jobs
     for (int e = 0; e < S; e++) {
         cf_segmenter* s = jobs[e].s;
         const int n_models = jobs[e].n_models, L = label_count(n_models, jobs[e].allow_new);
+        s->last_flip = flip; s->last_n = n_models; s->last_L = L;   // (cf_seg_buffer)
         SegPostArgsT<CAP>& p = PB.m[e];
         p.K = n; p.gx = s->gx; p.gy = s->gy; p.n_models = n_models; p.L = L; p.allow_new = jobs[e].allow_new ? 1 : 0;
         p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.next_id = jobs[e].next_model_id;
@@ -540,6 +543,33 @@ int cf_seg_labels(cf_segmenter* s, void** dptr, uint64_t* bytes)
     if (!s || !dptr) return CF_EINVAL;
     *dptr = s->labels;
     if (bytes) *bytes = (uint64_t)s->ctx->cfg.width * s->ctx->cfg.height * 4;
+    return CF_OK;
+}
+
+// Test access, read only: device views of what the chain holds between its stages (layouts and validity: include/cofusion_hip.h).
+// Hands out addresses; the caller reads them in stream order (cf_memcpy_d2d_async on the context's stream).
+int cf_seg_buffer(cf_segmenter* s, int which, void** dptr, uint64_t* bytes)
+{
+    if (!s || !dptr || !s->K) return CF_EINVAL;
+    const uint64_t K = (uint64_t)s->K, Lc = (uint64_t)s->Lcap, n = (uint64_t)s->last_n, L = (uint64_t)s->last_L;
+    void* p = nullptr; uint64_t b = 0;
+    switch (which) {
+    case 0: p = s->spix_count; b = K * 4; break;
+    case 1: p = s->depth_count; b = K * 4; break;
+    case 2: p = s->depth_sum; b = K * 8; break;
+    case 3: p = s->icp_sum; b = Lc * K * 8; break;
+    case 4: p = s->conf_sum; b = Lc * K * 8; break;
+    case 5: p = s->low_mean; b = (1 + 2 * n) * K * 4; break;
+    case 6: p = s->unary; b = K * L * 4; break;
+    case 7: p = s->feat2; b = K * 6 * 4; break;
+    case 8: p = s->avg_conf; b = n * 4; break;
+    case 9: p = s->depth_range; b = 4; break;
+    case 10: p = s->low_map; b = K; break;
+    case 11: p = s->last_flip ? s->Q1 : s->Q0; b = K * L * 4; break;
+    default: s->ctx->set_error("cf_seg_buffer: no such buffer"); return CF_EINVAL;
+    }
+    *dptr = p;
+    if (bytes) *bytes = b;
     return CF_OK;
 }
 

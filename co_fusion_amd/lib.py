@@ -29,7 +29,7 @@ SYMBOLS = [
     "cf_model_fuse", "cf_model_clean", "cf_models_frame_passes", "cf_models_preindex", "cf_model_download_map", "cf_model_upload_map", "cf_model_buffer",
     "cf_redetect_score", "cf_redetect_timing", "cf_relabel",
     "cf_fusion_weight", "cf_seg_create", "cf_seg_destroy", "cf_seg_slic", "cf_seg_crf", "cf_seg_sums", "cf_seg_infer", "cf_seg_early", "cf_seg_run_batch", "cf_seg_fetch", "cf_seg_publish_poses", "cf_seg_fetch_poses",
-    "cf_seg_labels", "cf_seg_create_masks", "cf_seg_masks", "cf_seg_masks_batch", "cf_seg_new_mask_value",
+    "cf_seg_labels", "cf_seg_buffer", "cf_seg_create_masks", "cf_seg_masks", "cf_seg_masks_batch", "cf_seg_new_mask_value",
     "cf_depth_pyramid", "cf_set_icp_launch", "cf_set_icp_arith", "cf_get_icp_arith", "cf_set_gn_mode", "cf_profile_enable", "cf_profile_read", "cf_odom_bench_icp", "cf_odom_level0_visited", "cf_odom_last_launch_shape",
     "cf_rccl_unique_id", "cf_rccl_init", "cf_rccl_allreduce", "cf_rccl_broadcast", "cf_rccl_info", "cf_rccl_destroy",
     "cf_render_create", "cf_render_destroy", "cf_render", "cf_render_palette",

@@ -554,6 +554,20 @@ int cf_seg_publish_poses(cf_segmenter *s, int n_models, cf_odom *const *trackers
 int cf_seg_fetch_poses(cf_segmenter *s, int n_models, int64_t *words_host);
 /* device view of the SLIC labels, int32 [H*W] */
 int cf_seg_labels(cf_segmenter *s, void **dptr, uint64_t *bytes);
+/* Test access, read only -- no segmenter state changes: device views of what the chain holds between its stages (K superpixels, n and
+ * L = the models and labels of the last inference, Lcap = max(16, the context's max_models)).  Only hands out addresses: the caller
+ * reads them in stream order (cf_memcpy_d2d_async on the context's stream).  which:
+ *    0 spix_count  u32 [K]        1 depth_count  u32 [K]         2 depth_sum  i64 [K] (Q32)
+ *    3 icp_sum     i64 [Lcap][K]  4 conf_sum     i64 [Lcap][K]   (Q32; model m's row at [m][.])
+ *        0-4 are valid BETWEEN cf_seg_sums and cf_seg_infer: the unary kernel zeroes them for the next frame.  Behind a matching
+ *        cf_seg_early only 0 and 3 are (the early half consumed and zeroed the others).
+ *    5 low_mean    f32 [1 + 2n][K]: lowDepth | lowICP[n] (after the weak-confidence substitution) | lowConf[n] (non-finite entries zeroed)
+ *    6 unary       f32 [K][L]     7 feat2        f32 [K][6]      8 avg_conf   f32 [n]      9 depth_range  f32 [1]
+ *   10 low_map     u8 [K], the map behind the component analysis and the gates
+ *   11 the marginals of the last inference (cf_seg_infer, cf_seg_run_batch or cf_seg_crf), f32 [K][L]: the one of the two buffers the
+ *      mean field's last step wrote
+ *        5-11 are valid behind cf_seg_infer / cf_seg_run_batch until the segmenter's next call (6, 7 and 11 also behind cf_seg_crf). */
+int cf_seg_buffer(cf_segmenter *s, int which, void **dptr, uint64_t *bytes);
 /* The label-mask branch (Segmentation.cpp:59-119; the reference's "pre-processed segmentation" input, Mask####.png) as kernels: a mask
  * with one value per object arrives with the frame (u8 [H*W], device memory), `mapping` binds mask values to model ids (0 = unmapped)
  * and, when allow_new is set, the value of the raster-first pixel that is non-zero and unmapped becomes next_model_id -- at most one new

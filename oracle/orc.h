@@ -241,6 +241,27 @@ int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *
                     const unsigned *model_ids, const float *const *icp_err, const float *const *vertconf4, unsigned nextModelID,
                     int allowNew, uint8_t *full_seg, orc_seg_model *out_models, int *n_out, int *hasNewLabel, float *depthRange_out,
                     int32_t *labels_out, uint8_t *low_map_out);
+/* What performSegmentationCRF holds between its stages, for the stage-by-stage parity tests (tests/seg_cases.py).  Caller-owned arrays,
+ * each nullable; K = (cols / 16) * (rows / 16) superpixels, n = n_models, L = n + (allowNew ? 1 : 0). */
+typedef struct {
+    uint32_t *spc, *dcnt;           /* [K] pixels / valid depth samples per superpixel */
+    int64_t *dsum;                  /* [K] Q32 depth sums */
+    int64_t *icp_sum, *conf_sum;    /* [n][K] Q32 sums of the ICP errors / confidences */
+    float *lowDepth;                /* [K] */
+    float *lowICP;                  /* [n][K], AFTER the weak-confidence substitution */
+    float *lowConf;                 /* [n][K], AFTER non-finite entries are zeroed */
+    float *depthRange;              /* [1] */
+    float *avgConfidence;           /* [n] */
+    float *unary;                   /* [K][L], after the 1e-5 floor */
+    float *feat2;                   /* [K][6] appearance features */
+    float *Q;                       /* [K][L] the final marginals */
+    uint8_t *argmax;                /* [K] the label map before the component analysis */
+} orc_seg_stages;
+/* orc_segment_crf with crafted labels (labels_in, nullable: SLIC runs) and the stages handed out (out, nullable) */
+int orc_segment_crf_stages(const orc_seg_params *P, int cols, int rows, const uint8_t *rgba, const float *depth, int n_models,
+                           const unsigned *model_ids, const float *const *icp_err, const float *const *vertconf4, unsigned nextModelID,
+                           int allowNew, uint8_t *full_seg, orc_seg_model *out_models, int *n_out, int *hasNewLabel, float *depthRange_out,
+                           int32_t *labels_out, uint8_t *low_map_out, const int32_t *labels_in, orc_seg_stages *out);
 int orc_segment_gt(const uint8_t *gt_mask, const float *depth, int cols, int rows, int n_models, const unsigned *model_ids,
                    unsigned nextModelID, int allowNew, uint8_t *mapping, uint8_t *full_seg, orc_seg_model *out_models, int *n_out,
                    int *hasNewLabel);

@@ -293,17 +293,21 @@ void orc_crf_meanfield(const float *unary /* [n][L] */, int L, int n, const floa
 /* ----------------------------------------------------- performSegmentationCRF ---- */
 /* Segmentation.cpp:124-706.  models[0] is the background.  icp_err[m] is the model's ICP error surface
  * [rows*cols], vertconf4[m] its splat vertexConf texture [rows*cols*4] (channel 3 = confidence). */
-int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *rgba, const float *depth, int n_models,
-                    const unsigned *model_ids, const float *const *icp_err, const float *const *vertconf4, unsigned nextModelID,
-                    int allowNew, uint8_t *full_seg, orc_seg_model *out_models, int *n_out, int *hasNewLabel, float *depthRange_out,
-                    int32_t *labels_out, uint8_t *low_map_out)
+/* The staged entry: labels_in (nullable) replaces SLIC's labels -- crafted label images, which must be in [0, K) --, and `st` (nullable,
+ * every array in it nullable) receives what the chain holds between its stages (orc.h: orc_seg_stages).  orc_segment_crf is this with
+ * neither. */
+int orc_segment_crf_stages(const orc_seg_params *P, int cols, int rows, const uint8_t *rgba, const float *depth, int n_models,
+                           const unsigned *model_ids, const float *const *icp_err, const float *const *vertconf4, unsigned nextModelID,
+                           int allowNew, uint8_t *full_seg, orc_seg_model *out_models, int *n_out, int *hasNewLabel, float *depthRange_out,
+                           int32_t *labels_out, uint8_t *low_map_out, const int32_t *labels_in, orc_seg_stages *st)
 {
     const int gx = cols / SPIX, gy = rows / SPIX, K = gx * gy;
     const size_t N = (size_t)cols * rows;
     const int numLabels = allowNew ? n_models + 1 : n_models;
     const float MAX_DEPTH = 100;
     int32_t *labels = labels_out ? labels_out : malloc(sizeof(int32_t) * N);
-    orc_slic(rgba, cols, rows, labels);
+    if (labels_in) memcpy(labels, labels_in, sizeof(int32_t) * N);
+    else orc_slic(rgba, cols, rows, labels);
 
     unsigned *spc = calloc((size_t)K, sizeof(unsigned)), *dcnt = calloc((size_t)K, sizeof(unsigned));
     int64_t *dsum = calloc((size_t)K, sizeof(int64_t));
@@ -313,6 +317,14 @@ int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *
     }
     float *lowDepth = malloc(sizeof(float) * (size_t)K);
     finish_mean(dsum, dcnt, spc, gx, gy, cols, rows, labels, lowDepth); /* downsampleThresholded, Slic.h:86-120 */
+    if (st) {
+        for (int k = 0; k < K; k++) {
+            if (st->spc) st->spc[k] = spc[k];
+            if (st->dcnt) st->dcnt[k] = dcnt[k];
+            if (st->dsum) st->dsum[k] = dsum[k];
+            if (st->lowDepth) st->lowDepth[k] = lowDepth[k];
+        }
+    }
 
     float depthMin = FLT_MAX, depthMax = 0;
     for (int i = 0; i < K; i++) {
@@ -332,9 +344,11 @@ int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *
         lowICP[m] = malloc(sizeof(float) * (size_t)K); lowConf[m] = malloc(sizeof(float) * (size_t)K);
         memset(acc, 0, sizeof(int64_t) * (size_t)K);
         for (size_t i = 0; i < N; i++) acc[labels[i]] += q32(icp_err[m][i]);
+        if (st && st->icp_sum) memcpy(st->icp_sum + (size_t)m * K, acc, sizeof(int64_t) * (size_t)K);
         finish_mean(acc, spc, spc, gx, gy, cols, rows, labels, lowICP[m]);
         memset(acc, 0, sizeof(int64_t) * (size_t)K);
         for (size_t i = 0; i < N; i++) acc[labels[i]] += q32(vertconf4[m][i * 4 + 3]);
+        if (st && st->conf_sum) memcpy(st->conf_sum + (size_t)m * K, acc, sizeof(int64_t) * (size_t)K);
         finish_mean(acc, spc, spc, gx, gy, cols, rows, labels, lowConf[m]);
         out_models[m].id = model_ids[m]; out_models[m].superPixelCount = 0; out_models[m].avgConfidence = 0;
         out_models[m].depthMean = 0; out_models[m].depthStd = 0;
@@ -388,14 +402,26 @@ int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *
             f2[index * 6 + 5] = fminf(lowDepth[index] * P->scaleFeaturesDepth, 100.0f);
         }
     for (size_t i = 0; i < (size_t)K * L; i++) if (unary[i] <= 1e-5f) unary[i] = 1e-5f;
+    if (st) {
+        if (st->depthRange) *st->depthRange = depthRange;
+        for (int m = 0; m < n_models; m++) {
+            if (st->lowICP) memcpy(st->lowICP + (size_t)m * K, lowICP[m], sizeof(float) * (size_t)K);    /* after the substitution */
+            if (st->lowConf) memcpy(st->lowConf + (size_t)m * K, lowConf[m], sizeof(float) * (size_t)K); /* non-finite entries zeroed */
+            if (st->avgConfidence) st->avgConfidence[m] = out_models[m].avgConfidence;
+        }
+        if (st->unary) memcpy(st->unary, unary, sizeof(float) * (size_t)K * L);
+        if (st->feat2) memcpy(st->feat2, f2, sizeof(float) * (size_t)K * 6);
+    }
     float *Q = malloc(sizeof(float) * (size_t)K * L);
     orc_crf_meanfield(unary, L, K, f1, f2, P->weightSmoothness, P->weightAppearance, P->crfIterations, Q);
+    if (st && st->Q) memcpy(st->Q, Q, sizeof(float) * (size_t)K * L);
     uint8_t *map = malloc((size_t)K);
     for (int i = 0; i < K; i++) {
         int m = 0; float best = Q[(size_t)i * L];
         for (int l = 1; l < L; l++) if (Q[(size_t)i * L + l] > best) { best = Q[(size_t)i * L + l]; m = l; }
         map[i] = (uint8_t)out_models[m].id;
     }
+    if (st && st->argmax) memcpy(st->argmax, map, (size_t)K);
 
     /* component analysis, Segmentation.cpp:483-563 */
     int *comp = malloc(sizeof(int) * (size_t)K);
@@ -488,6 +514,15 @@ int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *
     free(map); free(comp); free(cc);
     if (!labels_out) free(labels);
     return 0;
+}
+
+int orc_segment_crf(const orc_seg_params *P, int cols, int rows, const uint8_t *rgba, const float *depth, int n_models,
+                    const unsigned *model_ids, const float *const *icp_err, const float *const *vertconf4, unsigned nextModelID,
+                    int allowNew, uint8_t *full_seg, orc_seg_model *out_models, int *n_out, int *hasNewLabel, float *depthRange_out,
+                    int32_t *labels_out, uint8_t *low_map_out)
+{
+    return orc_segment_crf_stages(P, cols, rows, rgba, depth, n_models, model_ids, icp_err, vertconf4, nextModelID, allowNew, full_seg,
+                                  out_models, n_out, hasNewLabel, depthRange_out, labels_out, low_map_out, NULL, NULL);
 }
 
 /* ------------------------------------------------ GT-mask branch (Segmentation.cpp:59-119) ---- */

@@ -57,6 +57,45 @@ def segment_crf(params, rgba, depth, model_ids, icp_errs, vertconfs, next_id, al
     return dict(full=full, modelData=md, hasNewLabel=bool(has_new.value), depthRange=rng.value, labels=labels, low=low)
 
 
+class SegStages(C.Structure):
+    """orc_seg_stages (oracle/orc.h): caller-owned arrays, each nullable"""
+    NAMES = ("spc", "dcnt", "dsum", "icp_sum", "conf_sum", "lowDepth", "lowICP", "lowConf", "depthRange", "avgConfidence", "unary", "feat2",
+             "Q", "argmax")
+    _fields_ = [(k, C.c_void_p) for k in NAMES]
+
+
+def segment_crf_stages(params, rgba, depth, model_ids, icp_errs, vertconfs, next_id, allow_new, labels_in=None, stages=True):
+    """orc_segment_crf_stages: segment_crf with crafted labels (labels_in, None: SLIC runs) and, under "stages", what the chain holds
+    between its stages (stages=False: the entry is called with out = NULL)"""
+    h, w = depth.shape
+    n = len(model_ids)
+    K, L = (h // 16) * (w // 16), n + (1 if allow_new else 0)
+    ids = (C.c_uint * n)(*model_ids)
+    icp_keep = [f32(a) for a in icp_errs]; vc_keep = [f32(a) for a in vertconfs]
+    icp_arr = (C.c_void_p * n)(*[a.ctypes.data for a in icp_keep])
+    vc_arr = (C.c_void_p * n)(*[a.ctypes.data for a in vc_keep])
+    full = np.zeros((h, w), np.uint8)
+    models = (SegModel * (n + 1))()
+    n_out = C.c_int(); has_new = C.c_int(); rng = C.c_float()
+    labels = np.zeros((h, w), np.int32)
+    low = np.zeros(((h // 16), (w // 16)), np.uint8)
+    lab_in = None if labels_in is None else np.ascontiguousarray(labels_in, np.int32)
+    assert lab_in is None or (lab_in.shape == (h, w) and lab_in.min() >= 0 and lab_in.max() < K)
+    st = dict(spc=np.zeros(K, np.uint32), dcnt=np.zeros(K, np.uint32), dsum=np.zeros(K, np.int64), icp_sum=np.zeros((n, K), np.int64),
+              conf_sum=np.zeros((n, K), np.int64), lowDepth=np.zeros(K, np.float32), lowICP=np.zeros((n, K), np.float32),
+              lowConf=np.zeros((n, K), np.float32), depthRange=np.zeros(1, np.float32), avgConfidence=np.zeros(n, np.float32),
+              unary=np.zeros((K, L), np.float32), feat2=np.zeros((K, 6), np.float32), Q=np.zeros((K, L), np.float32),
+              argmax=np.zeros(K, np.uint8))
+    out = SegStages(**{k: st[k].ctypes.data for k in SegStages.NAMES})
+    lib.orc_segment_crf_stages(C.byref(params), w, h, P(u8(rgba)), P(f32(depth)), n, ids, icp_arr, vc_arr, C.c_uint(next_id), int(allow_new),
+                               P(full), models, C.byref(n_out), C.byref(has_new), C.byref(rng), P(labels), P(low),
+                               None if lab_in is None else P(lab_in), C.byref(out) if stages else None)
+    md = [dict(id=m.id, superPixelCount=m.superPixelCount, avgConfidence=m.avgConfidence, depthMean=m.depthMean, depthStd=m.depthStd,
+               top=m.top, right=m.right, bottom=m.bottom, left=m.left) for m in models[:n_out.value]]
+    return dict(full=full, modelData=md, hasNewLabel=bool(has_new.value), depthRange=rng.value, labels=labels, low=low,
+                stages=st if stages else None)
+
+
 def segment_gt(gt_mask, depth, model_ids, next_id, allow_new, mapping):
     h, w = depth.shape
     n = len(model_ids)

@@ -147,11 +147,14 @@ def test_early_chain_with_a_ragged_superpixel_count(monkeypatch):
 
 
 def test_superpixels_without_a_pixel():
-    """The oracle runs its own SLIC, so a label image cannot be handed to it: the device labels are overwritten so that a few superpixels
-    own no pixel -- their rows are replayed from the resample label, already divided when it is smaller than the superpixel's index
-    and still raw when larger -- and the split chain must equal the plain chain bit for bit (the list of these superpixels is formed by
-    the early half and replayed for the ICP rows by the late one)."""
+    """SLIC's own labels are overwritten on the device so that a few superpixels own no pixel -- their rows are replayed from the
+    resample label, already divided when it is smaller than the superpixel's index and still raw when larger -- and the split chain must
+    equal the plain chain bit for bit (the list of these superpixels is formed by the early half and replayed for the ICP rows by the
+    late one).  The new labels keep the precondition of seg_accumulate_kernel (a pixel's label is one of the 3x3 cells around the pixel's
+    own cell), and both chains must equal the oracle's staged entry on the same label image as well."""
     import torch
+    import orc_multi as om
+    import seg_cases
     ctx, seg = _context(base.W, base.H)
     gx, gy, K = base.GX, base.GY, base.GX * base.GY
     empty_natural = []
@@ -166,9 +169,13 @@ def test_superpixels_without_a_pixel():
         ctx.synchronize()
         lab = labels.cpu().numpy().copy()
         empty_natural.append(int(np.count_nonzero(np.bincount(lab.ravel(), minlength=K) == 0)))
-        # superpixel k gives its pixels to its left or right neighbour
-        for k, to in ((5, 6), (300, 299), (301, 302), (777, 776), (K - 1, K - 2), (0, 1)):
-            lab[lab == k] = to
+        assert seg_cases.invariant_3x3(lab)
+        # superpixel k gives its pixels to its left or right neighbour -- those in a cell that does not touch the neighbour's, to the cell's own
+        cell = seg_cases.grid_labels(base.W, base.H)
+        for k, to in ((5, 6), (300, 299), (302, 303), (777, 776), (K - 1, K - 2), (0, 1)):   # (no two of them neighbours: the cell between keeps its own)
+            near = (np.abs(cell % gx - to % gx) <= 1) & (np.abs(cell // gx - to // gx) <= 1)
+            lab[:] = np.where(lab == k, np.where(near, to, cell), lab)
+        assert seg_cases.invariant_3x3(lab)
         counts = np.bincount(lab.ravel(), minlength=K)
         empties = np.flatnonzero(counts == 0)
         ks = np.arange(K)
@@ -185,9 +192,12 @@ def test_superpixels_without_a_pixel():
             run.sums()
             return run.infer()
 
+        ref = om.segment_crf_stages(*sc[1:], labels_in=lab, stages=False)
         plain = chain(False)
+        _compare(f"{sc[0]}, superpixels without a pixel: plain chain against the oracle", *plain, ref)
         for rep in range(2):
             res, low, full = chain(True)
+            _compare(f"{sc[0]}, superpixels without a pixel: split chain against the oracle (pass {rep})", res, low, full, ref)
             assert np.array_equal(low, plain[1]) and np.array_equal(full, plain[2]), f"{sc[0]}: label maps (pass {rep})"
             assert bytes(res)[:12 + 36 * res.n_models] == bytes(plain[0])[:12 + 36 * plain[0].n_models], f"{sc[0]}: decisions (pass {rep})"
         again = chain(False)
