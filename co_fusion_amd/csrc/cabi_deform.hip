@@ -50,6 +50,29 @@ static int iterate(cf_deform* d, cf_deform_step* out)
     return CF_OK;
 }
 
+// constraint rows in device arrays of cf_deform_weights' host shapes (src, dst [n][3], time [n]) -> the graph's (x y z time), (x y z 0)
+__global__ void __launch_bounds__(kDeformMaxCons) deform_pack_constraints_kernel(const float* __restrict__ src, const float* __restrict__ dst,
+                                                                                const float* __restrict__ time, int n, float4* __restrict__ cons_src,
+                                                                                float4* __restrict__ cons_dst)
+{
+    const int l = threadIdx.x;
+    if (l >= n) return;
+    cons_src[l] = make_float4(src[3 * l], src[3 * l + 1], src[3 * l + 2], time[l]);
+    cons_dst[l] = make_float4(dst[3 * l], dst[3 * l + 1], dst[3 * l + 2], 0.f);
+}
+// the body cf_deform_weights and cf_deform_weights_device share: the n rows are in g.cons_src / g.cons_dst (enqueued)
+static int weight_constraints(cf_deform* d, int n)
+{
+    cf_ctx* ctx = d->ctx;
+    d->n_cons = n;
+    if (n) {
+        launch_deform_weights(ctx->cur(), d->g, d->n, n);
+        LAUNCHCHK(ctx);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->cur()));
+    return CF_OK;
+}
+
 extern "C" {
 
 void cf_deform_default_thresholds(cf_deform_thresholds* t)
@@ -149,15 +172,23 @@ int cf_deform_weights(cf_deform* d, const float* src, const float* dst, const fl
         d->h_cons[l] = make_float4(src[3 * l], src[3 * l + 1], src[3 * l + 2], src_time[l]);
         d->h_cons[kDeformMaxCons + l] = make_float4(dst[3 * l], dst[3 * l + 1], dst[3 * l + 2], 0.f);
     }
-    d->n_cons = n;
     if (n) {
         HIPCHK(ctx, hipMemcpyAsync(d->g.cons_src, d->h_cons, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
         HIPCHK(ctx, hipMemcpyAsync(d->g.cons_dst, d->h_cons + kDeformMaxCons, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
-        launch_deform_weights(ctx->cur(), d->g, d->n, n);
-        LAUNCHCHK(ctx);
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->cur()));
-    return CF_OK;
+    return weight_constraints(d, n);
+}
+
+int cf_deform_weights_device(cf_deform* d, const float* src_dev, const float* dst_dev, const float* src_time_dev, int n)
+{
+    if (!d || n < 0 || n > kDeformMaxCons || (n && (!src_dev || !dst_dev || !src_time_dev))) return CF_EINVAL;
+    if (int r = need_graph(d, "cf_deform_weights_device")) return r;
+    if (n) {
+        hipLaunchKernelGGL(deform_pack_constraints_kernel, dim3(1), dim3(kDeformMaxCons), 0, d->ctx->cur(), src_dev, dst_dev, src_time_dev, n,
+                           d->g.cons_src, d->g.cons_dst);
+        LAUNCHCHK(d->ctx);
+    }
+    return weight_constraints(d, n);
 }
 
 int cf_deform_assemble(cf_deform* d)

@@ -1,6 +1,8 @@
 // ferns.hip -- device-resident random-fern keyframe database (Core/Ferns.cpp, ElasticFusion's relocaliser): encode a frame's fill-in
 // maps into fern codes, scan the database for the most similar keyframes, append on the device, and relocalise against the match
-// with the small tracker.  DESIGN.md section 4.8 states the conventions (sampling, code bits, row layout, tie rules).
+// with the small tracker.  DESIGN.md section 4.8 states the conventions (sampling, code bits, row layout, tie rules).  The loop-closure
+// seam (include/cofusion_loop.h): a per-frame gate behind the scan, and the candidate part of Ferns::findFrame
+// (photometric check, accept rule, surface constraints) on the device.
 //
 // Database layout (HBM, all sized by `capacity` at creation):
 //   codes  u8  [capacity][row_bytes]   one byte per fern, row padded with 255 to a multiple of 16 B (a row is whole uint4 loads)
@@ -249,6 +251,148 @@ __global__ void __launch_bounds__(256) ferns_planar_to_x4_kernel(const float* __
     v4[p] = a; n4[p] = b;
 }
 
+// ---- gate (loop closure, every tracked frame): blockHDAware (Ferns.cpp:321-336) of the current codes against the published match's
+// row, one wave: a lane takes 16 B pieces of both rows, counts the ferns good in both and those of them with equal codes four at a
+// time, xor shuffles sum the pieces.  The padding of a row is 255 in both and counts in neither.  The record goes to PINNED memory
+// with plain stores, a system-scope fence, and the serial last: the host reads nothing else to learn of a candidate.
+__global__ void __launch_bounds__(64) ferns_gate_kernel(const FernsDev d, unsigned serial, cf_ferns_gate* __restrict__ rec)
+{
+    const FernState* st = d.state;
+    const int id = st->match_id, lane = threadIdx.x;
+    int count = 0, val = 0;
+    if (id >= 0) {   // (uniform)
+        const uint4* qrow = reinterpret_cast<const uint4*>(d.cur_codes);
+        const uint4* krow = reinterpret_cast<const uint4*>(d.codes + (size_t)id * d.row_bytes);
+        for (int p = lane; p < d.row16; p += 64) {
+            const uint4 q = qrow[p], c = krow[p];
+            const uint4 m = make_uint4(good_mask(q.x) & good_mask(c.x), good_mask(q.y) & good_mask(c.y), good_mask(q.z) & good_mask(c.z),
+                                       good_mask(q.w) & good_mask(c.w));
+            count += __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
+            val += eq_bytes16(q, m, c);
+        }
+        for (int o = 32; o; o >>= 1) { count += __shfl_xor(count, o, 64); val += __shfl_xor(val, o, 64); }
+    }
+    if (lane == 0) {
+        rec->match_id = id;
+        rec->dissimilarity = st->min_match;
+        rec->overlap = id >= 0 ? (float)val / (float)count : 0.0f;   // 0 / 0 -> NaN: no candidate
+        rec->good_q = st->good_cur;
+        rec->keyframe_time = id >= 0 ? d.time[id] : 0;
+        rec->count = count;
+        rec->keyframes = st->searched;
+        __threadfence_system();
+        rec->serial = serial;
+    }
+}
+
+// ---- the candidate part of Ferns::findFrame (Ferns.cpp:231-256) on the device, one workgroup of 256.
+struct CloseArgs {
+    float curr[16], est[16];
+    float icp_error, icp_count, photo_threshold;
+    float fx, fy, cx, cy;   // of the reduced frame
+    int keyframe, lost, time, max_depth_mm;
+    int samples_ok;         // the fern count fits CF_FERNS_MAX_SAMPLES (else no constraints are written)
+};
+struct ConsBuffers { float *src, *dst, *time; };   // f32 [128][3], [128][3], [128]
+
+__device__ __forceinline__ float3 mul_pose(const float* m, float x, float y, float z)
+{
+    return make_float3(((m[0] * x + m[1] * y) + m[2] * z) + m[3], ((m[4] * x + m[5] * y) + m[6] * z) + m[7],
+                       ((m[8] * x + m[9] * y) + m[10] * z) + m[11]);
+}
+
+// (a) photometricCheck (Ferns.cpp:264-307) as the host block of cf_ferns_relocalise states it: f64 from the f32 inputs, the same
+// association (the build has no FMA contraction), truncation towards zero; sum and count are integers, reduced exactly.  (b) the accept
+// rule.  (c) when accepted and not lost, wave 0 takes the samples i = lane * (n / 50), compacts the valid ones IN ORDER with a ballot and
+// the count of valid lanes below, and writes a constraint row and its pin per valid sample.
+__global__ void __launch_bounds__(256) ferns_close_kernel(const FernsDev d, const CloseArgs a, const ConsBuffers cons, cf_ferns_closure* __restrict__ out)
+{
+    __shared__ int wave_sum[4], wave_cnt[4];
+    __shared__ int s_accept;
+    const int tid = threadIdx.x, id = a.keyframe;
+    const size_t npx = (size_t)d.npx;
+    const bool have = id >= 0 && id < d.state->count;
+    int sum = 0, cnt = 0;   // (at most 2048 ferns x 765: no overflow)
+    if (have) {
+        const float* F = d.pose + (size_t)id * 16;
+        const float* P = a.est;
+        const double fx = (double)a.fx, fy = (double)a.fy, cx = (double)a.cx, cy = (double)a.cy;
+        double Rd[9], td[3];   // [R^T R', R^T (t' - t)]: fernPose^-1 * estPose
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++)
+                Rd[i * 3 + j] = ((double)F[0 * 4 + i] * (double)P[0 * 4 + j] + (double)F[1 * 4 + i] * (double)P[1 * 4 + j]) +
+                                (double)F[2 * 4 + i] * (double)P[2 * 4 + j];
+            td[i] = ((double)F[0 * 4 + i] * ((double)P[3] - (double)F[3]) + (double)F[1 * 4 + i] * ((double)P[7] - (double)F[7])) +
+                    (double)F[2 * 4 + i] * ((double)P[11] - (double)F[11]);
+        }
+        const uint8_t* krgb = d.rgb + (size_t)id * npx * 3;
+        for (int i = tid; i < d.n; i += 256) {
+            const cf_fern t = d.table[i];
+            const size_t p = (size_t)t.y * d.rw + t.x;
+            const float z = d.cur_v[p + 2 * npx];
+            if (!(z > 0) || !((int)(z * 1000.0f) < a.max_depth_mm)) continue;
+            const double x = (double)d.cur_v[p], y = (double)d.cur_v[p + npx], zz = (double)z;
+            const double wx = ((Rd[0] * x + Rd[1] * y) + Rd[2] * zz) + td[0];
+            const double wy = ((Rd[3] * x + Rd[4] * y) + Rd[5] * zz) + td[1];
+            const double wz = ((Rd[6] * x + Rd[7] * y) + Rd[8] * zz) + td[2];
+            const double u = wx * fx / wz + cx, v = wy * fy / wz + cy;
+            if (!(fabs(u) < 1e9) || !(fabs(v) < 1e9)) continue;   // (not finite or far outside: no correspondence)
+            const int iu = (int)u, iv = (int)v;                   // truncation towards zero
+            if (iu < 0 || iv < 0 || iu >= d.rw || iv >= d.rh) continue;
+            const uint8_t* kp = krgb + ((size_t)iv * d.rw + iu) * 3;
+            const int k0 = kp[0], k1 = kp[1], k2 = kp[2];
+            if (!(k0 > 0 || k1 > 0 || k2 > 0)) continue;
+            const uint8_t* cp = d.cur_rgb + p * 3;
+            sum += abs(k0 - (int)cp[0]) + abs(k1 - (int)cp[1]) + abs(k2 - (int)cp[2]);
+            cnt++;
+        }
+    }
+    for (int o = 32; o; o >>= 1) { sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
+    if ((tid & 63) == 0) { wave_sum[tid >> 6] = sum; wave_cnt[tid >> 6] = cnt; }
+    __syncthreads();
+    if (tid == 0) {
+        sum = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+        cnt = (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
+        const double photo = cnt ? (double)sum / (double)cnt : (double)INFINITY;
+        const int thresh = a.lost ? 1400 : 2400;
+        const int accepted = have && (double)a.icp_error < 0.0003 && a.icp_count > (float)thresh && photo < (double)a.photo_threshold;
+        s_accept = accepted;
+        out->accepted = accepted;
+        out->photo_sum = sum; out->photo_count = cnt; out->photo_error = photo;
+        out->keyframe = have ? id : -1;
+        out->keyframe_time = have ? d.time[id] : 0;
+        out->icp_error = a.icp_error; out->icp_count = a.icp_count;
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    int rows = 0;
+    if (s_accept && !a.lost && a.samples_ok) {   // (uniform: the whole wave takes part in the ballot)
+        const int step = d.n / 50;               // Ferns.cpp:240 (samples_ok: step >= 1 and at most 64 samples)
+        const long long i = (long long)tid * step;
+        bool valid = false;
+        float x = 0, y = 0, z = 0;
+        if (i < d.n) {
+            const cf_fern t = d.table[i];
+            const size_t p = (size_t)t.y * d.rw + t.x;
+            z = d.cur_v[p + 2 * npx];
+            valid = z > 0 && (int)(z * 1000.0f) < a.max_depth_mm;   // NaN z: invalid
+            if (valid) { x = d.cur_v[p]; y = d.cur_v[p + npx]; }
+        }
+        const unsigned long long mask = __ballot(valid);
+        rows = 2 * __popcll(mask);
+        if (valid) {
+            const int j = __popcll(mask & ((1ull << tid) - 1ull));
+            const float3 raw = mul_pose(a.curr, x, y, z), model = mul_pose(a.est, x, y, z);
+            float* s = cons.src + 6 * j; float* t = cons.dst + 6 * j;
+            s[0] = raw.x; s[1] = raw.y; s[2] = raw.z; t[0] = model.x; t[1] = model.y; t[2] = model.z;
+            s[3] = model.x; s[4] = model.y; s[5] = model.z; t[3] = model.x; t[4] = model.y; t[5] = model.z;
+            cons.time[2 * j] = (float)a.time;
+            cons.time[2 * j + 1] = (float)d.time[id];
+        }
+    }
+    if (tid == 0) out->n_constraints = rows;
+}
+
 }  // namespace
 
 struct cf_ferns {
@@ -262,6 +406,15 @@ struct cf_ferns {
     FernState* h_state = nullptr;               // pinned
     std::vector<cf_fern> table;
     long long adds_enqueued = 0;                // upper bound of the device-side count
+    // the loop-closure seam
+    cf_ferns_gate* h_gate = nullptr;            // pinned: written by ferns_gate_kernel
+    cf_ferns_closure* h_close = nullptr;        // pinned: written by ferns_close_kernel
+    ConsBuffers cons{};
+    hipEvent_t gate_event = nullptr;
+    unsigned gate_serial = 0;                   // of the last cf_ferns_gate_async
+    bool gate_pending = false;
+    cf_ferns_gate gate{};                       // what the last cf_ferns_gate_wait read
+    bool gated = false;
 };
 
 static uint64_t splitmix64(uint64_t& s)
@@ -328,6 +481,16 @@ static int ferns_build(cf_ctx* ctx, cf_ferns* f)
     init.key_all = kArmed; init.key_match = kArmed; init.min_all = 3.402823466e+38f; init.min_match = 3.402823466e+38f; init.match_id = -1;
     *f->h_state = init;
     HIPCHK(ctx, hipMemcpyAsync(d.state, f->h_state, sizeof(FernState), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipHostMalloc((void**)&f->h_gate, sizeof(cf_ferns_gate)));
+    HIPCHK(ctx, hipHostMalloc((void**)&f->h_close, sizeof(cf_ferns_closure)));
+    memset(f->h_gate, 0, sizeof(cf_ferns_gate)); memset(f->h_close, 0, sizeof(cf_ferns_closure));
+    HIPCHK(ctx, hipMalloc((void**)&f->cons.src, sizeof(float) * 3 * CF_DEFORM_MAX_CONSTRAINTS));
+    HIPCHK(ctx, hipMalloc((void**)&f->cons.dst, sizeof(float) * 3 * CF_DEFORM_MAX_CONSTRAINTS));
+    HIPCHK(ctx, hipMalloc((void**)&f->cons.time, sizeof(float) * CF_DEFORM_MAX_CONSTRAINTS));
+    HIPCHK(ctx, hipMemsetAsync(f->cons.src, 0, sizeof(float) * 3 * CF_DEFORM_MAX_CONSTRAINTS, s));
+    HIPCHK(ctx, hipMemsetAsync(f->cons.dst, 0, sizeof(float) * 3 * CF_DEFORM_MAX_CONSTRAINTS, s));
+    HIPCHK(ctx, hipMemsetAsync(f->cons.time, 0, sizeof(float) * CF_DEFORM_MAX_CONSTRAINTS, s));
+    HIPCHK(ctx, hipEventCreateWithFlags(&f->gate_event, hipEventDisableTiming));
     HIPCHK(ctx, hipStreamSynchronize(s));
     // the relocalisation tracker: RGBDOdometry at (W/8) x (H/8) with the intrinsics divided by 8 (Ferns.cpp:34-35)
     cf_config sc{};
@@ -338,6 +501,65 @@ static int ferns_build(cf_ctx* ctx, cf_ferns* f)
     // parent it holds the old stream until then, and re-binding drains that stream (cf_set_stream synchronises the one it leaves)
     if (int r = cf_set_stream(f->small, ctx->stream)) return r;
     if (int r = cf_odom_create(f->small, &f->odom)) { ctx->set_error(std::string("cf_ferns_create: small tracker: ") + cf_last_error(f->small)); return r; }
+    return CF_OK;
+}
+
+// ICP of the current reduced maps against keyframe `id`'s (Ferns.cpp:205-229), shared by cf_ferns_relocalise and cf_ferns_find_frame:
+// fetches the keyframe's pose, fills result->pose and icp_*.  The reference never initialises the colour side of this tracker and runs
+// it with icpWeight 100, which switches the RGB term off: its (all-zero) images are never read.
+static int track_against_keyframe(cf_ferns* f, int id, const char* who, float fern_pose[16], cf_ferns_result* result, cf_track_stats* stats)
+{
+    cf_ctx* ctx = f->ctx;
+    const FernsDev& d = f->d;
+    const size_t npx = (size_t)d.npx;
+    HIPCHK(ctx, hipMemcpy(fern_pose, d.pose + (size_t)id * 16, 64, hipMemcpyDeviceToHost));
+    hipStream_t s = ctx->cur();
+    if (f->small->stream != s) if (int r = cf_set_stream(f->small, s)) return r;
+    hipLaunchKernelGGL(ferns_planar_to_x4_kernel, dim3((d.npx + 255) / 256), dim3(256), 0, s, d.vmap + (size_t)id * npx * 3,
+                       d.nmap + (size_t)id * npx * 3, d.npx, reinterpret_cast<float4*>(f->kf_v4), reinterpret_cast<float4*>(f->kf_n4));
+    HIPCHK(ctx, hipGetLastError());
+    auto sub = [&](int r, const char* what) { if (r) ctx->set_error(std::string(who) + ": " + what + ": " + cf_last_error(f->small)); return r; };
+    if (int r = sub(cf_odom_init_icp_model(f->odom, f->kf_v4, f->kf_n4, fern_pose), "initICPModel")) return r;
+    const float* vm[CF_NUM_PYRS] = {d.cur_v, nullptr, nullptr};
+    const float* nm[CF_NUM_PYRS] = {d.cur_n, nullptr, nullptr};
+    if (int r = sub(cf_odom_bind_frame_maps(f->odom, vm, nm), "bind")) return r;
+    float trans[3] = {fern_pose[3], fern_pose[7], fern_pose[11]};
+    float rot[9] = {fern_pose[0], fern_pose[1], fern_pose[2], fern_pose[4], fern_pose[5], fern_pose[6], fern_pose[8], fern_pose[9], fern_pose[10]};
+    cf_track_opts opts{};
+    opts.rgb_only = 0; opts.icp_weight = 100; opts.pyramid = 0; opts.fast_odom = 0; opts.so3 = 0;
+    if (int r = sub(cf_odom_get_incremental_transformation(f->odom, trans, rot, &opts, nullptr, stats), "getIncrementalTransformation")) return r;
+    float* P = result->pose;
+    P[0] = rot[0]; P[1] = rot[1]; P[2] = rot[2]; P[3] = trans[0];
+    P[4] = rot[3]; P[5] = rot[4]; P[6] = rot[5]; P[7] = trans[1];
+    P[8] = rot[6]; P[9] = rot[7]; P[10] = rot[8]; P[11] = trans[2];
+    P[12] = 0; P[13] = 0; P[14] = 0; P[15] = 1;
+    result->icp_ran = 1; result->icp_error = stats->last_icp_error; result->icp_count = stats->last_icp_count;
+    return CF_OK;
+}
+
+static bool loop_samples_ok(int n_ferns)
+{
+    if (n_ferns < 50) return false;
+    const int step = n_ferns / 50;
+    return (n_ferns + step - 1) / step <= CF_FERNS_MAX_SAMPLES;
+}
+
+// the launch of ferns_close_kernel and the read of its record
+static int close_candidate(cf_ferns* f, int keyframe, const float curr_pose[16], const float est_pose[16], float icp_error, float icp_count,
+                           int lost, int time, cf_ferns_closure* out)
+{
+    cf_ctx* ctx = f->ctx;
+    CloseArgs a{};
+    memcpy(a.curr, curr_pose, sizeof(a.curr)); memcpy(a.est, est_pose, sizeof(a.est));
+    a.icp_error = icp_error; a.icp_count = icp_count; a.photo_threshold = f->cfg.photo_threshold;
+    a.fx = f->small->cfg.fx; a.fy = f->small->cfg.fy; a.cx = f->small->cfg.cx; a.cy = f->small->cfg.cy;
+    a.keyframe = keyframe; a.lost = lost ? 1 : 0; a.time = time; a.max_depth_mm = f->cfg.max_depth_mm;
+    a.samples_ok = loop_samples_ok(f->d.n) ? 1 : 0;
+    hipStream_t s = ctx->cur();
+    hipLaunchKernelGGL(ferns_close_kernel, dim3(1), dim3(256), 0, s, f->d, a, f->cons, f->h_close);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    *out = *f->h_close;
     return CF_OK;
 }
 
@@ -401,7 +623,11 @@ void cf_ferns_destroy(cf_ferns* f)
     (void)hipFree(f->d_table); (void)hipFree(d.codes); (void)hipFree(d.cur_codes); (void)hipFree(d.good); (void)hipFree(d.time); (void)hipFree(d.co);
     (void)hipFree(d.pose); (void)hipFree(d.vmap); (void)hipFree(d.nmap); (void)hipFree(d.rgb); (void)hipFree(d.cur_v); (void)hipFree(d.cur_n);
     (void)hipFree(d.cur_rgb); (void)hipFree(f->kf_v4); (void)hipFree(f->kf_n4); (void)hipFree(d.state);
+    (void)hipFree(f->cons.src); (void)hipFree(f->cons.dst); (void)hipFree(f->cons.time);
+    if (f->gate_event) (void)hipEventDestroy(f->gate_event);
     if (f->h_state) (void)hipHostFree(f->h_state);
+    if (f->h_gate) (void)hipHostFree(f->h_gate);
+    if (f->h_close) (void)hipHostFree(f->h_close);
     delete f;
 }
 
@@ -512,7 +738,7 @@ int cf_ferns_download(cf_ferns* f, int id, uint8_t* codes, int* good, float pose
 int cf_ferns_relocalise(cf_ferns* f, const float curr_pose[16], int time, int min_age, int lost, cf_ferns_result* result)
 {
     if (!f || !result) return CF_EINVAL;
-    (void)curr_pose;   // (only the surface constraints of a loop closure read it, Ferns.cpp:240-255: out of scope)
+    (void)curr_pose;   // (only the surface constraints of a loop closure read it, Ferns.cpp:240-255: cf_ferns_find_frame)
     cf_ctx* ctx = f->ctx;
     const FernsDev& d = f->d;
     memset(result, 0, sizeof(*result));
@@ -537,31 +763,9 @@ int cf_ferns_relocalise(cf_ferns* f, const float curr_pose[16], int time, int mi
     }
     if (!(result->overlap > 0.3f)) return CF_OK;
     float fern_pose[16];
-    HIPCHK(ctx, hipMemcpy(fern_pose, d.pose + (size_t)id * 16, 64, hipMemcpyDeviceToHost));
-    // ICP of the current reduced maps against the keyframe's (Ferns.cpp:205-225).  The reference never initialises the colour side of
-    // this tracker and runs it with icpWeight 100, which switches the RGB term off: its (all-zero) images are never read.
-    hipStream_t s = ctx->cur();
-    if (f->small->stream != s) if (int r = cf_set_stream(f->small, s)) return r;
-    hipLaunchKernelGGL(ferns_planar_to_x4_kernel, dim3((d.npx + 255) / 256), dim3(256), 0, s, d.vmap + (size_t)id * npx * 3,
-                       d.nmap + (size_t)id * npx * 3, d.npx, reinterpret_cast<float4*>(f->kf_v4), reinterpret_cast<float4*>(f->kf_n4));
-    HIPCHK(ctx, hipGetLastError());
-    auto sub = [&](int r, const char* what) { if (r) ctx->set_error(std::string("cf_ferns_relocalise: ") + what + ": " + cf_last_error(f->small)); return r; };
-    if (int r = sub(cf_odom_init_icp_model(f->odom, f->kf_v4, f->kf_n4, fern_pose), "initICPModel")) return r;
-    const float* vm[CF_NUM_PYRS] = {d.cur_v, nullptr, nullptr};
-    const float* nm[CF_NUM_PYRS] = {d.cur_n, nullptr, nullptr};
-    if (int r = sub(cf_odom_bind_frame_maps(f->odom, vm, nm), "bind")) return r;
-    float trans[3] = {fern_pose[3], fern_pose[7], fern_pose[11]};
-    float rot[9] = {fern_pose[0], fern_pose[1], fern_pose[2], fern_pose[4], fern_pose[5], fern_pose[6], fern_pose[8], fern_pose[9], fern_pose[10]};
-    cf_track_opts opts{};
-    opts.rgb_only = 0; opts.icp_weight = 100; opts.pyramid = 0; opts.fast_odom = 0; opts.so3 = 0;
     cf_track_stats stats{};
-    if (int r = sub(cf_odom_get_incremental_transformation(f->odom, trans, rot, &opts, nullptr, &stats), "getIncrementalTransformation")) return r;
-    float* P = result->pose;
-    P[0] = rot[0]; P[1] = rot[1]; P[2] = rot[2]; P[3] = trans[0];
-    P[4] = rot[3]; P[5] = rot[4]; P[6] = rot[5]; P[7] = trans[1];
-    P[8] = rot[6]; P[9] = rot[7]; P[10] = rot[8]; P[11] = trans[2];
-    P[12] = 0; P[13] = 0; P[14] = 0; P[15] = 1;
-    result->icp_ran = 1; result->icp_error = stats.last_icp_error; result->icp_count = stats.last_icp_count;
+    if (int r = track_against_keyframe(f, id, "cf_ferns_relocalise", fern_pose, result, &stats)) return r;
+    const float* P = result->pose;
     // photometricCheck, Ferns.cpp:264-307, in f64 from the f32 inputs
     std::vector<float> cv(npx * 3);
     std::vector<uint8_t> crgb(npx * 3), krgb(npx * 3);
@@ -604,6 +808,96 @@ int cf_ferns_relocalise(cf_ferns* f, const float curr_pose[16], int time, int mi
     const int icp_count_thresh = lost ? 1400 : 2400;
     result->accepted = ((double)stats.last_icp_error < 0.0003 && stats.last_icp_count > (float)icp_count_thresh &&
                         result->photo_error < (double)f->cfg.photo_threshold) ? 1 : 0;
+    return CF_OK;
+}
+
+// ---- the loop-closure seam (include/cofusion_loop.h)
+int cf_ferns_gate_async(cf_ferns* f)
+{
+    if (!f) return CF_EINVAL;
+    cf_ctx* ctx = f->ctx;
+    hipStream_t s = ctx->cur();
+    hipLaunchKernelGGL(ferns_gate_kernel, dim3(1), dim3(64), 0, s, f->d, ++f->gate_serial, f->h_gate);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(f->gate_event, s));
+    f->gate_pending = true; f->gated = false;
+    return CF_OK;
+}
+
+int cf_ferns_gate_wait(cf_ferns* f, cf_ferns_gate* out)
+{
+    if (!f || !out) return CF_EINVAL;
+    cf_ctx* ctx = f->ctx;
+    if (!f->gate_pending) { ctx->set_error("cf_ferns_gate_wait: no cf_ferns_gate_async is outstanding"); return CF_ESTATE; }
+    HIPCHK(ctx, hipEventSynchronize(f->gate_event));
+    f->gate_pending = false;
+    f->gate = *f->h_gate;
+    if (f->gate.serial != f->gate_serial) { ctx->set_error("cf_ferns_gate_wait: the record is not the one of the last gate launch"); return CF_ESTATE; }
+    f->gated = true;
+    *out = f->gate;
+    return CF_OK;
+}
+
+int cf_ferns_constraints(cf_ferns* f, int keyframe, const float curr_pose[16], const float est_pose[16], float icp_error, float icp_count,
+                         int lost, int time, cf_ferns_closure* out)
+{
+    if (!f || !curr_pose || !est_pose || !out) return CF_EINVAL;
+    if (!lost && !loop_samples_ok(f->d.n)) {
+        f->ctx->set_error("cf_ferns_constraints: loop closure needs n_ferns >= 50 and at most 64 samples of stride n_ferns / 50");
+        return CF_EINVAL;
+    }
+    if (keyframe < 0 || keyframe >= f->cfg.capacity) { f->ctx->set_error("cf_ferns_constraints: no such keyframe"); return CF_EINVAL; }
+    return close_candidate(f, keyframe, curr_pose, est_pose, icp_error, icp_count, lost, time, out);
+}
+
+int cf_ferns_find_frame(cf_ferns* f, const float curr_pose[16], int time, int min_age, int lost, cf_ferns_result* result,
+                        cf_ferns_closure* closure)
+{
+    if (!f || !curr_pose || !result || !closure) return CF_EINVAL;
+    (void)min_age;
+    cf_ctx* ctx = f->ctx;
+    if (!f->gated) { ctx->set_error("cf_ferns_find_frame: gate the slot first (cf_ferns_gate_async, cf_ferns_gate_wait)"); return CF_ESTATE; }
+    if (!lost && !loop_samples_ok(f->d.n)) {
+        ctx->set_error("cf_ferns_find_frame: loop closure needs n_ferns >= 50 and at most 64 samples of stride n_ferns / 50");
+        return CF_EINVAL;
+    }
+    memset(result, 0, sizeof(*result));
+    memset(closure, 0, sizeof(*closure));
+    closure->keyframe = -1;
+    result->keyframe = -1;
+    result->pose[0] = result->pose[5] = result->pose[10] = result->pose[15] = 1.0f;
+    result->photo_error = INFINITY;
+    result->dissimilarity = f->gate.dissimilarity;
+    const int id = f->gate.match_id;
+    if (id < 0) return CF_OK;
+    if (id >= f->cfg.capacity) { ctx->set_error("cf_ferns_find_frame: the gate record names no keyframe of the database"); return CF_ESTATE; }
+    result->keyframe = id;
+    result->overlap = f->gate.overlap;
+    if (!(result->overlap > 0.3f)) return CF_OK;
+    float fern_pose[16];
+    cf_track_stats stats{};
+    if (int r = track_against_keyframe(f, id, "cf_ferns_find_frame", fern_pose, result, &stats)) return r;
+    if (int r = close_candidate(f, id, curr_pose, result->pose, stats.last_icp_error, stats.last_icp_count, lost, time, closure)) return r;
+    result->photo_count = (int)closure->photo_count;
+    result->photo_error = closure->photo_error;
+    result->accepted = closure->accepted;
+    return CF_OK;
+}
+
+int cf_ferns_constraint_buffers(cf_ferns* f, float** src, float** dst, float** time)
+{
+    if (!f) return CF_EINVAL;
+    if (src) *src = f->cons.src;
+    if (dst) *dst = f->cons.dst;
+    if (time) *time = f->cons.time;
+    return CF_OK;
+}
+
+int cf_ferns_keyframe_buffers(cf_ferns* f, float** poses, int32_t** times)
+{
+    if (!f) return CF_EINVAL;
+    if (poses) *poses = f->d.pose;
+    if (times) *times = f->d.time;
     return CF_OK;
 }
 

@@ -49,6 +49,7 @@ SIGNATURES = {
     "cf_deform_sample": (_I, [_V, _V, C.c_uint32, _I, _PI, _PI, _PI]),
     "cf_deform_set_nodes": (_I, [_V, _V, _V, _I]),
     "cf_deform_weights": (_I, [_V, _V, _V, _V, _I]),
+    "cf_deform_weights_device": (_I, [_V, _V, _V, _V, _I]),
     "cf_deform_assemble": (_I, [_V]),
     "cf_deform_iterate": (_I, [_V, C.POINTER(Step)]),
     "cf_deform_optimise": (_I, [_V, C.POINTER(Thresholds), C.POINTER(Result)]),
@@ -122,6 +123,11 @@ class Deform:
         src, ps = _host(src, np.float32, (-1, 3)); dst, pd = _host(dst, np.float32, (-1, 3)); tm, pt = _host(src_time, np.float32, (-1,))
         assert len(src) == len(dst) == len(tm)
         self.ctx._check(self.lib.cf_deform_weights(self.h, ps, pd, pt, len(src)))
+
+    def weights_device(self, src, dst, src_time, n):
+        """the same from device arrays (tensors or raw addresses) f32 [>= n, 3], [>= n, 3], [>= n]: no host-to-device copy"""
+        addr = lambda a: C.c_void_p(a) if isinstance(a, int) else _p(a)
+        self.ctx._check(self.lib.cf_deform_weights_device(self.h, addr(src), addr(dst), addr(src_time), int(n)))
 
     def assemble(self):
         self.ctx._check(self.lib.cf_deform_assemble(self.h))

@@ -20,7 +20,7 @@ class Config(C.Structure):
                 ("pyramid", C.c_int), ("rgb_only", C.c_int), ("model_spawn_offset", C.c_uint), ("enable_multiple_models", C.c_int),
                 ("enable_pose_logging", C.c_int), ("rank", C.c_int), ("world", C.c_int), ("device_frames_complete", C.c_int),
                 ("mid_frame_predict", C.c_int), ("shard_background", C.c_int), ("enqueue_threads", C.c_int),
-                ("colocate_background", C.c_int), ("reloc", C.c_int), ("early_index_maps", C.c_int)]
+                ("colocate_background", C.c_int), ("reloc", C.c_int), ("early_index_maps", C.c_int), ("time_delta", C.c_int)]
 
 
 class RedetectCandidate(C.Structure):
@@ -377,6 +377,29 @@ class CoFusion:
         for k in ("optimised", "accepted", "failed"):
             out[k] = bool(out[k])
         out["nodes"] = nodes.value
+        return out
+
+    def set_loop_closure(self, on=True, sample_rate=25000):
+        """Global loop closure in the frame loop (cofusion_set_loop_closure): every tracked frame is gated against the
+        keyframe database; an accepted fern match deforms the background map from constraints generated on the device, and an accepted
+        graph corrects the map, the keyframe poses and the camera pose.  Needs set_relocalisation first."""
+        self._check(self.lib.cofusion_set_loop_closure(self.h, int(bool(on)), int(sample_rate)))
+
+    def loop_stats(self):
+        """-> frames gated, candidates, fern accepts, graphs optimised / accepted / failed, the last accept's keyframe, its srcTime, node count
+        and tick, and its optimisation outcome under `last` (co_fusion_amd.deform.RESULT_FIELDS)"""
+        from . import deform as _deform
+
+        class _Stats(C.Structure):
+            _fields_ = [(k, C.c_int32) for k in ("gated", "candidates", "fern_accepts", "optimised", "accepted", "failed", "last_keyframe",
+                                                "last_keyframe_time", "last_nodes", "last_tick")] + [("last", _deform.Result)]
+        s = _Stats()
+        self._check(self.lib.cofusion_loop_stats(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k, _ in _Stats._fields_[:-1]}
+        last = {k: getattr(s.last, k) for k in _deform.RESULT_FIELDS}
+        for k in ("optimised", "accepted", "failed"):
+            last[k] = bool(last[k])
+        out["last"] = last
         return out
 
     def set_redetection(self, on=True, min_fit=0.5, min_cover=0.044, depth_tol=0.10, max_candidates=8, keep_min_surfels=4000,

@@ -1,7 +1,9 @@
 """ctypes binding of the fern keyframe database (cf_ferns_* in include/cofusion_hip.h; csrc/ferns.hip).
 
 ElasticFusion's random-fern relocaliser (Core/Ferns.cpp), device resident: `Ferns.add` is Ferns::addFrame without a host wait,
-`Ferns.relocalise` is Ferns::findFrame.  Tensors are torch CUDA tensors handed over as raw device pointers.
+`Ferns.relocalise` is Ferns::findFrame.  The loop-closure seam (include/cofusion_loop.h): `gate_async` / `gate_wait` after a search,
+`find_frame` for a camera that is not lost, `constraints` for its device part alone.  Tensors are torch CUDA tensors handed over as raw
+device pointers.
 """
 from __future__ import annotations
 
@@ -43,8 +45,43 @@ SIGNATURES = {
 }
 
 
+class FernsGate(C.Structure):
+    """cf_ferns_gate (include/cofusion_loop.h): 32 bytes"""
+    _fields_ = [("serial", C.c_uint32), ("match_id", C.c_int32), ("dissimilarity", C.c_float), ("overlap", C.c_float),
+                ("good_q", C.c_int32), ("keyframe_time", C.c_int32), ("count", C.c_int32), ("keyframes", C.c_int32)]
+
+
+class FernsClosure(C.Structure):
+    """cf_ferns_closure: 48 bytes"""
+    _fields_ = [("accepted", C.c_int32), ("n_constraints", C.c_int32), ("photo_sum", C.c_int64), ("photo_count", C.c_int64),
+                ("photo_error", C.c_double), ("keyframe", C.c_int32), ("keyframe_time", C.c_int32), ("icp_error", C.c_float),
+                ("icp_count", C.c_float)]
+
+
+MAX_SAMPLES = 64
+MAX_CONSTRAINTS = 128
+# the loop-closure seam (include/cofusion_loop.h)
+LOOP_SIGNATURES = {
+    "cf_ferns_gate_async": (_I, [_V]),
+    "cf_ferns_gate_wait": (_I, [_V, C.POINTER(FernsGate)]),
+    "cf_ferns_constraints": (_I, [_V, _I, _V, _V, _F, _F, _I, _I, C.POINTER(FernsClosure)]),
+    "cf_ferns_find_frame": (_I, [_V, _V, _I, _I, _I, C.POINTER(FernsResult), C.POINTER(FernsClosure)]),
+    "cf_ferns_constraint_buffers": (_I, [_V, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V)]),
+    "cf_ferns_keyframe_buffers": (_I, [_V, C.POINTER(_V), C.POINTER(_V)]),
+}
+
+
+def loop_samples(n_ferns):
+    """samples loop closure draws from n_ferns ferns (Ferns.cpp:240), or None where it is refused (fewer than 50 ferns, more than 64 samples)"""
+    if n_ferns < 50:
+        return None
+    step = n_ferns // 50
+    m = (n_ferns + step - 1) // step
+    return m if m <= MAX_SAMPLES else None
+
+
 def bind(lib):
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOOP_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
@@ -119,9 +156,65 @@ class Ferns:
         res = FernsResult()
         p = _pose(curr_pose)
         self.ctx._check(self.lib.cf_ferns_relocalise(self.h, p.ctypes.data, int(time), int(min_age), int(bool(lost)), C.byref(res)))
+        return self._result(res)
+
+    @staticmethod
+    def _result(res):
         return dict(accepted=bool(res.accepted), keyframe=res.keyframe, dissimilarity=np.float32(res.dissimilarity), overlap=np.float32(res.overlap),
                     pose=np.array(res.pose, np.float32).reshape(4, 4), icp_error=np.float32(res.icp_error), icp_count=np.float32(res.icp_count),
                     icp_ran=bool(res.icp_ran), photo_count=res.photo_count, photo_error=float(res.photo_error))
+
+    @staticmethod
+    def _closure(c):
+        return dict(accepted=bool(c.accepted), n_constraints=c.n_constraints, photo_sum=c.photo_sum, photo_count=c.photo_count,
+                    photo_error=float(c.photo_error), keyframe=c.keyframe, keyframe_time=c.keyframe_time, icp_error=np.float32(c.icp_error),
+                    icp_count=np.float32(c.icp_count))
+
+    def gate_async(self):
+        """blockHDAware of the current slot against the match of the last search: one launch, enqueued"""
+        self.ctx._check(self.lib.cf_ferns_gate_async(self.h))
+
+    def gate_wait(self):
+        g = FernsGate()
+        self.ctx._check(self.lib.cf_ferns_gate_wait(self.h, C.byref(g)))
+        return dict(serial=g.serial, match_id=g.match_id, dissimilarity=np.float32(g.dissimilarity), overlap=np.float32(g.overlap), good_q=g.good_q,
+                    keyframe_time=g.keyframe_time, count=g.count, keyframes=g.keyframes)
+
+    def constraints(self, keyframe, curr_pose, est_pose, icp_error, icp_count, lost, time):
+        """photometric check, accept rule and surface constraints against `keyframe`, the tracker's results handed in"""
+        c = FernsClosure()
+        cp, ep = _pose(curr_pose), _pose(est_pose)
+        self.ctx._check(self.lib.cf_ferns_constraints(self.h, int(keyframe), cp.ctypes.data, ep.ctypes.data, float(icp_error), float(icp_count),
+                                                      int(bool(lost)), int(time), C.byref(c)))
+        return self._closure(c)
+
+    def find_frame(self, curr_pose, time, min_age=300, lost=False):
+        """Ferns::findFrame for a slot that has been encoded, searched and gated -> (result as relocalise gives it, closure)"""
+        res, c = FernsResult(), FernsClosure()
+        p = _pose(curr_pose)
+        self.ctx._check(self.lib.cf_ferns_find_frame(self.h, p.ctypes.data, int(time), int(min_age), int(bool(lost)), C.byref(res), C.byref(c)))
+        return self._result(res), self._closure(c)
+
+    def constraint_buffers(self):
+        """device addresses of src, dst f32 [128][3] and time f32 [128]"""
+        s, d, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.lib.cf_ferns_constraint_buffers(self.h, C.byref(s), C.byref(d), C.byref(t)))
+        return s.value, d.value, t.value
+
+    def keyframe_buffers(self):
+        """device addresses of the database's poses f32 [capacity][16] and times i32 [capacity]"""
+        p, t = C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.lib.cf_ferns_keyframe_buffers(self.h, C.byref(p), C.byref(t)))
+        return p.value, t.value
+
+    def download_constraints(self, n):
+        """the first n rows of the constraint buffers -> src [n, 3], dst [n, 3], time [n] (host)"""
+        s, d, t = self.constraint_buffers()
+        src = np.zeros((n, 3), np.float32); dst = np.zeros((n, 3), np.float32); tm = np.zeros(n, np.float32)
+        for a, p in ((src, s), (dst, d), (tm, t)):
+            if n:
+                self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, a.ctypes.data_as(C.c_void_p), C.c_void_p(p), C.c_uint64(a.nbytes)))
+        return src, dst, tm
 
     def count(self):
         c, f = C.c_int(), C.c_int()

@@ -1275,11 +1275,29 @@ void CoFusion::setRelocalisation(bool on, int nFerns, float fernThresh, float ph
     if (on && !ownsCtx) throw std::runtime_error("setRelocalisation: not available for a sequence of a lock-step group");
     if (ferns) { cf_ferns_destroy(ferns); ferns = nullptr; }
     lastFrameRecovery = false; fernLastClosest = -1; recoveries = 0;   // the statistics belong to the database
+    closeLoops = false; fernFirstAdd = -1; fernCount = 0; loopSt = LoopStats{};
     if (!on) return;
     cf_ferns_config fc{};
     fc.n_ferns = nFerns; fc.capacity = capacity; fc.max_depth_mm = (int)(cfg.depthCutoff * 1000.0f); fc.photo_threshold = photoThresh;
     check(ctx, cf_ferns_create(ctx, &fc, nullptr, seed, &ferns), "cf_ferns_create");
-    fernThreshold = fernThresh; fernMinAge = minAge;
+    fernThreshold = fernThresh; fernMinAge = minAge; fernCount = nFerns;
+}
+
+void CoFusion::setLoopClosure(bool on, int sampleRate)
+{
+    if (on && dist.world > 1) throw std::runtime_error("setLoopClosure: a single-GPU option, like reloc");
+    if (on && !ownsCtx) throw std::runtime_error("setLoopClosure: not available for a sequence of a lock-step group");
+    if (on && !ferns) throw std::runtime_error("setLoopClosure: needs setRelocalisation on (the keyframe database)");
+    if (on && sampleRate < 1) throw std::runtime_error("setLoopClosure: sampleRate >= 1");
+    if (on) {   // Ferns.cpp:240 draws the samples 0, s, 2s, ... with s = n / 50; each may add a constraint and its pin
+        const int step = fernCount / 50;
+        if (fernCount < 50 || (fernCount + step - 1) / step > CF_FERNS_MAX_SAMPLES)
+            throw std::runtime_error("setLoopClosure: the fern count must be at least 50 and give at most 64 samples of stride n / 50");
+        if (!deform) check(ctx, cf_deform_create(ctx, &deform), "cf_deform_create");
+    }
+    closeLoops = on;
+    if (on) loopSampleRate = sampleRate;
+    loopSt = LoopStats{};
 }
 
 void CoFusion::relocStats(int* keyframes, int* lastClosest, int* recoveriesOut, int* databaseFull)
@@ -1304,7 +1322,27 @@ void CoFusion::fernsAfterPredict()
     const float* n = static_cast<const float*>(mbuf(ctx, g.handle(), 9));
     const uint8_t* img = static_cast<const uint8_t*>(mbuf(ctx, g.handle(), 10));
     if (!lost) {
-        check(ctx, cf_ferns_add_async(ferns, v, n, img, g.getPose().m, tick, fernThreshold), "cf_ferns_add_async");
+        // no keyframe can be older than min_age yet: nothing to gate, the frame is offered as ever
+        const bool gate = closeLoops && fernFirstAdd >= 0 && tick - fernFirstAdd > fernMinAge;
+        if (fernFirstAdd < 0) fernFirstAdd = tick;
+        if (!gate) {
+            check(ctx, cf_ferns_add_async(ferns, v, n, img, g.getPose().m, tick, fernThreshold), "cf_ferns_add_async");
+            return;
+        }
+        // Ferns::findFrame for a tracked camera (CoFusion.cpp:349, closeLoops).  The scan publishes the minimum over all keyframes and
+        // the match older than min_age in one pass, so the append below needs no second search.
+        cf_ferns_gate rec{};
+        check(ctx, cf_ferns_encode(ferns, v, n, img), "cf_ferns_encode");
+        check(ctx, cf_ferns_search(ferns, tick, fernMinAge), "cf_ferns_search");
+        check(ctx, cf_ferns_gate_async(ferns), "cf_ferns_gate_async");
+        check(ctx, cf_ferns_gate_wait(ferns, &rec), "cf_ferns_gate_wait");
+        loopSt.gated++;
+        fernLastClosest = -1;
+        if (rec.match_id >= 0 && rec.overlap > 0.3f) {
+            loopSt.candidates++;
+            if (closeLoop(rec)) return;   // (the corrected frame has been offered from the redone fill-in)
+        }
+        check(ctx, cf_ferns_append(ferns, g.getPose().m, tick, fernThreshold), "cf_ferns_append");
         return;
     }
     lastFrameRecovery = false;   // :352
@@ -1336,31 +1374,75 @@ int CoFusion::deformBackground(const float* src, const float* dst, const float* 
         s.insert(s.end(), src + 3 * i, src + 3 * i + 3); d.insert(d.end(), dst + 3 * i, dst + 3 * i + 3); t.push_back(srcTime[i]);
         if (pin) { s.insert(s.end(), dst + 3 * i, dst + 3 * i + 3); d.insert(d.end(), dst + 3 * i, dst + 3 * i + 3); t.push_back(dstTime[i]); }
     }
+    // the clock has already moved on from the frame the map was last fused in (frameEnd): the stamp and the prediction are that frame's
+    cf_deform_result res{};
+    const int nodes = deformMap(sampleRate > 0 ? sampleRate : 25000, [&] { return cf_deform_weights(deform, s.data(), d.data(), t.data(), (int)t.size()); },
+                                lost ? 0 : 1, nullptr, 0, &res);
+    if (result) *result = res;
+    if (res.accepted) check(ctx, cf_synchronize(ctx), "cf_synchronize");
+    return nodes;
+}
+
+int CoFusion::deformMap(int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes,
+                        cf_deform_result* result)
+{
     Model& g = *globalModel;
     uint32_t count = 0;
     check(ctx, cf_model_count(g.handle(), &count), "cf_model_count");
     float* map = static_cast<float*>(const_cast<void*>(mbuf(ctx, g.handle(), 11)));
     int nodes = 0, stride = 0, monotone = 0;
-    check(ctx, cf_deform_sample(deform, map, count, sampleRate > 0 ? sampleRate : 25000, &nodes, &stride, &monotone), "cf_deform_sample");
+    check(ctx, cf_deform_sample(deform, map, count, sampleRate, &nodes, &stride, &monotone), "cf_deform_sample");
     cf_deform_result res{};
     if (result) *result = res;
     if (nodes < 5 || !monotone) return nodes;
-    check(ctx, cf_deform_weights(deform, s.data(), d.data(), t.data(), (int)t.size()), "cf_deform_weights");
+    check(ctx, weigh(), "cf_deform_weights");
     check(ctx, cf_deform_optimise(deform, nullptr, &res), "cf_deform_optimise");
     if (result) *result = res;
     if (!res.accepted) return nodes;
+    if (correctedPose) g.overridePose(*correctedPose);
     cf_deform_reactivate re{};
     for (int i = 0; i < 16; i++) re.pose[i] = g.getPose().m[i];
     re.cam = cf_cam{cfg.fx, cfg.fy, cfg.cx, cfg.cy}; re.cols = cfg.width; re.rows = cfg.height; re.max_depth = maxDepthProcessed;
-    // the clock has already moved on from the frame the map was last fused in (frameEnd): the stamp and the prediction are that frame's
-    const int ahead = lost ? 0 : 1;
-    tick -= ahead;
+    tick -= clockAhead;
     re.depth = depthFiltered_dev; re.conf_threshold = g.getConfidenceThreshold(); re.tick = tick;
-    struct Restore { int& t; int a; ~Restore() { t += a; } } restore{tick, ahead};
+    struct Restore { int& t; int a; ~Restore() { t += a; } } restore{tick, clockAhead};
     check(ctx, cf_deform_apply(deform, map, count, &re), "cf_deform_apply");
+    if (keyframes > 0) {   // Deformation::constrain moves the fern poses with the map
+        float* poses = nullptr; int32_t* times = nullptr;
+        check(ctx, cf_ferns_keyframe_buffers(ferns, &poses, &times), "cf_ferns_keyframe_buffers");
+        check(ctx, cf_deform_apply_poses(deform, poses, times, keyframes), "cf_deform_apply_poses");
+    }
     fuseAndPredict(false, st.weightMultiplier, lost, true, 0);   // (as the recovery path: the next frame tracks against the corrected map)
-    check(ctx, cf_synchronize(ctx), "cf_synchronize");
     return nodes;
+}
+
+// A candidate of the gate: Ferns::findFrame, and for an accepted keyframe the deformation of the background map from the constraints
+// the fern kernel left on the device.  true: the loop was closed (map, keyframe poses and camera pose corrected, prediction redone,
+// the frame offered to the database from the redone fill-in); false: map and pose are untouched.
+bool CoFusion::closeLoop(const cf_ferns_gate& gate)
+{
+    Model& g = *globalModel;
+    cf_ferns_result res{};
+    cf_ferns_closure cl{};
+    check(ctx, cf_ferns_find_frame(ferns, g.getPose().m, tick, fernMinAge, 0, &res, &cl), "cf_ferns_find_frame");
+    if (!res.accepted || cl.n_constraints < 1) return false;
+    loopSt.fernAccepts++;
+    loopSt.lastKeyframe = fernLastClosest = res.keyframe;
+    loopSt.lastKeyframeTime = cl.keyframe_time;
+    loopSt.lastTick = tick;
+    float *src = nullptr, *dst = nullptr, *time = nullptr;
+    check(ctx, cf_ferns_constraint_buffers(ferns, &src, &dst, &time), "cf_ferns_constraint_buffers");
+    Mat4f est;
+    for (int i = 0; i < 16; i++) est.m[i] = res.pose[i];
+    cf_deform_result dr{};
+    loopSt.lastNodes = deformMap(loopSampleRate, [&] { return cf_deform_weights_device(deform, src, dst, time, cl.n_constraints); }, 0, &est,
+                                 gate.keyframes, &dr);
+    loopSt.last = dr;
+    loopSt.optimised += dr.optimised; loopSt.accepted += dr.accepted; loopSt.failed += dr.failed;
+    if (!dr.accepted) return false;
+    check(ctx, cf_ferns_add_async(ferns, static_cast<const float*>(mbuf(ctx, g.handle(), 8)), static_cast<const float*>(mbuf(ctx, g.handle(), 9)),
+                                  static_cast<const uint8_t*>(mbuf(ctx, g.handle(), 10)), g.getPose().m, tick, fernThreshold), "cf_ferns_add_async");
+    return true;
 }
 
 // The first index maps of the surfel chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) enqueued BEHIND the

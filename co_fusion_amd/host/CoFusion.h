@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <functional>
 #include <list>
 #include <memory>
 #include <string>
@@ -357,6 +358,21 @@ class CoFusion {
     void setRelocalisation(bool on, int nFerns = 500, float fernThreshold = 0.3095f, float photoThreshold = 115.0f, int minAge = 300,
                            uint64_t seed = 0, int capacity = 1024);
     void relocStats(int* keyframes, int* lastClosest, int* recoveries, int* databaseFull);
+    // Global loop closure (the closeLoops branch of CoFusion.cpp:345-384, which the reference stubs; ElasticFusion's).
+    // Off by default; with it off the frame loop is what it was, launch for launch.  On: a tracked frame encodes, searches and GATES its
+    // fill-in maps against the database (one more launch and one host wait on a 32-byte record); a candidate runs Ferns::findFrame
+    // (cf_ferns_find_frame), and an accepted one samples the deformation graph of the background map, weights the constraints the fern
+    // kernel left on the device, optimises, and on acceptance moves the map and the keyframe poses, overrides the camera pose and
+    // redoes the prediction.  Needs setRelocalisation on (which, called again, switches this off) and a fern count loop closure
+    // accepts (CF_FERNS_MAX_SAMPLES); single process, not a sequence of a lock-step group.
+    void setLoopClosure(bool on, int sampleRate = 25000);
+    struct LoopStats {
+        int gated = 0, candidates = 0, fernAccepts = 0;   // frames gated, candidates (match with overlap > 0.3), Ferns::findFrame accepts
+        int optimised = 0, accepted = 0, failed = 0;      // graphs
+        int lastKeyframe = -1, lastKeyframeTime = -1, lastNodes = 0, lastTick = -1;   // of the last fern accept: keyframe, its srcTime, graph nodes, the frame's tick
+        cf_deform_result last{};
+    };
+    const LoopStats& loopStats() const { return loopSt; }
     bool isGroupSequence() const { return !ownsCtx; }
     // Loop closure of the background map from caller-supplied constraints: sample the deformation graph, weight the
     // constraint points, optimise, and on acceptance move the map (cf_deform_*) and redo the prediction.  Returns the node count.
@@ -464,7 +480,14 @@ class CoFusion {
     int fernMinAge = 300, fernLastClosest = -1, recoveries = 0;
     bool lastFrameRecovery = false;   // CoFusion.h:363
     void fernsAfterPredict();
-    cf_deform* deform = nullptr;   // deformBackground (created at first use)
+    cf_deform* deform = nullptr;   // deformBackground, setLoopClosure (created at first use)
+    bool closeLoops = false;       // setLoopClosure
+    int loopSampleRate = 25000, fernCount = 0, fernFirstAdd = -1;   // fernFirstAdd: tick of the first frame offered to the database
+    LoopStats loopSt;
+    bool closeLoop(const cf_ferns_gate& gate);
+    // the body deformBackground and closeLoop share: sample, weigh (the caller's upload), optimise, and on acceptance the map pass with
+    // the reactivation stamp (at *correctedPose when given, which becomes the camera pose), the keyframe poses and the prediction
+    int deformMap(int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes, cf_deform_result* result);
     // device frame buffers (CoFusion::textures)
     // filtered depth + its pyramid are double buffered: the filter of frame t+1 runs on an auxiliary stream while the fusion
     // passes of frame t still read frame t's filtered depth (processFrame)

@@ -49,6 +49,7 @@ void cofusion_default_config(cofusion_config* c)
     c->colocate_background = d.colocateBackground;
     c->reloc = d.reloc;
     c->early_index_maps = d.earlyIndexMaps;
+    c->time_delta = 0;   // (open loop: Config::timeDelta's default)
 }
 
 static CoFusion::Config to_config(const cofusion_config* c)
@@ -69,6 +70,7 @@ static CoFusion::Config to_config(const cofusion_config* c)
     d.colocateBackground = c->colocate_background != 0;
     d.reloc = c->reloc != 0;
     d.earlyIndexMaps = c->early_index_maps != 0;
+    if (c->time_delta > 0) d.timeDelta = c->time_delta;
     return d;
 }
 
@@ -170,6 +172,22 @@ int cofusion_deform_background(cofusion_handle* h, const float* src, const float
     int got = 0;
     GUARD(got = h->cf->deformBackground(src, dst, src_time, dst_time, n, pin != 0, sample_rate, static_cast<cf_deform_result*>(result)));
     if (nodes) *nodes = got;
+    return 0;
+}
+int cofusion_set_loop_closure(cofusion_handle* h, int on, int sample_rate)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->borrowed) { g_err = "loop closure is not available for a sequence of a lock-step group"; return -1; }
+    GUARD(h->cf->setLoopClosure(on != 0, sample_rate > 0 ? sample_rate : 25000));
+    return 0;
+}
+int cofusion_loop_stats(cofusion_handle* h, cofusion_loop_stats_t* out)
+{
+    if (!h || !out) { g_err = "cofusion_loop_stats: bad arguments"; return -1; }
+    const CoFusion::LoopStats& s = h->cf->loopStats();
+    *out = cofusion_loop_stats_t{s.gated, s.candidates, s.fernAccepts, s.optimised, s.accepted, s.failed, s.lastKeyframe, s.lastKeyframeTime, s.lastNodes, s.lastTick, {}};
+    static_assert(sizeof(s.last) == sizeof(out->last_result), "cf_deform_result is 8 words");
+    memcpy(out->last_result, &s.last, sizeof(out->last_result));
     return 0;
 }
 

@@ -49,6 +49,10 @@ typedef struct {
                                  * DEVICE, behind the segmentation and before the frame's host wait (cf_models_preindex), so the GPU works
                                  * while the host reads poses and decisions; 0: with the rest of the surfel chain, after the wait.  Results are
                                  * identical either way. */
+    int time_delta;             /* ElasticFusion's timeDelta: a surfel not seen for more than this many ticks is inactive (it is neither
+                                 * tracked against nor fused into).  <= 0 (default): never, the open-loop operation of the reference
+                                 * (MainController.cpp:328).  Loop closure (cofusion_set_loop_closure) wants a finite value, ElasticFusion
+                                 * runs with 200: a camera that returns then fuses fresh surfels, which the closure moves onto the old ones. */
 } cofusion_config;
 
 void cofusion_default_config(cofusion_config *cfg);
@@ -100,6 +104,24 @@ int cofusion_reloc_stats(cofusion_handle *h, int *keyframes, int *last_closest, 
  * a sequence handle of a lock-step group.  Waits for the stream. */
 int cofusion_deform_background(cofusion_handle *h, const float *src, const float *dst, const float *src_time, const float *dst_time, int n,
                                int pin, int sample_rate, void *result, int *nodes);
+/* Global loop closure in the frame loop (the closeLoops branch of CoFusion.cpp:345-384): with it on, every tracked frame
+ * is encoded, searched and gated against the keyframe database (one small launch and one host wait on a 32-byte record, skipped while
+ * no keyframe can be older than min_age); a candidate (a match with overlap > 0.3) runs Ferns::findFrame; an accepted one deforms the
+ * background map from the constraints the fern kernel left on the device, and an accepted graph moves the map (with the reactivation
+ * stamp) and the keyframe poses, overrides the camera pose with the tracker's estimate and redoes the prediction.  It runs at the end of
+ * the frame: the corrected map is first tracked against in the next frame.  sample_rate <= 0: 25000.  Needs cofusion_set_relocalisation
+ * on (calling that again switches this off) with at least 50 ferns that give at most 64 samples of stride n / 50 (500: 50, 2048: 52,
+ * 127: 64; 99 is refused); world == 1; refused for a sequence handle of a lock-step group.  Off (the default): the frame loop is
+ * unchanged. */
+int cofusion_set_loop_closure(cofusion_handle *h, int on, int sample_rate);
+typedef struct {
+    int32_t gated, candidates, fern_accepts;        /* frames gated, candidates, Ferns::findFrame accepts */
+    int32_t optimised, accepted, failed;            /* deformation graphs */
+    int32_t last_keyframe, last_keyframe_time, last_nodes, last_tick;   /* of the last fern accept (-1, -1, 0, -1: none): the keyframe, its srcTime,
+                                                                          * the graph's nodes, the frame's tick */
+    int32_t last_result[8];                         /* its cf_deform_result as cofusion_deform_background returns it */
+} cofusion_loop_stats_t;
+int cofusion_loop_stats(cofusion_handle *h, cofusion_loop_stats_t *out);
 /* Re-detection of inactive object models (the reference's CoFusion::redetectModels is an empty hook, CoFusion.cpp:599-602).
  * A model whose label gets no superpixels is deactivated; kept models (surfel count >= keep_min_surfels and confidence threshold >
  * keep_conf_threshold -- 4000 / 0.3, the reference's rule) wait in a list.  Off (the default) nothing reads that list: an object that

@@ -757,6 +757,8 @@ int cf_ferns_download(cf_ferns *f, int id, uint8_t *codes, int *good, float pose
  * none), the match (-1: none) and the decision of the last append; each nullable */
 int cf_ferns_last_search(cf_ferns *f, int32_t *co_host, int co_capacity, int *searched, float *min_all, float *min_match, int *match_id,
                          int *appended);
+/* the loop-closure seam of the database (gate, constraints, findFrame for a camera that is not lost) */
+#include "cofusion_loop.h"
 
 /* ------------------------------------------- frame decoder of the .klg log player ---- */
 /* Finishes the frames of a .klg log on the device (csrc/frame_decode.hip): host threads inflate the depth and
@@ -948,6 +950,8 @@ int cf_deform_sample(cf_deform *d, const float *map_dev, uint32_t count, int sam
 int cf_deform_set_nodes(cf_deform *d, const float *nodes_host, const float *params_host, int n);
 /* the constraints (host: src, dst [n][3], src_time [n]; a pin is the constraint dst -> dst at dst's time) and their weight sets */
 int cf_deform_weights(cf_deform *d, const float *src, const float *dst, const float *src_time, int n);
+/* the same from device arrays of the same shapes (cf_ferns_constraint_buffers): no host-to-device copy */
+int cf_deform_weights_device(cf_deform *d, const float *src_dev, const float *dst_dev, const float *src_time_dev, int n);
 /* residuals, A = J^T J in band storage and b = -J^T r for the current parameters */
 int cf_deform_assemble(cf_deform *d);
 /* one Gauss-Newton step: assemble, band Cholesky, parameters += delta, the new error.  failed = 1: a pivot <= 0, parameters unchanged */

@@ -10,7 +10,14 @@ line and writes it to profiles/loop_bench.json:
   * wall time of cofusion_deform_background on a fused 640x480 map (an accepted correction, and one the 0.06 gate turns away) beside
     the wall time of a plain frame of the same sequence.
 
+With --seam, the legs of the fern seam (cofusion_set_loop_closure) instead, merged into the same file under "seam": the gate launch and
+the closure launch at 500 ferns and 640x480, cf_ferns_find_frame's wall time beside cf_ferns_relocalise's on the same state, frames/s of
+bench.py's objects4 workload with loop closure on against relocalisation alone and against off (alternated --rounds times in one
+process; the price of the per-frame wait in microseconds beside the relocalisation leg's own spread), and the wall time of the frame
+that closes the loop in the scenario of tests/test_loop_closure_gpu.py.
+
     python tools/loop_bench.py [--iters 30] [--no-frames]
+    python tools/loop_bench.py --seam [--steps 300] [--warmup 30] [--rounds 3] [--min-age 30]
 """
 import argparse
 import json
@@ -105,12 +112,140 @@ def frames(torch):
         cf.close()
 
 
+def seam_kernels(torch, iters):
+    """the fern side of the seam at 500 ferns, 640x480 (the room of tests/ferns_scene.py, query 94 against keyframe 2): the gate launch
+    and the closure launch by in-stream events, cf_ferns_find_frame's wall time against cf_ferns_relocalise's on the same state"""
+    import ferns_scene as fs
+    from co_fusion_amd import api, ferns
+    c = fs.CAM
+    ctx = api.Context(fs.W, fs.H, c.fx, c.fy, c.cx, c.cy, max_models=1, max_surfels=1024)
+    f = ferns.Ferns(ctx, n_ferns=500, capacity=8, max_depth_mm=5000, photo_threshold=115.0, seed=7)
+    try:
+        for i, t in enumerate(fs.KEYFRAME_TIMES):
+            f.add(*(ctx.to_device(a) for a in fs.maps(t)), fs.view(t)[2], 1 + i, -1.0)
+        f.encode(*(ctx.to_device(a) for a in fs.maps(fs.QUERY_TIME)))
+        curr = fs.view(fs.QUERY_TIME)[2]
+        f.search(1000, 300)
+        gate_ms = median_ms(torch, lambda: (f.gate_async(), f.gate_wait()), iters)
+        f.gate_async(); g = f.gate_wait()
+        res, cl = f.find_frame(curr, 1000, 300, lost=False)
+        close_ms = median_ms(torch, lambda: f.constraints(res["keyframe"], curr, res["pose"], res["icp_error"], res["icp_count"], False, 1000), iters)
+        wall = dict(find_frame=[], relocalise=[])
+        for _ in range(iters + 3):
+            f.search(1000, 300); f.gate_async(); f.gate_wait()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            f.find_frame(curr, 1000, 300, lost=False)
+            wall["find_frame"].append((time.perf_counter() - t0) * 1e3)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            f.relocalise(curr, 1000, 300, lost=False)   # (its own search included: one launch)
+            wall["relocalise"].append((time.perf_counter() - t0) * 1e3)
+        return dict(gate_launch_and_wait_ms=gate_ms, closure_launch_and_read_ms=close_ms, overlap=float(g["overlap"]), accepted=bool(cl["accepted"]),
+                    n_constraints=cl["n_constraints"], find_frame_wall_ms=float(np.median(wall["find_frame"][3:])),
+                    relocalise_wall_ms=float(np.median(wall["relocalise"][3:])))
+    finally:
+        f.close(); ctx.close()
+
+
+def seam_objects4(torch, steps, warmup, rounds, min_age):
+    """frames/s of bench.py's objects4 workload in ONE process, the legs alternated `rounds` times: as bench.py runs it, with the
+    relocalisation switch on, and with loop closure on top (every measured frame gated: min_age ticks are over before the warm-up ends)"""
+    import bench
+    from co_fusion_amd import facade
+    wl = bench.WORKLOADS["objects4"]
+    W, H = wl["size"]
+    n_frames, n_obj = 16, wl["n_obj"]
+    cam, fr = bench.make_stream(W, H, n_frames, n_obj=n_obj, seed=1234)
+    dev = torch.device("cuda", 0)
+    resident = [dict(depth=torch.from_numpy(f["depth"]).to(dev), rgba=torch.from_numpy(f["rgba"]).to(dev)) for f in fr]
+    P = 24 * n_obj + 30
+    legs = (("off", {}, 0), ("relocalisation_on", dict(reloc=1), 1), ("loop_closure_on", dict(reloc=1, time_delta=200), 2))
+    out = {name: dict(frames_per_s=[]) for name, _, _ in legs}
+    for _ in range(rounds):
+        for name, kw, level in legs:
+            cf = facade.CoFusion(W, H, cam.fx, cam.fy, cam.cx, cam.cy, enable_multiple_models=1, device_frames_complete=1, **kw)
+            if level >= 1:
+                cf.set_relocalisation(True, min_age=min_age)
+            if level >= 2:
+                cf.set_loop_closure(True)
+            for i in range(P):   # the pre-roll of bench.py: ground-truth masks until the object models exist
+                f = fr[bench.frame_index(i, n_frames)]
+                cf.process_frame(f["depth"], f["rgb"], mask=(f["label"] * 40).astype(np.uint8), timestamp=i)
+            def run(lo, hi):
+                for i in range(lo, hi):
+                    r = resident[bench.frame_index(i, n_frames)]
+                    cf.process_frame_device(r["depth"], r["rgba"], timestamp=i)
+            run(P, P + warmup)
+            torch.cuda.synchronize()
+            g0 = cf.loop_stats()["gated"] if level >= 2 else 0
+            t0 = time.perf_counter()
+            run(P + warmup, P + warmup + steps)
+            torch.cuda.synchronize()
+            out[name]["frames_per_s"].append(round(steps / (time.perf_counter() - t0), 1))
+            if level >= 2:
+                out[name]["stats"] = cf.loop_stats(); out[name]["gated_in_measured_frames"] = out[name]["stats"]["gated"] - g0
+            cf.close()
+    med = {k: float(np.median(v["frames_per_s"])) for k, v in out.items()}
+    out["per_frame_price_us_vs_relocalisation_on"] = round((1.0 / med["loop_closure_on"] - 1.0 / med["relocalisation_on"]) * 1e6, 1)
+    out["relocalisation_on_spread_us"] = round((1.0 / min(out["relocalisation_on"]["frames_per_s"]) - 1.0 / max(out["relocalisation_on"]["frames_per_s"])) * 1e6, 1)
+    return out
+
+
+def seam_scenario(torch):
+    """wall time of the frame that closes the loop in the scenario of tests/test_loop_closure_gpu.py, beside the plain frames before it"""
+    import test_loop_closure_gpu as sc
+    from co_fusion_amd import facade, synth
+    scene = synth.Scene(n_obj=0, seed=1234)
+    scene.camera_pose = lambda t: sc.yaw_pose(sc.TURN_DEG * t)
+    cam, cache = synth.Camera(), {}
+    cf = facade.CoFusion(reloc=1, enable_multiple_models=0, max_models=2, max_surfels=1 << 22, time_delta=sc.TIME_DELTA)
+    try:
+        cf.set_relocalisation(True, min_age=sc.MIN_AGE, seed=3)
+        cf.set_loop_closure(True, sample_rate=sc.RATE)
+        rows = []
+        for k in range(sc.LAST + 1):
+            if k % 120 not in cache:
+                cache[k % 120] = scene.render(cam, k % 120, noise=False)[:2]
+            d, rgb = cache[k % 120]
+            before = cf.loop_stats()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            cf.process_frame(d, rgb, timestamp=k, in_pose=sc.yaw_pose(sc.DRIFT * sc.TURN_DEG * k))
+            torch.cuda.synchronize(); ms = (time.perf_counter() - t0) * 1e3
+            after = cf.loop_stats()
+            kind = ("closing" if after["accepted"] > before["accepted"] else "graph_rejected" if after["optimised"] > before["optimised"] else
+                    "fern_rejected" if after["candidates"] > before["candidates"] else "gated" if after["gated"] > before["gated"] else "plain")
+            rows.append((kind, ms))
+            if kind == "closing":
+                break
+        out = {k: dict(frames=sum(1 for a, _ in rows if a == k), median_wall_ms=float(np.median([m for a, m in rows if a == k])))
+               for k in ("plain", "gated", "fern_rejected", "graph_rejected", "closing") if any(a == k for a, _ in rows)}
+        out["stats"] = cf.loop_stats(); out["surfels"] = cf.model_info(0)["count"]
+        return out
+    finally:
+        cf.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--no-frames", action="store_true")
+    ap.add_argument("--seam", action="store_true", help="only the legs of the fern seam (written to the 'seam' entry of profiles/loop_bench.json)")
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--min-age", type=int, default=30)
     a = ap.parse_args()
     import torch
+    path = os.path.join(ROOT, "profiles", "loop_bench.json")
+    if a.seam:
+        out = json.load(open(path)) if os.path.exists(path) else {}
+        out["seam"] = dict(kernels=seam_kernels(torch, a.iters), scenario=seam_scenario(torch))
+        if not a.no_frames:
+            out["seam"]["objects4"] = seam_objects4(torch, a.steps, a.warmup, a.rounds, a.min_age)
+        line = json.dumps(out)
+        print(json.dumps(out["seam"]))
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     out = stages(torch, a.iters)
     if not a.no_frames:
         out["deform_background"] = frames(torch)

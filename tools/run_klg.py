@@ -58,6 +58,11 @@ def main():
     ap.add_argument("--photo-threshold", type=float, default=115.0)
     ap.add_argument("--fern-min-age", type=int, default=300, help="ticks a keyframe must be old to be matched")
     ap.add_argument("--fern-seed", type=int, default=0)
+    ap.add_argument("--close-loops", action="store_true", help="global loop closure: a view that returns with drift corrects the background map "
+                                                                "(implies --relocalise)")
+    ap.add_argument("--loop-sample-rate", type=int, default=25000, help="every N-th surfel of the background map is a node of the deformation graph")
+    ap.add_argument("--time-delta", type=int, default=0, help="ticks after which an unseen surfel is inactive (0: never; ElasticFusion's 200 with "
+                                                              "--close-loops)")
     ap.add_argument("--redetect", action="store_true", help="an object that is labelled again resumes its kept inactive model (old id and map) "
                                                             "where that explains the frame, instead of a new model")
     ap.add_argument("--redetect-fit", type=float, default=-1.0, help="least agree_on_label / (agree + seen_through) of a candidate (default 0.5)")
@@ -95,10 +100,14 @@ def main():
             raise SystemExit("a dataset with masks needs the multi-model mode (no --static)")
     else:
         log = None if a.player else klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
+    a.relocalise = a.relocalise or a.close_loops
+    time_delta = a.time_delta if a.time_delta > 0 else 200 if a.close_loops else 0
     cf = facade.CoFusion(a.width, a.height, a.fx, a.fy, a.cx, a.cy, max_surfels=a.max_surfels, enable_multiple_models=int(not a.static),
-                         enable_pose_logging=1, reloc=int(a.relocalise))
+                         enable_pose_logging=1, reloc=int(a.relocalise), time_delta=time_delta)
     if a.relocalise:
         cf.set_relocalisation(True, fern_threshold=a.fern_threshold, photo_threshold=a.photo_threshold, min_age=a.fern_min_age, seed=a.fern_seed)
+    if a.close_loops:
+        cf.set_loop_closure(True, sample_rate=a.loop_sample_rate)
     if a.redetect:
         if a.static:
             raise SystemExit("--redetect needs the multi-model mode (no --static)")
@@ -169,6 +178,8 @@ def main():
     print(f"{n} frames of {log.num_frames} in {dt:.2f} s ({n / dt:.1f} frames/s {how}), {cf.num_models} active models")
     if a.relocalise:
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
+    if a.close_loops:
+        print(f"loop closure: {cf.loop_stats()}")
     if a.redetect:
         print(f"re-detection: {cf.redetect_stats()}, {cf.num_inactive_models} inactive model(s) kept")
     if a.export_async:
