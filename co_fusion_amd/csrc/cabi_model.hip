@@ -31,7 +31,8 @@ struct cf_model {
     unsigned* block_sums = nullptr;
     unsigned* d_count = nullptr;      // device surfel count
     unsigned* d_nfresh = nullptr;     // appended new-unstable count
-    unsigned* d_tmp2 = nullptr;       // [4] scratch counters
+    unsigned* d_tmp2 = nullptr;       // [8] scratch counters: [2], [3] the fill ratio's (covered, total); [4], [5] its 64-bit accumulator | ticket in the batched chain
+    int ratio_blocks = 0;             // workgroups of the resolve that hold a sample position of the fill ratio
     unsigned* h_counts = nullptr;     // pinned [4]
     // per-pixel rank-ordered fusion records
     float* records = nullptr;         // [N*12]
@@ -94,7 +95,9 @@ int cf_model_create(cf_ctx* ctx, int max_surfels, cf_model** out)
     if (int r = dmalloc(ctx, &m->block_sums, (M + Q) / 2048 + N / 2048 + 16)) return r;
     if (int r = dmalloc(ctx, &m->d_count, 1)) return r;
     if (int r = dmalloc(ctx, &m->d_nfresh, 1)) return r;
-    if (int r = dmalloc(ctx, &m->d_tmp2, 4)) return r;
+    if (int r = dmalloc(ctx, &m->d_tmp2, 8)) return r;
+    HIPCHK(ctx, hipMemsetAsync(m->d_tmp2, 0, 8 * sizeof(unsigned), ctx->cur()));   // ([4], [5]: zero between launches, SplatFillArgs::acc)
+    m->ratio_blocks = fill_ratio_sample_blocks(W, H);
     if (int r = dmalloc(ctx, &m->records, N * 12)) return r;
     if (int r = dmalloc(ctx, &m->fresh, Q * 12)) return r;
     if (int r = dmalloc(ctx, &m->new_flags, N)) return r;
@@ -602,9 +605,18 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         p.confThreshold = it.conf_threshold; p.time = it.time; p.maxTime = it.time; p.timeDelta = time_delta; p.rays = m->rays; p.keys = m->keys;
         p.image = m->splat_image; p.vertexConf = m->splat_vertex; p.normalRad = m->splat_normal; p.time16 = m->splat_time;
         m->ratio_valid = false;  // a new prediction: any prefetched fill-in ratio is stale
+        if (it.fill_in)          // Model::performFillIn and the count of cf_model_prefetch_fill_ratio inside the resolve launch (SplatFillArgs)
+            p.fill = SplatFillArgs{it.depth_filtered, it.rgba, m->inv_fx, m->inv_fy, it.passthrough_geom ? 1 : 0, it.passthrough_rgb ? 1 : 0,
+                                   m->fill_vertex, m->fill_normal, m->fill_image, reinterpret_cast<unsigned long long*>(m->d_tmp2 + 4),
+                                   m->d_tmp2 + 2, m->h_counts + 2, m->ratio_blocks};
     }
     launch_combined_predict_batch(s, pa.data(), n, cam, W, H);
     LAUNCHCHK(ctx);
+    for (int k = 0; k < n; k++)
+        if (items[k].fill_in) {   // (as cf_model_prefetch_fill_ratio: the resolve launch publishes the two counts to pinned memory)
+            HIPCHK(ctx, hipEventRecord(items[k].model->ratio_event, s));
+            items[k].model->ratio_valid = true;
+        }
     if (surf_ev >= 0) HIPCHK(ctx, hipEventRecord(ctx->surf_events[surf_ev + 1], s));
     if (!fusing.empty()) {
         HIPCHK(ctx, hipEventRecord(ctx->batch_event, s));

@@ -396,9 +396,24 @@ __host__ __device__ inline void inv44f(const float a[16], float o[16])
 }
 // the tracked poses of n trackers (their device states, as the last solve left them), inverted into out[k][16]: what the index pass of a
 // model needs of its pose, without the host
+// Model::performFillIn and the count of CoFusion::requiresFillIn inside the resolve launch of the prediction they read (all zeros: not
+// asked for).  The thread that has just formed a texel of the prediction evaluates the fill-in on it (fill_in_px, the statements of
+// fill_in_kernel) and, at the sample positions of fill_ratio_kernel, counts it; of the workgroups that hold sample positions the one
+// that finishes last (a completion ticket, nobody waits) publishes (covered, dw * dh) to out2 / out2_host and leaves acc zeroed for
+// the next launch.
+struct SplatFillArgs {
+    const float* depth_filt; const uint8_t* rgba;   // the frame: filtered depth, RGBA8; depth_filt == nullptr: plain resolve
+    float inv_fx, inv_fy; int pass_geom, pass_rgb;
+    float* fill_vertex; float* fill_normal; uint8_t* fill_image;
+    unsigned long long* acc;                 // device: covered count << 32 | ticket -- zero between launches
+    unsigned* out2; unsigned* out2_host;     // [2] each: device, pinned host
+    int sample_blocks;                       // fill_ratio_sample_blocks(cols, rows)
+};
+int fill_ratio_sample_blocks(int cols, int rows);
 struct SplatPassArgs {   // ModelProjection::combinedPredict of one model
     const float* surfels; const unsigned* count; unsigned count_bound; float t_inv[16]; float maxDepth, confThreshold; int time, maxTime, timeDelta;
     const float* rays; unsigned long long* keys; uint8_t* image; float* vertexConf; float* normalRad; uint16_t* time16;
+    SplatFillArgs fill;
 };
 struct UpdatePassArgs { const float* in; const unsigned* count; unsigned count_bound; unsigned* owner; const float* records; int time; float* out; };
 struct SurfelFuseArgs {

@@ -444,6 +444,7 @@ __global__ void __launch_bounds__(kB) splat_rays_kernel(cf_cam cam, int cols, in
 struct SplatArgs {   // combinedPredict of one model (both kernels)
     const float4* surfels; const unsigned* count; Mat4 t_inv; float maxDepth, confThreshold; int time, maxTime, timeDelta;
     const float4* rays; unsigned long long* keys; uchar4* image; float4* vertexConf; float4* normalRad; unsigned short* time16;
+    SplatFillArgs fill;   // (resolve only)
 };
 
 __global__ void __launch_bounds__(kB) splat_raster_kernel(const Batch<SplatArgs> B, const FrameGeom g)
@@ -480,6 +481,62 @@ __global__ void __launch_bounds__(kB) splat_raster_kernel(const Batch<SplatArgs>
     }
 }
 
+// ==================================================================================== fill-in ====
+// fill_vertex.frag / fill_normal.frag / fill_rgb.frag on texel q = (x, y) of a prediction: v, n, e are its vertex, normal and colour
+__device__ __forceinline__ void fill_in_px(float4 v, float4 n, uchar4 e, const float* __restrict__ depth, const uchar4* __restrict__ rgba, int cols,
+                                           int rows, int x, int y, int q, float cx, float cy, float inv_fx, float inv_fy, int pass_geom, int pass_rgb,
+                                           float4* __restrict__ ov, float4* __restrict__ on, uchar4* __restrict__ oi)
+{
+    const float z = depth[q];
+    const f3 p = {((float)x - cx) * z * inv_fx, ((float)y - cy) * z * inv_fy, z};
+    ov[q] = (v.z == 0 || pass_geom) ? make_float4(p.x, p.y, p.z, 1.f) : v;
+    if (n.z == 0 || pass_geom) {
+        const float zx = depth[y * cols + min(x + 1, cols - 1)], zy = depth[min(y + 1, rows - 1) * cols + x];
+        const f3 vx = {((float)(x + 1) - cx) * zx * inv_fx, ((float)y - cy) * zx * inv_fy, zx};
+        const f3 vy = {((float)x - cx) * zy * inv_fx, ((float)(y + 1) - cy) * zy * inv_fy, zy};
+        const f3 nn = normalized(cross(vx - p, vy - p));
+        on[q] = make_float4(nn.x, nn.y, nn.z, 1.f);
+    } else
+        on[q] = n;
+    oi[q] = (((int)e.x + (int)e.y + (int)e.z) == 0 || pass_rgb) ? rgba[q] : e;
+}
+__global__ void __launch_bounds__(kB) fill_in_kernel(const float4* __restrict__ pv, const float4* __restrict__ pn, const uchar4* __restrict__ pimg,
+                                                     const float* __restrict__ depth, const uchar4* __restrict__ rgba, int cols, int rows,
+                                                     float cx, float cy, float inv_fx, float inv_fy, int pass_geom, int pass_rgb,
+                                                     float4* __restrict__ ov, float4* __restrict__ on, uchar4* __restrict__ oi)
+{
+    const int q = blockIdx.x * kB + threadIdx.x;
+    if (q >= cols * rows) return;
+    const int y = q / cols, x = q - y * cols;
+    fill_in_px(pv[q], pn[q], pimg[q], depth, rgba, cols, rows, x, y, q, cx, cy, inv_fx, inv_fy, pass_geom, pass_rgb, ov, on, oi);
+}
+// is coordinate p one of the dn sample positions nearest_texel((i + .5) / dn, size) of fill_ratio_kernel along an axis?  The positions
+// are 20 texels or more apart and the i-th lies in [i size / dn, (i + 1) size / dn): only i = p dn / size and its neighbours can hit p.
+__device__ __forceinline__ bool fill_ratio_sample(int p, int dn, int size)
+{
+    const int i0 = p * dn / size;
+    bool hit = false;
+    for (int i = max(i0 - 1, 0); i <= min(i0 + 1, dn - 1); i++) hit = hit || nearest_texel(((float)i + 0.5f) / (float)dn, size) == p;
+    return hit;
+}
+
+// host twin of nearest_texel / of the sample positions: how many workgroups of kB consecutive texels hold at least one of them
+int fill_ratio_sample_blocks(int cols, int rows)
+{
+    const int dw = cols / 20, dh = rows / 20;
+    int blocks = 0, last = -1;
+    for (int j = 0; j < dh; j++)
+        for (int i = 0; i < dw; i++) {   // (row-major: the texel index only grows)
+            const auto texel = [](float u, int size) { const int t = (int)floorf(u * (float)size); return t < 0 ? 0 : (t > size - 1 ? size - 1 : t); };
+            const int b = (texel(((float)j + 0.5f) / (float)dh, rows) * cols + texel(((float)i + 0.5f) / (float)dw, cols)) / kB;
+            if (b != last) { blocks++; last = b; }
+        }
+    return blocks;
+}
+
+// The resolve of the splat pass.  A model whose arguments carry SplatFillArgs also gets, from the same registers, its fill-in maps and
+// the covered count of CoFusion::requiresFillIn (see SplatFillArgs): such a share runs without early exits, so that every thread of
+// a workgroup meets the barriers of the count.
 __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs> B, const FrameGeom g)
 {
     const VBlock vb = batch_decode(B.h);
@@ -490,56 +547,58 @@ __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs
     const int cols = g.cols, rows = g.rows;
     const cf_cam cam = g.cam;
     const int q = vb.bid * kB + threadIdx.x;
-    if (q >= cols * rows) return;
-    const unsigned long long k = keys[q];
-    keys[q] = kEmptyKey;  // leave the z-buffer cleared for the next pass (no memset launch per projection)
-    if (k == kEmptyKey) {
-        image[q] = make_uchar4(0, 0, 0, 0);
-        vertexConf[q] = normalRad[q] = make_float4(0, 0, 0, 0);
-        time16[q] = 0;
-        return;
+    const bool fill = a.fill.depth_filt != nullptr;   // (uniform)
+    bool covered = false, sample = false;
+    if (q < cols * rows) {
+        const int py = q / cols, px = q - py * cols;
+        const unsigned long long k = keys[q];
+        keys[q] = kEmptyKey;  // leave the z-buffer cleared for the next pass (no memset launch per projection)
+        uchar4 img = make_uchar4(0, 0, 0, 0);
+        float4 vc = make_float4(0, 0, 0, 0), nrad = make_float4(0, 0, 0, 0);
+        unsigned short t16 = 0;
+        if (k != kEmptyKey) {
+            const unsigned id = (unsigned)k;
+            const float4 pc = surfels[id * 3], ct = surfels[id * 3 + 1], nr = surfels[id * 3 + 2];
+            SplatSetup s;
+            splat_setup(pc, ct, nr, a.t_inv, cam, cols, rows, a.maxDepth, a.confThreshold, a.time, a.maxTime, a.timeDelta, s);
+            float z;
+            splat_fragment(s, rays, cols, px, py, a.maxDepth, z);
+            const f3 col = decode_color(ct.x);
+            img = make_uchar4((unsigned char)glsl_round(col.x * 255.0f), (unsigned char)glsl_round(col.y * 255.0f),
+                              (unsigned char)glsl_round(col.z * 255.0f), 255);
+            const float fx_ = (float)px + 0.5f, fy_ = (float)py + 0.5f;
+            vc = make_float4((fx_ - cam.cx) * z * (1.f / cam.fx), (fy_ - cam.cy) * z * (1.f / cam.fy), z, pc.w);
+            nrad = make_float4(s.n.x, s.n.y, s.n.z, s.rad);
+            t16 = (unsigned short)(unsigned)ct.z;
+        }
+        image[q] = img; vertexConf[q] = vc; normalRad[q] = nrad; time16[q] = t16;
+        if (fill) {
+            fill_in_px(vc, nrad, img, a.fill.depth_filt, reinterpret_cast<const uchar4*>(a.fill.rgba), cols, rows, px, py, q, cam.cx, cam.cy,
+                       a.fill.inv_fx, a.fill.inv_fy, a.fill.pass_geom, a.fill.pass_rgb, reinterpret_cast<float4*>(a.fill.fill_vertex),
+                       reinterpret_cast<float4*>(a.fill.fill_normal), reinterpret_cast<uchar4*>(a.fill.fill_image));
+            const int dw = cols / 20, dh = rows / 20;
+            sample = dw > 0 && dh > 0 && fill_ratio_sample(py, dh, rows) && fill_ratio_sample(px, dw, cols);
+            covered = sample && img.x > 0 && img.y > 0 && img.z > 0;
+        }
     }
-    const unsigned id = (unsigned)k;
-    const int py = q / cols, px = q - py * cols;
-    const float4 pc = surfels[id * 3], ct = surfels[id * 3 + 1], nr = surfels[id * 3 + 2];
-    SplatSetup s;
-    splat_setup(pc, ct, nr, a.t_inv, cam, cols, rows, a.maxDepth, a.confThreshold, a.time, a.maxTime, a.timeDelta, s);
-    float z;
-    splat_fragment(s, rays, cols, px, py, a.maxDepth, z);
-    const f3 col = decode_color(ct.x);
-    image[q] = make_uchar4((unsigned char)glsl_round(col.x * 255.0f), (unsigned char)glsl_round(col.y * 255.0f),
-                           (unsigned char)glsl_round(col.z * 255.0f), 255);
-    const float fx_ = (float)px + 0.5f, fy_ = (float)py + 0.5f;
-    vertexConf[q] = make_float4((fx_ - cam.cx) * z * (1.f / cam.fx), (fy_ - cam.cy) * z * (1.f / cam.fy), z, pc.w);
-    normalRad[q] = make_float4(s.n.x, s.n.y, s.n.z, s.rad);
-    time16[q] = (unsigned short)(unsigned)ct.z;
-}
-
-// ==================================================================================== fill-in ====
-// fill_vertex.frag / fill_normal.frag / fill_rgb.frag
-__global__ void __launch_bounds__(kB) fill_in_kernel(const float4* __restrict__ pv, const float4* __restrict__ pn, const uchar4* __restrict__ pimg,
-                                                     const float* __restrict__ depth, const uchar4* __restrict__ rgba, int cols, int rows,
-                                                     float cx, float cy, float inv_fx, float inv_fy, int pass_geom, int pass_rgb,
-                                                     float4* __restrict__ ov, float4* __restrict__ on, uchar4* __restrict__ oi)
-{
-    const int q = blockIdx.x * kB + threadIdx.x;
-    if (q >= cols * rows) return;
-    const int y = q / cols, x = q - y * cols;
-    const float z = depth[q];
-    const f3 p = {((float)x - cx) * z * inv_fx, ((float)y - cy) * z * inv_fy, z};
-    const float4 v = pv[q];
-    ov[q] = (v.z == 0 || pass_geom) ? make_float4(p.x, p.y, p.z, 1.f) : v;
-    const float4 n = pn[q];
-    if (n.z == 0 || pass_geom) {
-        const float zx = depth[y * cols + min(x + 1, cols - 1)], zy = depth[min(y + 1, rows - 1) * cols + x];
-        const f3 vx = {((float)(x + 1) - cx) * zx * inv_fx, ((float)y - cy) * zx * inv_fy, zx};
-        const f3 vy = {((float)x - cx) * zy * inv_fx, ((float)(y + 1) - cy) * zy * inv_fy, zy};
-        const f3 nn = normalized(cross(vx - p, vy - p));
-        on[q] = make_float4(nn.x, nn.y, nn.z, 1.f);
-    } else
-        on[q] = n;
-    const uchar4 e = pimg[q];
-    oi[q] = (((int)e.x + (int)e.y + (int)e.z) == 0 || pass_rgb) ? rgba[q] : e;
+    if (!fill) return;
+    // Only the workgroups that hold a sample position take part (the host counted them: sample_blocks), each with ONE atomic that
+    // carries its covered count in the high word and its ticket in the low one.  The adds to one address are totally ordered, so the
+    // value the last one gets back already holds every other workgroup's count: no fence, no second read.  (A ticket drawn by every
+    // workgroup of the share -- 1200 same-address atomics behind a fence each -- made this launch 70 us instead of 19.)
+    const unsigned samples = (unsigned)((cols / 20) * (rows / 20));
+    unsigned total = 0;
+    if (a.fill.sample_blocks > 0) {
+        const int n_covered = __syncthreads_count(covered ? 1 : 0);
+        if (!__syncthreads_or(sample ? 1 : 0) || threadIdx.x != 0) return;
+        const unsigned long long old = atomicAdd(a.fill.acc, ((unsigned long long)(unsigned)n_covered << 32) | 1ull);
+        if ((unsigned)old != (unsigned)a.fill.sample_blocks - 1u) return;
+        total = (unsigned)(old >> 32) + (unsigned)n_covered;
+        __hip_atomic_store(a.fill.acc, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero again for the next launch
+    } else if (vb.bid != 0 || threadIdx.x != 0)
+        return;   // (an image without sample positions: the first workgroup publishes (0, 0))
+    a.fill.out2[0] = total; a.fill.out2[1] = samples;
+    if (a.fill.out2_host) { a.fill.out2_host[0] = total; a.fill.out2_host[1] = samples; }
 }
 
 // CoFusion::requiresFillIn (CoFusion.cpp:547-565): one workgroup counts the 20x down-sampled image
@@ -1071,7 +1130,7 @@ void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, in
             const SplatPassArgs& h = items[base + k];
             B.m[k] = SplatArgs{reinterpret_cast<const float4*>(h.surfels), h.count, mat4_from(h.t_inv), h.maxDepth, h.confThreshold, h.time, h.maxTime,
                                h.timeDelta, reinterpret_cast<const float4*>(h.rays), h.keys, reinterpret_cast<uchar4*>(h.image),
-                               reinterpret_cast<float4*>(h.vertexConf), reinterpret_cast<float4*>(h.normalRad), h.time16};
+                               reinterpret_cast<float4*>(h.vertexConf), reinterpret_cast<float4*>(h.normalRad), h.time16, h.fill};
             blocks[k] = h.count_bound > 0 ? gridFor(4ll * h.count_bound) : 0;
             any += blocks[k];
         }

@@ -130,20 +130,27 @@ __device__ __forceinline__ int gauss_w(int k) { return k == 2 ? 6 : ((k == 0 || 
 // END, int count).  The reference cudaMalloc/Free's the weights per call (:523-531).  Fully unrolled 5x5 walks (25
 // independent loads, row-major summation order as the reference's loops): literal weights in the interior, weights
 // computed from the window end (ty - cy - 1, tx - cx - 1) and predicated taps on the border.
-__device__ __forceinline__ void pyrdown_f32_px(const float* __restrict__ src, int scols, int srows, float* __restrict__ dst, int i)
+// The taps of both walks come through a loader `ld(row, col, inside)` of the source level: the image in memory (GlobalTaps) or a
+// workgroup's footprint of it in LDS (TileTaps, rgbd_tile_body); a tap that is not `inside` is never used.
+template <class T> struct GlobalTaps {
+    const T* __restrict__ src; int scols;
+    __device__ __forceinline__ T operator()(int cy, int cx, bool in) const { return src[in ? cy * scols + cx : 0]; }
+};
+template <class T> struct TileTaps {   // (oy, ox): the image position of t[0]
+    const T* t; int pitch, oy, ox;
+    __device__ __forceinline__ T operator()(int cy, int cx, bool in) const { return in ? t[(cy - oy) * pitch + (cx - ox)] : (T)0; }
+};
+template <class Ld> __device__ __forceinline__ float pyrdown_f32_at(Ld ld, int scols, int srows, int x, int y)
 {
-    const int dcols = scols / 2;
-    const int y = i / dcols, x = i - y * dcols;
     float sum = 0; int count = 0;
     if (2 * x - 2 >= 0 && 2 * y - 2 >= 0 && 2 * x + 3 <= scols - 1 && 2 * y + 3 <= srows - 1) {
         // interior: full window, literal weights (index 4-r, 4-c == r, c by symmetry)
         constexpr int g[5] = {1, 4, 6, 4, 1};
-        const float* __restrict__ p0 = src + (2 * y - 2) * scols + (2 * x - 2);
 #pragma unroll
         for (int r = 0; r < 5; r++)
 #pragma unroll
             for (int c = 0; c < 5; c++) {
-                const float s = p0[r * scols + c];
+                const float s = ld(2 * y - 2 + r, 2 * x - 2 + c, true);
                 if (!is_nan(s)) { sum += s * (float)(g[r] * g[c]); count += g[r] * g[c]; }
             }
     } else {
@@ -156,7 +163,7 @@ __device__ __forceinline__ void pyrdown_f32_px(const float* __restrict__ src, in
             for (int c = 0; c < 5; c++) {
                 const int cx = 2 * x - 2 + c;
                 const bool in = cy >= 0 && cy < ty && cx >= 0 && cx < tx;
-                const float s = src[in ? cy * scols + cx : 0];
+                const float s = ld(cy, cx, in);
                 if (in && !is_nan(s)) {
                     const int wi = gauss_w(ty - cy - 1) * gauss_w(tx - cx - 1);
                     sum += s * (float)wi;
@@ -165,7 +172,13 @@ __device__ __forceinline__ void pyrdown_f32_px(const float* __restrict__ src, in
             }
         }
     }
-    dst[i] = sum / (float)count;
+    return sum / (float)count;
+}
+__device__ __forceinline__ void pyrdown_f32_px(const float* __restrict__ src, int scols, int srows, float* __restrict__ dst, int i)
+{
+    const int dcols = scols / 2;
+    const int y = i / dcols, x = i - y * dcols;
+    dst[i] = pyrdown_f32_at(GlobalTaps<float>{src, scols}, scols, srows, x, y);
 }
 __global__ void __launch_bounds__(kBlock) pyrdown_f32_kernel(const float* __restrict__ src, int scols, int srows,
                                                              float* __restrict__ dst)
@@ -175,19 +188,16 @@ __global__ void __launch_bounds__(kBlock) pyrdown_f32_kernel(const float* __rest
 }
 
 // pyrDownKernelIntensityGauss, cudafuncs.cu:534-564
-__device__ __forceinline__ uint8_t pyrdown_u8_val(const uint8_t* __restrict__ src, int scols, int srows, int i)
+template <class Ld> __device__ __forceinline__ uint8_t pyrdown_u8_at(Ld ld, int scols, int srows, int x, int y)
 {
-    const int dcols = scols / 2;
-    const int y = i / dcols, x = i - y * dcols;
     float sum = 0; int count = 0;
     if (2 * x - 2 >= 0 && 2 * y - 2 >= 0 && 2 * x + 3 <= scols - 1 && 2 * y + 3 <= srows - 1) {
         constexpr int g[5] = {1, 4, 6, 4, 1};
-        const uint8_t* __restrict__ p0 = src + (2 * y - 2) * scols + (2 * x - 2);
 #pragma unroll
         for (int r = 0; r < 5; r++)
 #pragma unroll
             for (int c = 0; c < 5; c++) {
-                const uint8_t s = p0[r * scols + c];
+                const uint8_t s = ld(2 * y - 2 + r, 2 * x - 2 + c, true);
                 if (s > 0) { sum += (float)s * (float)(g[r] * g[c]); count += g[r] * g[c]; }
             }
     } else {
@@ -199,7 +209,7 @@ __device__ __forceinline__ uint8_t pyrdown_u8_val(const uint8_t* __restrict__ sr
             for (int c = 0; c < 5; c++) {
                 const int cx = 2 * x - 2 + c;
                 const bool in = cy >= 0 && cy < ty && cx >= 0 && cx < tx;
-                const uint8_t s = src[in ? cy * scols + cx : 0];
+                const uint8_t s = ld(cy, cx, in);
                 if (in && s > 0) {
                     const int wi = gauss_w(ty - cy - 1) * gauss_w(tx - cx - 1);
                     sum += (float)s * (float)wi;
@@ -210,6 +220,12 @@ __device__ __forceinline__ uint8_t pyrdown_u8_val(const uint8_t* __restrict__ sr
     }
     const float q = sum / (float)count;
     return is_nan(q) ? (uint8_t)0 : (uint8_t)(int)q;
+}
+__device__ __forceinline__ uint8_t pyrdown_u8_val(const uint8_t* __restrict__ src, int scols, int srows, int i)
+{
+    const int dcols = scols / 2;
+    const int y = i / dcols, x = i - y * dcols;
+    return pyrdown_u8_at(GlobalTaps<uint8_t>{src, scols}, scols, srows, x, y);
 }
 __device__ __forceinline__ void pyrdown_u8_px(const uint8_t* __restrict__ src, int scols, int srows, uint8_t* __restrict__ dst, int i)
 {
@@ -233,6 +249,11 @@ __global__ void __launch_bounds__(kBlock) pyrdown_u8_kernel(const uint8_t* __res
 
 // RGBDOdometry::populateRGBDData (RGBDOdometry.cpp:177-194) issues a depth chain and an intensity chain that do not
 // depend on each other: each pyramid step of both shares one launch (workgroups [0, nd) depth, the rest intensity).
+__device__ __forceinline__ float rgbd_base_depth(float4 v, float cutoff) { return (v.z > cutoff || v.z <= 0) ? qnan() : v.z; }   // verticesToDepthKernel, cudafuncs.cu:602-613
+__device__ __forceinline__ uint8_t rgbd_base_intensity(uchar4 s)   // bgr2IntensityKernel, cudafuncs.cu:626-639
+{
+    return (uint8_t)(int)((float)s.x * 0.114f + (float)s.y * 0.299f + (float)s.z * 0.587f);
+}
 __device__ __forceinline__ void rgbd_base_body(const RgbdBatch& b, int N, float cutoff, int bx, int by)
 {
     const RgbdChain& c = b.c[by];  // one (depth, intensity) chain per grid row: models x {prediction, frame}
@@ -240,17 +261,72 @@ __device__ __forceinline__ void rgbd_base_body(const RgbdBatch& b, int N, float 
     const float4* __restrict__ v4 = reinterpret_cast<const float4*>(alt ? c.alt_v4 : c.v4);
     const uchar4* __restrict__ rgba = reinterpret_cast<const uchar4*>(alt ? c.alt_rgba : c.rgba);
     const int nb = (N + kBlock - 1) / kBlock;
-    if (bx < nb) {  // verticesToDepthKernel, cudafuncs.cu:602-613
+    if (bx < nb) {
         const int i = bx * kBlock + threadIdx.x;
         if (i >= N || !c.depth[0]) return;  // (a chain without a depth pyramid: the intensity half only)
-        const float z = v4[i].z;
-        c.depth[0][i] = (z > cutoff || z <= 0) ? qnan() : z;
-    } else {                     // bgr2IntensityKernel, cudafuncs.cu:626-639
+        c.depth[0][i] = rgbd_base_depth(v4[i], cutoff);
+    } else {
         const int i = (bx - nb) * kBlock + threadIdx.x;
         if (i >= N) return;
-        const uchar4 s = rgba[i];
-        rgbd_store_image(b, by, 0, i, (uint8_t)(int)((float)s.x * 0.114f + (float)s.y * 0.299f + (float)s.z * 0.587f));
+        rgbd_store_image(b, by, 0, i, rgbd_base_intensity(rgba[i]));
     }
+}
+// All three levels of one pyramid of a chain for a rectangle of level-2 pixels (kDepth: the depth pyramid, else the intensity pyramid).
+// The level below is a pure per-pixel function of the level above, so a workgroup evaluates the base level for the level-0 footprint
+// its rectangle needs into LDS (a 5x5 window at stride 2, twice: 4 T + 9 pixels a side), level 1 for the footprint level 2 needs from
+// there, and level 2 from that: the halo is computed again by the neighbouring workgroups instead of being read back from memory by a
+// later launch.  Every pixel of every level is STORED by the one workgroup whose rectangle covers it (cols % 4 == 0 && rows % 4 == 0,
+// as cf_create admits: the levels halve exactly); borders are those of the image (pyrdown_*_at get the image's size), and footprint
+// pixels outside the image are neither evaluated nor read.
+constexpr int kT2W = 16, kT2H = 8;                            // a workgroup's rectangle of level-2 pixels
+constexpr int kF1W = 2 * kT2W + 3, kF1H = 2 * kT2H + 3;       // its level-1 footprint: 35 x 19
+constexpr int kF0W = 2 * kF1W + 3, kF0H = 2 * kF1H + 3;       // ... and level-0 footprint: 73 x 41
+constexpr int kTileLds = kF0W * kF0H + kF1W * kF1H;           // elements (f32: 14.3 KB; u8: 3.6 KB of the same array)
+static inline int rgbd_tiles(int W, int H) { return ((W / 4 + kT2W - 1) / kT2W) * ((H / 4 + kT2H - 1) / kT2H); }
+template <bool kDepth> __device__ __forceinline__ void rgbd_tile_body(const RgbdBatch& b, int W, int H, float cutoff, int tile, int by, float* lds)
+{
+    using T = typename std::conditional<kDepth, float, uint8_t>::type;
+    const RgbdChain& c = b.c[by];
+    if (kDepth && !c.depth[0]) return;  // (a chain without a depth pyramid; uniform, in front of the barriers)
+    const bool alt = c.sel && (float)c.sel[0] / (float)c.sel[1] < c.sel_ratio;
+    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(alt ? c.alt_v4 : c.v4);
+    const uchar4* __restrict__ rgba = reinterpret_cast<const uchar4*>(alt ? c.alt_rgba : c.rgba);
+    const int W1 = W / 2, H1 = H / 2, W2 = W1 / 2, H2 = H1 / 2;
+    const int tiles_x = (W2 + kT2W - 1) / kT2W;
+    const int tyi = tile / tiles_x, x2 = (tile - tyi * tiles_x) * kT2W, y2 = tyi * kT2H;
+    T* const t0 = reinterpret_cast<T*>(lds);
+    T* const t1 = t0 + kF0W * kF0H;
+    const int ox0 = 4 * x2 - 6, oy0 = 4 * y2 - 6, ox1 = 2 * x2 - 2, oy1 = 2 * y2 - 2;
+    auto store = [&](int level, int i, T v) {
+        if constexpr (kDepth) c.depth[level][i] = v;
+        else rgbd_store_image(b, by, level, i, v);
+    };
+    for (int k = threadIdx.x; k < kF0W * kF0H; k += kBlock) {
+        const int fy = k / kF0W, fx = k - fy * kF0W, gx = ox0 + fx, gy = oy0 + fy;
+        if (gx < 0 || gy < 0 || gx >= W || gy >= H) continue;
+        const int i = gy * W + gx;
+        T v;
+        if constexpr (kDepth) v = rgbd_base_depth(v4[i], cutoff);
+        else v = rgbd_base_intensity(rgba[i]);
+        t0[k] = v;
+        if (fx >= 6 && fx < 6 + 4 * kT2W && fy >= 6 && fy < 6 + 4 * kT2H) store(0, i, v);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kF1W * kF1H; k += kBlock) {
+        const int fy = k / kF1W, fx = k - fy * kF1W, gx = ox1 + fx, gy = oy1 + fy;
+        if (gx < 0 || gy < 0 || gx >= W1 || gy >= H1) continue;
+        T v;
+        if constexpr (kDepth) v = pyrdown_f32_at(TileTaps<float>{t0, kF0W, oy0, ox0}, W, H, gx, gy);
+        else v = pyrdown_u8_at(TileTaps<uint8_t>{t0, kF0W, oy0, ox0}, W, H, gx, gy);
+        t1[k] = v;
+        if (fx >= 2 && fx < 2 + 2 * kT2W && fy >= 2 && fy < 2 + 2 * kT2H) store(1, gy * W1 + gx, v);
+    }
+    __syncthreads();
+    static_assert(kT2W * kT2H <= kBlock, "one level-2 pixel per thread");
+    const int k = threadIdx.x, fy = k / kT2W, gx = x2 + (k - fy * kT2W), gy = y2 + fy;
+    if (fy >= kT2H || gx >= W2 || gy >= H2) return;
+    if constexpr (kDepth) store(2, gy * W2 + gx, pyrdown_f32_at(TileTaps<float>{t1, kF1W, oy1, ox1}, W1, H1, gx, gy));
+    else store(2, gy * W2 + gx, pyrdown_u8_at(TileTaps<uint8_t>{t1, kF1W, oy1, ox1}, W1, H1, gx, gy));
 }
 __global__ void __launch_bounds__(kBlock) rgbd_base_kernel(const RgbdBatch b, int N, float cutoff) { rgbd_base_body(b, N, cutoff, (int)blockIdx.x, (int)blockIdx.y); }
 __global__ void __launch_bounds__(kBlock) rgbd_pyrdown_kernel(const RgbdBatch b, int level, int scols, int srows)
@@ -516,14 +592,22 @@ __device__ __forceinline__ void model_maps_tiled_body(const ModelMapsBatch& b, i
     }
 }
 __global__ void __launch_bounds__(256) model_maps_tiled_kernel(const ModelMapsBatch b) { model_maps_tiled_body(b, (int)blockIdx.x, (int)blockIdx.y); }
-// {model maps || base level of the depth / intensity pyramids} of a batch of trackers in ONE launch: the two passes read the same
-// predictions and write different buffers; alone each is a 10-25 us kernel in the chain in front of the Gauss-Newton loop.  A
-// one-dimensional grid: [model-map workgroups of all models | pyramid-base workgroups of all chains].
-__global__ void __launch_bounds__(256) prep_fused_kernel(const ModelMapsBatch mb, int mm_bx, int mm_total, const RgbdBatch rb, int N, float cutoff, int rb_bx)
+// {model maps || the depth / intensity pyramids, all levels} of a batch of trackers in ONE launch: the two passes read the same
+// predictions and write different buffers; alone each is a 10-25 us kernel in the chain in front of the Gauss-Newton loop, and the
+// two pyramid steps were two more dependent launches behind it.  A one-dimensional grid: [per chain: `tiles` depth-pyramid
+// workgroups, `tiles` intensity-pyramid workgroups (rgbd_tile_body) | model-map workgroups of all models].  The pyramid workgroups
+// come FIRST: each is a chain of three dependent stages, and dispatched behind the model-map workgroups they were the launch's tail
+// (67.9 us; 47-53 us in this order; the same launch with the base level only, as it was: 42.4 us -- DESIGN-NOTES R8).
+__global__ void __launch_bounds__(256) prep_fused_kernel(const ModelMapsBatch mb, int mm_bx, int mm_total, const RgbdBatch rb, int W, int H, float cutoff, int tiles)
 {
-    const int b = blockIdx.x;
-    if (b < mm_total) { const int by = b / mm_bx; model_maps_tiled_body(mb, b - by * mm_bx, by); }
-    else { const int r = b - mm_total, by = r / rb_bx; rgbd_base_body(rb, N, cutoff, r - by * rb_bx, by); }
+    __shared__ float tile_lds[kTileLds];
+    const int n_pyr = (int)gridDim.x - mm_total, b = blockIdx.x;
+    if (b >= n_pyr) { const int m = b - n_pyr, by = m / mm_bx; model_maps_tiled_body(mb, m - by * mm_bx, by); }
+    else {
+        const int by = b / (2 * tiles), t = b - by * 2 * tiles;
+        if (t < tiles) rgbd_tile_body<true>(rb, W, H, cutoff, t, by, tile_lds);
+        else rgbd_tile_body<false>(rb, W, H, cutoff, t - tiles, by, tile_lds);
+    }
 }
 
 // ------------------------------------------------------------------ launchers ----
@@ -557,10 +641,8 @@ void launch_model_maps(hipStream_t s, const ModelMapsBatch& b, int n)
 void launch_model_maps_and_pyramids(hipStream_t s, const ModelMapsBatch& mb, int n, const RgbdBatch& rb, int n_chains, int W, int H, float cutoff)
 {
     static_assert(kBlock == 256, "the fused launch runs both bodies with 256 threads");
-    const int mm_bx = ((mb.m[0].cols >> 4) * (mb.m[0].rows >> 2) + 3) / 4, rb_bx = 2 * grid_for(W * H);
-    prep_fused_kernel<<<mm_bx * n + rb_bx * n_chains, 256, 0, s>>>(mb, mm_bx, mm_bx * n, rb, W * H, cutoff, rb_bx);
-    for (int i = 0; i + 1 < 3; i++)
-        rgbd_pyrdown_kernel<<<dim3(2 * grid_for(((W >> i) / 2) * ((H >> i) / 2)), n_chains), kBlock, 0, s>>>(rb, i, W >> i, H >> i);
+    const int mm_bx = ((mb.m[0].cols >> 4) * (mb.m[0].rows >> 2) + 3) / 4, tiles = rgbd_tiles(W, H);   // (cols % 16 == 0 && rows % 4 == 0: launch_model_maps)
+    prep_fused_kernel<<<2 * tiles * n_chains + mm_bx * n, 256, 0, s>>>(mb, mm_bx, mm_bx * n, rb, W, H, cutoff, tiles);
 }
 void launch_rgbd_pyramids(hipStream_t s, const RgbdBatch& b, int n_chains, int W, int H, float cutoff)
 {

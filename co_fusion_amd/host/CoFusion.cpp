@@ -811,13 +811,16 @@ void CoFusion::frameFuseCollect(std::vector<cf_model_pass>& items)
         it.do_fuse = (st.fuseNow && !m->predictOnlyThisFrame) ? 1 : 0; it.time = tick;   // (a model reactivated in this frame: prediction only)
         it.fuse_max_depth = maxDepthProcessed < m->getMaxDepth() ? maxDepthProcessed : m->getMaxDepth();  // std::min(depthCutoff, maxDepth), Model.cpp:443
         it.weighting = m->computeFusionWeight(st.weightMultiplier); it.mask_id = (int)m->getID(); it.conf_threshold = m->getConfidenceThreshold();
+        // prefetchFillRatio + performFillIn ride in the chain's last launch (requiresFillIn() of the next frame asks about THIS prediction)
+        if (m->fillsInHere()) { it.fill_in = 1; it.passthrough_geom = lost ? 1 : 0; it.passthrough_rgb = (lost || cfg.frameToFrameRGB) ? 1 : 0; }
         items.push_back(it);
     }
 }
 void CoFusion::frameFuseFinish()
 {
     for (auto& m : models) {
-        m->prefetchFillRatio();  // requiresFillIn() of the next frame asks about THIS prediction
+        if (m->fillsInHere()) continue;   // (served by the chain: frameFuseCollect)
+        m->prefetchFillRatio();
         m->performFillIn(curRgba, depthFiltered_dev, cfg.frameToFrameRGB, lost);
     }
 }

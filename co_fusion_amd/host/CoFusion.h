@@ -132,6 +132,7 @@ class Model {
     const uint32_t* fillRatioDevice() const;
     void prefetchFillRatio();
     bool allowsFillIn() const { return fillIn; }
+    bool fillsInHere() const { return fillIn && owned; }   // does performFillIn / prefetchFillRatio launch anything for this model?
     std::vector<float> downloadMap() const;  // count x 12 floats
 
     float getConfidenceThreshold() const { return confidenceThreshold; }

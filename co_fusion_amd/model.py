@@ -16,7 +16,8 @@ class ModelPass(C.Structure):
     """cf_model_pass (include/cofusion_hip.h)"""
     _fields_ = [("model", C.c_void_p), ("pose", C.POINTER(C.c_float)), ("rgba", C.c_void_p), ("mask", C.c_void_p), ("depth_raw", C.c_void_p),
                 ("depth_filtered", C.c_void_p), ("do_fuse", C.c_int), ("time", C.c_int), ("fuse_max_depth", C.c_float), ("weighting", C.c_float),
-                ("mask_id", C.c_int), ("conf_threshold", C.c_float)]
+                ("mask_id", C.c_int), ("conf_threshold", C.c_float), ("fill_in", C.c_int), ("passthrough_geom", C.c_int),
+                ("passthrough_rgb", C.c_int)]
 
 
 class ModelPreindex(C.Structure):
@@ -26,7 +27,8 @@ class ModelPreindex(C.Structure):
 
 def frame_passes(ctx: Context, items, depth_cutoff, outlier_coeff, time_delta=None):
     """cf_models_frame_passes.  items: dicts with model (a Model), pose, rgba, depth_filt, time, conf_threshold and, for do_fuse (default 1),
-    mask, depth_raw, fuse_max_depth, weighting, mask_id; the images are device tensors"""
+    mask, depth_raw, fuse_max_depth, weighting, mask_id; the images are device tensors.  fill_in (default 0) with passthrough_geom /
+    passthrough_rgb: the fill-in maps and the fill ratio of the model out of the same chain"""
     n = len(items)
     arr = (ModelPass * n)()
     keep = []
@@ -43,6 +45,7 @@ def frame_passes(ctx: Context, items, depth_cutoff, outlier_coeff, time_delta=No
         a.weighting = float(it.get("weighting", 1.0))
         a.mask_id = int(it.get("mask_id", 0))
         a.conf_threshold = float(it["conf_threshold"])
+        a.fill_in, a.passthrough_geom, a.passthrough_rgb = int(it.get("fill_in", 0)), int(it.get("passthrough_geom", 0)), int(it.get("passthrough_rgb", 0))
     ctx._check(ctx.lib.cf_models_frame_passes(ctx.h, arr, n, C.c_float(depth_cutoff), C.c_float(outlier_coeff),
                                               int(TIME_DELTA if time_delta is None else time_delta)))
 
@@ -121,6 +124,19 @@ class Model:
 
     def perform_fill_in(self, rgba, depth_filt, pass_geom=False, pass_rgb=False):
         self.ctx._check(self.ctx.lib.cf_model_perform_fill_in(self.h, _p(rgba), _p(depth_filt), int(pass_geom), int(pass_rgb)))
+
+    def prefetch_fill_ratio(self):
+        self.ctx._check(self.ctx.lib.cf_model_prefetch_fill_ratio(self.h))
+
+    def fill_counts_device(self):
+        """the (covered, total) counts of the pending fill-ratio prefetch as they stand in device memory, or None without one"""
+        ptr = C.c_void_p()
+        self.ctx._check(self.ctx.lib.cf_model_fill_ratio_device(self.h, C.byref(ptr)))
+        if not ptr.value:
+            return None
+        host = np.empty(2, np.uint32)
+        self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, host.ctypes.data_as(C.c_void_p), ptr, C.c_uint64(8)))
+        return host
 
     def requires_fill_in(self, ratio=0.75):
         out = C.c_int()

@@ -414,6 +414,11 @@ typedef struct {
     float weighting;                         /* Model::computeFusionWeight */
     int mask_id;
     float conf_threshold;
+    /* fill_in != 0: the chain also does what cf_model_prefetch_fill_ratio + cf_model_perform_fill_in(rgba, depth_filtered,
+     * passthrough_geom, passthrough_rgb) behind it would -- inside the last launch of the prediction, from the registers that hold the
+     * texel, instead of two more launches that read it back.  Identical fill maps and counts; cf_model_requires_fill_in and
+     * cf_model_fill_ratio_device answer as after the prefetch.  All zero: the chain as before. */
+    int fill_in, passthrough_geom, passthrough_rgb;
 } cf_model_pass;
 int cf_models_frame_passes(cf_ctx *ctx, const cf_model_pass *items, int n, float depth_cutoff, float outlier_coeff, int time_delta);
 /* The first index pass of that chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) for models that were tracked this
