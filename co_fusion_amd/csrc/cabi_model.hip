@@ -65,6 +65,43 @@ struct cf_model {
     void drop_preindex() { preindex_od = nullptr; preindex_time = -1; }             // every entry that rewrites the surfels or the index maps calls it
     float* rays = nullptr;  // per-pixel view rays of the splat fragment stage, float4 [H*W]
     float inv_fx = 0, inv_fy = 0;
+    // EXTENTS (surfel.hip) of the index maps: a ring of three pixel rectangles in device memory, the number of the next batched index pass
+    // modulo 3, and "the maps may hold anything outside the ring's rectangles": true from creation, after every writer other than a
+    // culled batched pass, and after a batched chain that did not get to its end
+    unsigned* d_ext = nullptr;        // [3][4]
+    int ext_k = 0;
+    bool ext_unknown = true;
+    void extents_unknown() { ext_unknown = true; }
+};
+// The ring slot of the next batched index pass of `m`, for IndexPassArgs (ext, ext_slot).  A pass that starts from
+// an unknown state handles every texel and finds the whole ring zeroed first (a chain that stopped half-way may have left a slot extended).
+// `on` false: the pass runs today's launch, and the set's state is unknown afterwards.  So does the pass of a model with more surfels (`nb`,
+// the bound of the launch) than half the image has texels: such a map -- the background -- covers the screen, its resolve has nothing
+// to skip, and the rectangle would cost its rasteriser a reduction in every one of its thousands of waves (measured: +25 us per frame
+// over the rasterisers of objects4 with the background's 275 000 surfels taking part, against 10 us gained in the resolves).
+static int next_extent(cf_model* m, bool on, uint32_t nb, hipStream_t s, unsigned** ext, int* ext_slot)
+{
+    *ext = nullptr; *ext_slot = 0;
+    if (2ull * nb >= (unsigned long long)m->ctx->cfg.width * m->ctx->cfg.height) on = false;
+    if (!on) { m->ext_unknown = true; return CF_OK; }
+    const bool full = m->ext_unknown;
+    if (full) HIPCHK(m->ctx, hipMemsetAsync(m->d_ext, 0, 12 * sizeof(unsigned), s));
+    *ext = m->d_ext; *ext_slot = m->ext_k | (full ? 4 : 0);
+    m->ext_k = (m->ext_k + 1) % 3;
+    m->ext_unknown = false;   // (known once this pass has run; the chain's guard puts it back if the chain does not get to its end)
+    return CF_OK;
+}
+// extent culling of the batched passes of this context: the switch (cf_set_extent_culling; on), not under a collective (the sharded passes
+// of model-parallel runs write the maps through the per-model entry points), not with CF_NO_EXTENT_CULL in the environment (diagnostic)
+static bool extent_culling_on(const cf_ctx* ctx)
+{
+    static const bool env_on = getenv("CF_NO_EXTENT_CULL") == nullptr;
+    return env_on && ctx->extent_cull && !ctx->collective && !ctx->rccl;
+}
+// a batched chain that returns before its end leaves the extents of all its models unknown
+struct ExtentGuard {
+    std::vector<cf_model*> models; bool done = false;
+    ~ExtentGuard() { if (!done) for (cf_model* m : models) if (m) m->extents_unknown(); }
 };
 
 using cf::inv44f;   // (cf_kernels.h: shared with the device)
@@ -124,6 +161,7 @@ int cf_model_create(cf_ctx* ctx, int max_surfels, cf_model** out)
     if (int r = dmalloc(ctx, &m->tcy, (size_t)H)) return r;
     if (int r = dmalloc(ctx, &m->rays, N * 4)) return r;
     if (int r = dmalloc(ctx, &m->t_inv_dev, 16)) return r;
+    if (int r = dmalloc(ctx, &m->d_ext, 12)) return r;
     launch_splat_rays(ctx->cur(), ctx_cam(ctx), W, H, m->rays);
     HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&m->h_counts), sizeof(unsigned) * 4, hipHostMallocCoherent));  // kernels store the counts here
     HIPCHK(ctx, hipEventCreateWithFlags(&m->count_event, hipEventDisableTiming));
@@ -146,7 +184,7 @@ void cf_model_destroy(cf_model* m)
     void* ptrs[] = {m->buf[0], m->buf[1], m->staged, m->flags, m->block_sums, m->d_count, m->d_nfresh, m->d_tmp2, m->records,
                     m->fresh, m->new_flags, m->owner, m->fb_rec, m->fb_raw, m->fb_filt, m->keys, m->index, m->vertConf,
                     m->colorTime, m->normRad, m->splat_image, m->splat_vertex, m->splat_normal, m->splat_time, m->fill_vertex,
-                    m->fill_normal, m->fill_image, m->tcx, m->tcy, m->rays, m->t_inv_dev, m->clean_rec};
+                    m->fill_normal, m->fill_image, m->tcx, m->tcy, m->rays, m->t_inv_dev, m->clean_rec, m->d_ext};
     for (void* p : ptrs) (void)hipFree(p);
     (void)hipHostFree(m->h_counts);
     if (m->count_event) (void)hipEventDestroy(m->count_event);
@@ -206,6 +244,7 @@ int cf_model_initialise(cf_model* m, const uint8_t* rgba, const float* depth_raw
 {
     if (!m || !rgba || !depth_raw || !depth_filt) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();
     cf_ctx* ctx = m->ctx; hipStream_t s = ctx->cur();
     const int W = ctx->cfg.width, H = ctx->cfg.height; const long long N = (long long)W * H;
     if ((uint32_t)N > m->max_surfels) return CF_ENOMEM;
@@ -230,6 +269,7 @@ int cf_model_predict_indices(cf_model* m, const float pose[16], int time, float 
 {
     if (!m || !pose) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();   // (an unculled pass: the index maps' footprint is not in the ring)
     cf_ctx* ctx = m->ctx;
     float t_inv[16];
     inv44f(pose, t_inv);
@@ -250,6 +290,7 @@ int cf_model_index_keys(cf_model* m, const float pose[16], int time, float maxDe
 {
     if (!m || !pose || !keys_dev || surfel_begin > surfel_end) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();   // (keys_dev may be the model's own z-keys: cf_model_predict_indices_sharded)
     cf_ctx* ctx = m->ctx;
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     float t_inv[16];
@@ -266,6 +307,7 @@ int cf_model_index_resolve(cf_model* m, const float pose[16], uint64_t* keys_dev
 {
     if (!m || !pose || !keys_dev) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();
     cf_ctx* ctx = m->ctx;
     float t_inv[16];
     inv44f(pose, t_inv);
@@ -366,6 +408,7 @@ int cf_model_fuse(cf_model* m, const float pose[16], int time, const uint8_t* rg
 {
     if (!m || !pose || !rgba || !mask || !depth_raw || !depth_filt) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();
     cf_ctx* ctx = m->ctx; hipStream_t s = ctx->cur();
     const int W = ctx->cfg.width, H = ctx->cfg.height; const long long N = (long long)W * H;
     SurfelFuseArgs a;
@@ -396,6 +439,7 @@ int cf_model_clean(cf_model* m, const float pose[16], int time, float confThresh
 {
     if (!m || !pose || !depth_filt || !mask) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();
     cf_ctx* ctx = m->ctx; hipStream_t s = ctx->cur();
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     uint32_t nb = 0;
@@ -425,9 +469,13 @@ int cf_models_preindex(cf_ctx* ctx, const cf_model_preindex* items, int n, float
     hipStream_t s = ctx->cur();
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     std::vector<IndexPassArgs> a((size_t)n);
+    for (int k = 0; k < n; k++)
+        if (!items[k].model || !items[k].odom || items[k].model->ctx != ctx || items[k].odom->ctx != ctx) return CF_EINVAL;
+    ExtentGuard guard;
+    for (int k = 0; k < n; k++) guard.models.push_back(items[k].model);
+    const bool cull = extent_culling_on(ctx);
     for (int k = 0; k < n; k++) {
         cf_model* m = items[k].model; const cf_odom* od = items[k].odom;
-        if (!m || !od || m->ctx != ctx || od->ctx != ctx) return CF_EINVAL;
         uint32_t nb = 0;
         if (int r = count_bound(m, &nb)) return r;
         const float* pinv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(od->d_state) + offsetof(cf::OdomDev, pose_inv));
@@ -435,6 +483,7 @@ int cf_models_preindex(cf_ctx* ctx, const cf_model_preindex* items, int n, float
         p.surfels = m->buf[m->target]; p.count = m->d_count; p.id_begin = 0; p.id_end = nb; p.maxDepth = depth_cutoff; p.time = items[k].time;
         p.timeDelta = time_delta; p.keys = m->keys; p.index = m->index; p.vertConf = m->vertConf; p.colorTime = m->colorTime; p.normRad = m->normRad;
         p.t_inv_dev = pinv;   // (the inverse of the tracked pose, left in the tracker's state by the last solve of its schedule)
+        if (int r = next_extent(m, cull, nb, s, &p.ext, &p.ext_slot)) return r;
     }
     launch_index_keys_batch(s, a.data(), n, ctx_cam(ctx), W, H);
     launch_index_resolve_batch(s, a.data(), n, ctx_cam(ctx), W, H);
@@ -443,6 +492,7 @@ int cf_models_preindex(cf_ctx* ctx, const cf_model_preindex* items, int n, float
         cf_model* m = items[k].model;
         m->preindex_od = items[k].odom; m->preindex_time = items[k].time; m->preindex_cutoff = depth_cutoff; m->preindex_delta = time_delta; m->preindex_nb = a[k].id_end;
     }
+    guard.done = true;
     return CF_OK;
 }
 // is the index map of `m` already the one the first index pass of this chain would produce?
@@ -484,6 +534,9 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         }
     }
     for (int k = 0; k < n; k++) { uint32_t nb = 0; if (int r = count_bound(items[k].model, &nb)) return r; }
+    ExtentGuard guard;   // (from here on a return that is not the last one leaves the models' extents unknown)
+    for (int k = 0; k < n; k++) guard.models.push_back(items[k].model);
+    const bool cull = extent_culling_on(ctx);
     // profiling (cf_profile_enable N): an event pair around every N-th chain + its algorithmic bytes
     int surf_ev = -1;
     if (ctx->prof.enabled > 0 && (ctx->surf_calls_seen++ % (unsigned)ctx->prof.enabled) == 0 && ctx->surf_used + 2 <= cf_ctx::kSurfEvents) {
@@ -508,6 +561,7 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
             // the pass in front of the clean stage also packs what that stage reads per texel -- with this frame's filtered depth -- into
             // one 32-byte record (clean_kernel stages a 4x4 neighbourhood per surfel: one array and 16-byte pieces instead of three arrays)
             if (feeds_clean && clean_rec_on) { p.clean_rec = m->clean_rec; p.clean_depth = it.depth_filtered; }
+            if (int r = next_extent(m, cull, nb, s, &p.ext, &p.ext_slot)) return r;   // (every index pass of the chain is enqueued once its arguments exist)
         }
         return CF_OK;
     };
@@ -623,6 +677,7 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         for (int k : fusing) items[k].model->count_wait = ctx->batch_event;
     }
     for (int k = 0; k < n; k++) items[k].model->drop_preindex();
+    guard.done = true;
     return CF_OK;
 }
 
@@ -644,6 +699,7 @@ int cf_model_upload_map(cf_model* m, const float* host_surfels, uint32_t count)
 {
     if (!m || (!host_surfels && count) || count > m->max_surfels) return CF_EINVAL;
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
+    m->extents_unknown();
     cf_ctx* ctx = m->ctx;
     if (count) HIPCHK(ctx, hipMemcpyAsync(m->buf[m->target], host_surfels, (size_t)count * 48, hipMemcpyHostToDevice, ctx->cur()));
     launch_set_count(ctx->cur(), m->d_count, count);
@@ -655,7 +711,7 @@ int cf_model_upload_map(cf_model* m, const float* host_surfels, uint32_t count)
 // which: 0 index(u32) 1 vertConf 2 colorTime 3 normRad (f32x4) | 4 splat image (rgba8) 5 splat vertexConf 6 splat normalRad
 // (f32x4) 7 splat time (u16) | 8 fill vertex 9 fill normal (f32x4) 10 fill image (rgba8) | 11 surfels (f32x12, count entries)
 // test access, read only: 12 the new unstable surfels the last fuse appended (f32x12, as many as it counted) 13 the packed texel records of
-// the clean stage (f32x8 per texel; written by cf_models_frame_passes only)
+// the clean stage (f32x8 per texel; written by cf_models_frame_passes only) 14 the z-keys (u64 per texel; all ones between passes)
 int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
 {
     if (!m || !dptr) return CF_EINVAL;
@@ -682,9 +738,23 @@ int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
             p = m->fresh; b = (size_t)nf * 48; break;
         }
         case 13: p = m->clean_rec; b = N * 32; break;
+        case 14: p = m->keys; b = N * 8; break;
         default: return CF_EINVAL;
     }
     *dptr = p; if (bytes) *bytes = b;
+    return CF_OK;
+}
+
+int cf_set_extent_culling(cf_ctx* ctx, int on)
+{
+    if (!ctx) return CF_EINVAL;
+    ctx->extent_cull = on != 0;   // (a pass that runs while it is off leaves its maps' extents unknown: next_extent)
+    return CF_OK;
+}
+int cf_model_extents_unknown(cf_model* m)
+{
+    if (!m) return CF_EINVAL;
+    m->extents_unknown();
     return CF_OK;
 }
 

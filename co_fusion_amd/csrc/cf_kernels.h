@@ -375,6 +375,9 @@ struct IndexPassArgs {   // Model::predictIndices of one model: rasterise surfel
                               // before the host has seen the tracked pose (cf_models_preindex)
     float* clean_rec;         // nullable: [rows * cols][8] -- what the clean pass stages per texel, packed by the resolve pass that feeds it:
     const float* clean_depth; // vertConf.xyzw | colorTime.z, colorTime.w, index, this filtered depth (SurfelCleanArgs::rec)
+    unsigned* ext;            // nullable: the model's ring of three index-map rectangles [3][4] (surfel.hip, EXTENTS): the rasteriser extends slot
+    int ext_slot;             // (ext_slot & 3), the resolve skips the waves outside it and the slot before it -- unless bit 2 says that the maps may
+                              // hold anything -- and zeroes the slot after it.  nullptr: every texel, no ring
 };
 // pose.inverse() of a rigid transform: linear part by cofactors (the statement of the oracle, orc_surfel.c); host and device
 __host__ __device__ inline void inv44f(const float a[16], float o[16])

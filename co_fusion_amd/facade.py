@@ -465,6 +465,10 @@ class CoFusion:
     def set_gn_mode(self, mode):
         assert self.abi.cf_set_gn_mode(self._ctx(), int(mode)) == 0
 
+    def set_extent_culling(self, on=True):
+        """the batched surfel passes skip the texels outside the models' extents (default on; results unchanged: cf_set_extent_culling)"""
+        assert self.abi.cf_set_extent_culling(self._ctx(), int(bool(on))) == 0
+
     def model_download(self, index):
         n = self.model_info(index)["count"]
         out = np.zeros((max(n, 1), 12), np.float32)

@@ -1410,6 +1410,7 @@ int CoFusion::deformMap(int sampleRate, const std::function<int()>& weigh, int c
     re.depth = depthFiltered_dev; re.conf_threshold = g.getConfidenceThreshold(); re.tick = tick;
     struct Restore { int& t; int a; ~Restore() { t += a; } } restore{tick, clockAhead};
     check(ctx, cf_deform_apply(deform, map, count, &re), "cf_deform_apply");
+    check(ctx, cf_model_extents_unknown(g.handle()), "cf_model_extents_unknown");   // (the map was rewritten behind the library's back)
     if (keyframes > 0) {   // Deformation::constrain moves the fern poses with the map
         float* poses = nullptr; int32_t* times = nullptr;
         check(ctx, cf_ferns_keyframe_buffers(ferns, &poses, &times), "cf_ferns_keyframe_buffers");

@@ -27,6 +27,7 @@ SYMBOLS = [
     "cf_bilateral", "cf_model_create", "cf_model_destroy", "cf_model_initialise", "cf_model_count",
     "cf_model_predict_indices", "cf_model_index_keys", "cf_model_index_resolve", "cf_model_combined_predict", "cf_model_prefetch_fill_ratio", "cf_model_perform_fill_in", "cf_model_requires_fill_in",
     "cf_model_fuse", "cf_model_clean", "cf_models_frame_passes", "cf_models_preindex", "cf_model_download_map", "cf_model_upload_map", "cf_model_buffer",
+    "cf_set_extent_culling", "cf_model_extents_unknown",
     "cf_redetect_score", "cf_redetect_timing", "cf_relabel",
     "cf_fusion_weight", "cf_seg_create", "cf_seg_destroy", "cf_seg_slic", "cf_seg_crf", "cf_seg_sums", "cf_seg_infer", "cf_seg_early", "cf_seg_run_batch", "cf_seg_fetch", "cf_seg_publish_poses", "cf_seg_fetch_poses",
     "cf_seg_labels", "cf_seg_buffer", "cf_seg_create_masks", "cf_seg_masks", "cf_seg_masks_batch", "cf_seg_new_mask_value",

@@ -59,6 +59,11 @@ def preindex(ctx: Context, items, depth_cutoff, time_delta=None):
     ctx._check(ctx.lib.cf_models_preindex(ctx.h, arr, n, C.c_float(depth_cutoff), int(TIME_DELTA if time_delta is None else time_delta)))
 
 
+def set_extent_culling(ctx: Context, on=True):
+    """cf_set_extent_culling: the batched passes (frame_passes, preindex) skip the texels outside the models' extents; default on"""
+    ctx._check(ctx.lib.cf_set_extent_culling(ctx.h, int(bool(on))))
+
+
 _BUF = {0: (np.uint32, 1), 1: (np.float32, 4), 2: (np.float32, 4), 3: (np.float32, 4), 4: (np.uint8, 4), 5: (np.float32, 4),
         6: (np.float32, 4), 7: (np.uint16, 1), 8: (np.float32, 4), 9: (np.float32, 4), 10: (np.uint8, 4)}
 
@@ -164,6 +169,10 @@ class Model:
         s = np.ascontiguousarray(surfels, np.float32).reshape(-1, SURFEL)
         self.ctx._check(self.ctx.lib.cf_model_upload_map(self.h, s.ctypes.data_as(C.c_void_p), s.shape[0]))
 
+    def extents_unknown(self):
+        """cf_model_extents_unknown: the caller wrote the model's device buffers itself"""
+        self.ctx._check(self.ctx.lib.cf_model_extents_unknown(self.h))
+
     def tensor(self, which):
         """Zero-copy torch view of a projection buffer (stays valid while the model lives)."""
         ptr = C.c_void_p(); nbytes = C.c_uint64()
@@ -180,6 +189,8 @@ class Model:
             return host.view(np.float32).reshape(-1, SURFEL)
         if which == 13:         # the clean stage's packed texel records
             return host.view(np.float32).reshape(h, w, 8)
+        if which == 14:         # the rasterisers' z-keys
+            return host.view(np.uint64).reshape(h, w)
         dt, ch = _BUF[which]
         a = host.view(dt)
         return a.reshape(h, w, ch) if ch > 1 else a.reshape(h, w)

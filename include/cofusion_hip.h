@@ -443,8 +443,19 @@ int cf_model_upload_map(cf_model *m, const float *host_surfels, uint32_t count);
  *   12  the new unstable surfels the last cf_model_fuse / cf_models_frame_passes appended behind the map before its clean stage
  *       (f32x12 in column-major pixel order; bytes = 48 x their count; waits for the stream)
  *   13  the packed per-texel records cf_models_frame_passes leaves for its clean stage: vertConf | colorTime.z, colorTime.w, index (u32
- *       bits), filtered depth -- 32 bytes per texel (never written by the per-model calls) */
+ *       bits), filtered depth -- 32 bytes per texel (never written by the per-model calls)
+ *   14  the z-keys of the rasterisers (u64 per texel): all ones between passes, every resolve leaves them so */
 int cf_model_buffer(cf_model *m, int which, void **dptr, uint64_t *bytes);
+/* Extent culling of the batched index passes (cf_models_preindex, cf_models_frame_passes).  Every model keeps the pixel rectangle its
+ * index maps were last rasterised into; the resolve launches skip the 64-texel runs outside this pass's and the previous pass's
+ * rectangle, which hold the empty value already (a model with more surfels than half the image has texels is left out: it covers the
+ * screen).  Every buffer holds the same bytes as without it after every launch.
+ * Default on; never under a collective (cf_set_collective, cf_rccl_init).  The per-model entry points always run unculled, and a batched
+ * pass behind one of them -- or behind anything else that leaves the maps in a state the library has not seen -- handles every texel.
+ * CF_NO_EXTENT_CULL in the environment switches it off for the process (diagnostic). */
+int cf_set_extent_culling(cf_ctx *ctx, int on);
+/* for a caller that writes a model's device buffers itself (through the pointers of cf_model_buffer): the next batched pass handles every texel */
+int cf_model_extents_unknown(cf_model *m);
 /* Re-detection of inactive models (CoFusion::redetectModels; the reference left the hook empty, CoFusion.cpp:599-602):
  * how well does a kept map, placed at a hypothesis pose, explain the pixels of a frame that carry a NEW label?  For every surfel i below
  * the model's count with confidence >= conf_threshold: projected as the index pass projects it (index_map.vert:38-63 without the time
