@@ -396,6 +396,10 @@ class Odometry:
         self._keep = depth_pyr
         self.ctx._check(self.ctx.lib.cf_odom_init_icp(self.h, arr, C.c_float(cutoff)))
 
+    def init_icp_maps(self, vertex4, normal4):
+        """the frame side from device maps f32 [H, W, 4] (cf_odom_init_icp_maps): the model-to-model tracker"""
+        self.ctx._check(self.ctx.lib.cf_odom_init_icp_maps(self.h, _p(vertex4), _p(normal4)))
+
     def track(self, trans, rot, rgb_only=False, icp_weight=10.0, pyramid=True, fast_odom=False, so3=True,
               err_surface=None):
         t = _f(np.asarray(trans, np.float32).reshape(3))

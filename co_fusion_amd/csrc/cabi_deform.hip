@@ -15,8 +15,10 @@ struct cf_deform {
     DeformMeta* d_meta = nullptr;
     DeformMeta* h_meta = nullptr;   // pinned
     DeformOut* h_out = nullptr;     // pinned
-    float4* h_cons = nullptr;       // pinned [2][kDeformMaxCons]: sources, targets
-    int n = 0, n_cons = 0;
+    float4* h_cons = nullptr;       // pinned [2][max_cons]: sources, targets
+    float* params0 = nullptr;       // device [kDeformMaxNodes][12]: the parameters cf_deform_optimise_local started from
+    int n = 0, n_cons = 0, max_cons = kDeformMaxCons;
+    int local_time = -1;            // last_deform_time of the cf_deform_optimise_local that left the parameters (-1: none since the graph was made)
 };
 
 static int need_graph(cf_deform* d, const char* who)
@@ -32,18 +34,18 @@ static int read_out(cf_deform* d)
     HIPCHK(ctx, hipStreamSynchronize(ctx->cur()));
     return CF_OK;
 }
-static int assemble(cf_deform* d)
+static int assemble(cf_deform* d, int ldt)
 {
-    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons);
-    launch_deform_assemble(d->ctx->cur(), d->g, d->n, d->n_cons);
+    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons, ldt);
+    launch_deform_assemble(d->ctx->cur(), d->g, d->n, d->n_cons, ldt);
     LAUNCHCHK(d->ctx);
     return CF_OK;
 }
-static int iterate(cf_deform* d, cf_deform_step* out)
+static int iterate(cf_deform* d, int ldt, cf_deform_step* out)
 {
-    if (int r = assemble(d)) return r;
+    if (int r = assemble(d, ldt)) return r;
     launch_deform_solve(d->ctx->cur(), d->g, d->n);
-    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons);
+    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons, ldt);
     LAUNCHCHK(d->ctx);
     if (int r = read_out(d)) return r;
     *out = cf_deform_step{d->h_out->error, d->h_out->delta_norm, d->h_out->failed, d->h_out->mean_cons_error};
@@ -55,7 +57,7 @@ __global__ void __launch_bounds__(kDeformMaxCons) deform_pack_constraints_kernel
                                                                                 const float* __restrict__ time, int n, float4* __restrict__ cons_src,
                                                                                 float4* __restrict__ cons_dst)
 {
-    const int l = threadIdx.x;
+    const int l = (int)(blockIdx.x * kDeformMaxCons + threadIdx.x);
     if (l >= n) return;
     cons_src[l] = make_float4(src[3 * l], src[3 * l + 1], src[3 * l + 2], time[l]);
     cons_dst[l] = make_float4(dst[3 * l], dst[3 * l + 1], dst[3 * l + 2], 0.f);
@@ -86,30 +88,35 @@ void cf_deform_destroy(cf_deform* d)
     (void)hipStreamSynchronize(d->ctx->cur());
     void* ptrs[] = {d->g.nodes, d->g.params, d->g.edges, d->g.cons_src, d->g.cons_dst, d->g.ids, d->g.w, d->g.AB, d->g.b, d->g.r, d->g.out, d->d_meta};
     for (void* p : ptrs) (void)hipFree(p);
+    (void)hipFree(d->params0);
     (void)hipHostFree(d->h_meta); (void)hipHostFree(d->h_out); (void)hipHostFree(d->h_cons);
     delete d;
 }
 
-int cf_deform_create(cf_ctx* ctx, cf_deform** out)
+int cf_deform_create(cf_ctx* ctx, cf_deform** out) { return cf_deform_create_sized(ctx, kDeformMaxCons, out); }
+
+int cf_deform_create_sized(cf_ctx* ctx, int max_constraints, cf_deform** out)
 {
-    if (!ctx || !out) return CF_EINVAL;
+    if (!ctx || !out || max_constraints < 1 || max_constraints > kDeformMaxConsSized) return CF_EINVAL;
     *out = nullptr;
     cf_deform* d = new cf_deform;
     d->ctx = ctx;
-    const size_t nv = (size_t)kDeformMaxNodes * kDeformVars;
-    const size_t rows = (size_t)kDeformMaxNodes * 18 + (size_t)kDeformMaxCons * 3;
+    d->max_cons = max_constraints;
+    const size_t nv = (size_t)kDeformMaxNodes * kDeformVars, mc = (size_t)max_constraints;
+    const size_t rows = (size_t)kDeformMaxNodes * 18 + mc * 3;
     int r = dmalloc(ctx, &d->g.nodes, kDeformMaxNodes);
     if (!r) r = dmalloc(ctx, &d->g.params, nv);
     if (!r) r = dmalloc(ctx, &d->g.edges, (size_t)kDeformMaxNodes * kDeformK);
-    if (!r) r = dmalloc(ctx, &d->g.cons_src, kDeformMaxCons);
-    if (!r) r = dmalloc(ctx, &d->g.cons_dst, kDeformMaxCons);
-    if (!r) r = dmalloc(ctx, &d->g.ids, kDeformMaxCons);
-    if (!r) r = dmalloc(ctx, &d->g.w, kDeformMaxCons);
+    if (!r) r = dmalloc(ctx, &d->g.cons_src, mc);
+    if (!r) r = dmalloc(ctx, &d->g.cons_dst, mc);
+    if (!r) r = dmalloc(ctx, &d->g.ids, mc);
+    if (!r) r = dmalloc(ctx, &d->g.w, mc);
     if (!r) r = dmalloc(ctx, &d->g.AB, nv * kDeformBand);
     if (!r) r = dmalloc(ctx, &d->g.b, nv);
     if (!r) r = dmalloc(ctx, &d->g.r, rows);
     if (!r) r = dmalloc(ctx, &d->g.out, 1);
     if (!r) r = dmalloc(ctx, &d->d_meta, 1);
+    if (!r) r = dmalloc(ctx, &d->params0, nv);
     auto pinned = [&](void** p, size_t bytes) {
         if (r) return;
         const hipError_t e = hipHostMalloc(p, bytes);
@@ -117,7 +124,7 @@ int cf_deform_create(cf_ctx* ctx, cf_deform** out)
     };
     pinned(reinterpret_cast<void**>(&d->h_meta), sizeof(DeformMeta));
     pinned(reinterpret_cast<void**>(&d->h_out), sizeof(DeformOut));
-    pinned(reinterpret_cast<void**>(&d->h_cons), sizeof(float4) * 2 * kDeformMaxCons);
+    pinned(reinterpret_cast<void**>(&d->h_cons), sizeof(float4) * 2 * mc);
     if (!r && hipStreamSynchronize(ctx->cur()) != hipSuccess) { ctx->set_error("cf_deform_create: the fills failed"); r = CF_EHIP; }
     if (r) { cf_deform_destroy(d); return r; }
     *out = d;
@@ -128,6 +135,7 @@ int cf_deform_sample(cf_deform* d, const float* map_dev, uint32_t count, int sam
 {
     if (!d || (!map_dev && count) || sample_rate < 1) return CF_EINVAL;
     cf_ctx* ctx = d->ctx;
+    d->local_time = -1;
     if (reinterpret_cast<uintptr_t>(map_dev) & 15u) { ctx->set_error("cf_deform_sample: the map must be 16-byte aligned"); return CF_EINVAL; }
     uint64_t st = (uint64_t)sample_rate;
     while (((uint64_t)count + st - 1) / st > (uint64_t)kDeformMaxNodes) st += (uint64_t)sample_rate;
@@ -150,6 +158,7 @@ int cf_deform_set_nodes(cf_deform* d, const float* nodes_host, const float* para
 {
     if (!d || !nodes_host || n < 0 || n > kDeformMaxNodes) return CF_EINVAL;
     cf_ctx* ctx = d->ctx;
+    d->local_time = -1;
     d->n = 0; d->n_cons = 0;
     if (n) {
         HIPCHK(ctx, hipMemcpyAsync(d->g.nodes, nodes_host, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
@@ -164,27 +173,27 @@ int cf_deform_set_nodes(cf_deform* d, const float* nodes_host, const float* para
 
 int cf_deform_weights(cf_deform* d, const float* src, const float* dst, const float* src_time, int n)
 {
-    if (!d || n < 0 || n > kDeformMaxCons || (n && (!src || !dst || !src_time))) return CF_EINVAL;
+    if (!d || n < 0 || n > d->max_cons || (n && (!src || !dst || !src_time))) return CF_EINVAL;
     if (int r = need_graph(d, "cf_deform_weights")) return r;
     cf_ctx* ctx = d->ctx;
     HIPCHK(ctx, hipStreamSynchronize(ctx->cur()));   // (the staging block of the previous call)
     for (int l = 0; l < n; l++) {
         d->h_cons[l] = make_float4(src[3 * l], src[3 * l + 1], src[3 * l + 2], src_time[l]);
-        d->h_cons[kDeformMaxCons + l] = make_float4(dst[3 * l], dst[3 * l + 1], dst[3 * l + 2], 0.f);
+        d->h_cons[d->max_cons + l] = make_float4(dst[3 * l], dst[3 * l + 1], dst[3 * l + 2], 0.f);
     }
     if (n) {
         HIPCHK(ctx, hipMemcpyAsync(d->g.cons_src, d->h_cons, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
-        HIPCHK(ctx, hipMemcpyAsync(d->g.cons_dst, d->h_cons + kDeformMaxCons, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
+        HIPCHK(ctx, hipMemcpyAsync(d->g.cons_dst, d->h_cons + d->max_cons, sizeof(float4) * n, hipMemcpyHostToDevice, ctx->cur()));
     }
     return weight_constraints(d, n);
 }
 
 int cf_deform_weights_device(cf_deform* d, const float* src_dev, const float* dst_dev, const float* src_time_dev, int n)
 {
-    if (!d || n < 0 || n > kDeformMaxCons || (n && (!src_dev || !dst_dev || !src_time_dev))) return CF_EINVAL;
+    if (!d || n < 0 || n > d->max_cons || (n && (!src_dev || !dst_dev || !src_time_dev))) return CF_EINVAL;
     if (int r = need_graph(d, "cf_deform_weights_device")) return r;
     if (n) {
-        hipLaunchKernelGGL(deform_pack_constraints_kernel, dim3(1), dim3(kDeformMaxCons), 0, d->ctx->cur(), src_dev, dst_dev, src_time_dev, n,
+        hipLaunchKernelGGL(deform_pack_constraints_kernel, dim3((n + kDeformMaxCons - 1) / kDeformMaxCons), dim3(kDeformMaxCons), 0, d->ctx->cur(), src_dev, dst_dev, src_time_dev, n,
                            d->g.cons_src, d->g.cons_dst);
         LAUNCHCHK(d->ctx);
     }
@@ -195,7 +204,16 @@ int cf_deform_assemble(cf_deform* d)
 {
     if (!d) return CF_EINVAL;
     if (int r = need_graph(d, "cf_deform_assemble")) return r;
-    if (int r = assemble(d)) return r;
+    if (int r = assemble(d, kDeformAllEnabled)) return r;
+    HIPCHK(d->ctx, hipStreamSynchronize(d->ctx->cur()));
+    return CF_OK;
+}
+
+int cf_deform_assemble_local(cf_deform* d, int last_deform_time)
+{
+    if (!d) return CF_EINVAL;
+    if (int r = need_graph(d, "cf_deform_assemble_local")) return r;
+    if (int r = assemble(d, last_deform_time)) return r;
     HIPCHK(d->ctx, hipStreamSynchronize(d->ctx->cur()));
     return CF_OK;
 }
@@ -204,17 +222,25 @@ int cf_deform_iterate(cf_deform* d, cf_deform_step* out)
 {
     if (!d || !out) return CF_EINVAL;
     if (int r = need_graph(d, "cf_deform_iterate")) return r;
-    return iterate(d, out);
+    return iterate(d, kDeformAllEnabled, out);
+}
+
+int cf_deform_iterate_local(cf_deform* d, int last_deform_time, cf_deform_step* out)
+{
+    if (!d || !out) return CF_EINVAL;
+    if (int r = need_graph(d, "cf_deform_iterate_local")) return r;
+    return iterate(d, last_deform_time, out);
 }
 
 int cf_deform_optimise(cf_deform* d, const cf_deform_thresholds* th_in, cf_deform_result* out)
 {
     if (!d || !out) return CF_EINVAL;
     if (int r = need_graph(d, "cf_deform_optimise")) return r;
+    d->local_time = -1;
     cf_deform_thresholds th;
     cf_deform_default_thresholds(&th);
     if (th_in) th = *th_in;
-    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons);
+    launch_deform_residual(d->ctx->cur(), d->g, d->n, d->n_cons, kDeformAllEnabled);
     LAUNCHCHK(d->ctx);
     if (int r = read_out(d)) return r;
     *out = cf_deform_result{0, 0, 0, 0, d->h_out->error, d->h_out->mean_cons_error, d->h_out->error, d->h_out->mean_cons_error};
@@ -223,7 +249,7 @@ int cf_deform_optimise(cf_deform* d, const cf_deform_thresholds* th_in, cf_defor
     double last = (double)out->error;
     for (int it = 1; it <= th.max_iterations; it++) {
         cf_deform_step st;
-        if (int r = iterate(d, &st)) return r;
+        if (int r = iterate(d, kDeformAllEnabled, &st)) return r;
         out->iterations = it;
         if (st.failed) { out->failed = 1; return CF_OK; }
         out->error = st.error; out->mean_cons_error = st.mean_cons_error;
@@ -234,6 +260,44 @@ int cf_deform_optimise(cf_deform* d, const cf_deform_thresholds* th_in, cf_defor
         last = e;
     }
     out->accepted = out->mean_cons_error < th.accept_cons_error && out->error < th.accept_error;
+    return CF_OK;
+}
+
+// optimiseGraphSparse(fernMatch = false): no 0.06 gate, no `error > 10` stop; Deformation::constrain accepts whatever it leaves
+int cf_deform_optimise_local(cf_deform* d, int last_deform_time, const cf_deform_thresholds* th_in, cf_deform_result* out)
+{
+    if (!d || !out) return CF_EINVAL;
+    if (int r = need_graph(d, "cf_deform_optimise_local")) return r;
+    cf_ctx* ctx = d->ctx;
+    d->local_time = last_deform_time < 0 ? -1 : last_deform_time;
+    cf_deform_thresholds th;
+    cf_deform_default_thresholds(&th);
+    if (th_in) th = *th_in;
+    const size_t pbytes = sizeof(float) * kDeformVars * (size_t)d->n;
+    HIPCHK(ctx, hipMemcpyAsync(d->params0, d->g.params, pbytes, hipMemcpyDeviceToDevice, ctx->cur()));
+    launch_deform_residual(ctx->cur(), d->g, d->n, d->n_cons, last_deform_time);
+    LAUNCHCHK(ctx);
+    if (int r = read_out(d)) return r;
+    *out = cf_deform_result{0, 0, 0, 0, d->h_out->error, d->h_out->mean_cons_error, d->h_out->error, d->h_out->mean_cons_error};
+    if (d->h_out->enabled <= 0) return CF_OK;   // every node is older than the last deformation: nothing to solve
+    out->optimised = 1;
+    double last = (double)out->error;
+    for (int it = 1; it <= th.max_iterations; it++) {
+        cf_deform_step st;
+        if (int r = iterate(d, last_deform_time, &st)) return r;
+        out->iterations = it;
+        if (st.failed) {   // (a failed step leaves the parameters of ITS start; an earlier step of this call may have moved them)
+            out->failed = 1;
+            HIPCHK(ctx, hipMemcpyAsync(d->g.params, d->params0, pbytes, hipMemcpyDeviceToDevice, ctx->cur()));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->cur()));
+            return CF_OK;
+        }
+        out->error = st.error; out->mean_cons_error = st.mean_cons_error;
+        const double e = (double)st.error;
+        if (e > last || st.delta_norm < (double)th.min_delta || e < (double)th.min_error || fabs(e - last) < (double)th.min_change * e) break;
+        last = e;
+    }
+    out->accepted = 1;
     return CF_OK;
 }
 
@@ -250,7 +314,7 @@ int cf_deform_apply(cf_deform* d, float* map_dev, uint32_t count, const cf_defor
         ra.cam = re->cam; ra.cols = re->cols; ra.rows = re->rows; ra.max_depth = re->max_depth; ra.depth = re->depth;
         ra.threshold = re->conf_threshold; ra.tick = (float)re->tick;
     }
-    launch_deform_apply(ctx->cur(), d->g, d->n, map_dev, count, re ? &ra : nullptr);
+    launch_deform_apply(ctx->cur(), d->g, d->n, map_dev, count, re ? &ra : nullptr, d->local_time);
     LAUNCHCHK(ctx);
     return CF_OK;
 }

@@ -51,6 +51,11 @@ struct cf_model {
     uint8_t* splat_image = nullptr;
     float *splat_vertex = nullptr, *splat_normal = nullptr;
     uint16_t* splat_time = nullptr;
+    // the INACTIVE prediction (the reference's oldFrameBuffer), allocated by the first cf_model_predict_inactive
+    uint8_t* old_image = nullptr;
+    float *old_vertex = nullptr, *old_normal = nullptr;
+    uint16_t* old_time = nullptr;
+    unsigned* old_covered = nullptr;   // [1] texels of the last inactive prediction with time > 0
     // FillIn textures
     float *fill_vertex = nullptr, *fill_normal = nullptr;
     uint8_t* fill_image = nullptr;
@@ -186,6 +191,8 @@ void cf_model_destroy(cf_model* m)
                     m->colorTime, m->normRad, m->splat_image, m->splat_vertex, m->splat_normal, m->splat_time, m->fill_vertex,
                     m->fill_normal, m->fill_image, m->tcx, m->tcy, m->rays, m->t_inv_dev, m->clean_rec, m->d_ext};
     for (void* p : ptrs) (void)hipFree(p);
+    void* old[] = {m->old_image, m->old_vertex, m->old_normal, m->old_time, m->old_covered};
+    for (void* p : old) (void)hipFree(p);
     (void)hipHostFree(m->h_counts);
     if (m->count_event) (void)hipEventDestroy(m->count_event);
     if (m->ratio_event) (void)hipEventDestroy(m->ratio_event);
@@ -351,6 +358,54 @@ int cf_model_combined_predict(cf_model* m, const float pose[16], float maxDepth,
                             m->splat_time);
     LAUNCHCHK(ctx);
     m->ratio_valid = false;  // a new prediction: any prefetched fill-in ratio is stale
+    return CF_OK;
+}
+
+static SplatPassArgs splat_args(cf_model* m, const float pose[16], uint32_t nb, float maxDepth, float confThreshold, int time, int maxTime, int timeDelta)
+{
+    SplatPassArgs a{};
+    a.surfels = m->buf[m->target]; a.count = m->d_count; a.count_bound = nb; inv44f(pose, a.t_inv); a.maxDepth = maxDepth;
+    a.confThreshold = confThreshold; a.time = time; a.maxTime = maxTime; a.timeDelta = timeDelta; a.rays = m->rays; a.keys = m->keys;
+    return a;
+}
+
+// ModelProjection::combinedPredict(..., INACTIVE) as CoFusion.cpp:390 calls it (time = 0, so no surfel is too old; maxTime = tick -
+// timeDelta, so no active surfel passes) into the model's second target set.  The ACTIVE targets are not touched.
+int cf_model_predict_inactive(cf_model* m, const float pose[16], float maxDepth, float confThreshold, int maxTime, int timeDelta)
+{
+    if (!m || !pose) return CF_EINVAL;
+    cf_ctx* ctx = m->ctx;
+    const size_t N = (size_t)ctx->cfg.width * ctx->cfg.height;
+    if (!m->old_covered) {   // (set last: a call that failed half-way allocates only what is still missing)
+        if (!m->old_image) if (int r = dmalloc(ctx, &m->old_image, N * 4)) return r;
+        if (!m->old_vertex) if (int r = dmalloc(ctx, &m->old_vertex, N * 4)) return r;
+        if (!m->old_normal) if (int r = dmalloc(ctx, &m->old_normal, N * 4)) return r;
+        if (!m->old_time) if (int r = dmalloc(ctx, &m->old_time, N)) return r;
+        if (int r = dmalloc(ctx, &m->old_covered, 1)) return r;
+    }
+    uint32_t nb = 0;
+    if (int r = count_bound(m, &nb)) return r;
+    SplatPassArgs a = splat_args(m, pose, nb, maxDepth, confThreshold, 0, maxTime, timeDelta);
+    a.image = m->old_image; a.vertexConf = m->old_vertex; a.normalRad = m->old_normal; a.time16 = m->old_time;
+    a.fill.out2 = m->old_covered;
+    HIPCHK(ctx, hipMemsetAsync(m->old_covered, 0, sizeof(unsigned), ctx->cur()));
+    launch_predict_counted(ctx->cur(), a, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
+    LAUNCHCHK(ctx);
+    return CF_OK;
+}
+
+// ModelProjection::synthesizeDepth: the vertex stage of the splat and depth_splat.frag -- the acceptance rule of the colour splat
+int cf_model_synthesize_depth(cf_model* m, const float pose[16], float maxDepth, float confThreshold, int time, int maxTime, int timeDelta,
+                              float* depth_out_dev)
+{
+    if (!m || !pose || !depth_out_dev) return CF_EINVAL;
+    cf_ctx* ctx = m->ctx;
+    uint32_t nb = 0;
+    if (int r = count_bound(m, &nb)) return r;
+    SplatPassArgs a = splat_args(m, pose, nb, maxDepth, confThreshold, time, maxTime, timeDelta);
+    a.vertexConf = depth_out_dev;
+    launch_synthesize_depth(ctx->cur(), a, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
+    LAUNCHCHK(ctx);
     return CF_OK;
 }
 
@@ -712,6 +767,8 @@ int cf_model_upload_map(cf_model* m, const float* host_surfels, uint32_t count)
 // (f32x4) 7 splat time (u16) | 8 fill vertex 9 fill normal (f32x4) 10 fill image (rgba8) | 11 surfels (f32x12, count entries)
 // test access, read only: 12 the new unstable surfels the last fuse appended (f32x12, as many as it counted) 13 the packed texel records of
 // the clean stage (f32x8 per texel; written by cf_models_frame_passes only) 14 the z-keys (u64 per texel; all ones between passes)
+// the inactive prediction (cf_model_predict_inactive; CF_ESTATE before the first one): 15 image (rgba8) 16 vertexConf 17 normalRad (f32x4)
+// 18 time (u16) 19 the covered-texel count (one u32)
 int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
 {
     if (!m || !dptr) return CF_EINVAL;
@@ -739,6 +796,14 @@ int cf_model_buffer(cf_model* m, int which, void** dptr, uint64_t* bytes)
         }
         case 13: p = m->clean_rec; b = N * 32; break;
         case 14: p = m->keys; b = N * 8; break;
+        case 15: case 16: case 17: case 18: case 19:
+            if (!m->old_covered) { m->ctx->set_error("cf_model_buffer: no inactive prediction yet (cf_model_predict_inactive)"); return CF_ESTATE; }
+            if (which == 15) { p = m->old_image; b = N * 4; }
+            else if (which == 16) { p = m->old_vertex; b = N * 16; }
+            else if (which == 17) { p = m->old_normal; b = N * 16; }
+            else if (which == 18) { p = m->old_time; b = N * 2; }
+            else { p = m->old_covered; b = 4; }
+            break;
         default: return CF_EINVAL;
     }
     *dptr = p; if (bytes) *bytes = b;

@@ -237,6 +237,28 @@ int cf_odom_init_icp(cf_odom* od, const float* const depth_pyr[CF_NUM_PYRS], flo
     return CF_OK;
 }
 
+// The initICP(GPUTexture*, GPUTexture*, cutoff) overload of RGBDOdometry.cpp:120-141, the frame side of the model-to-model tracker:
+// the vertices into vmaps_tmp (so that the cf_odom_init_rgb behind it derives a genuine nextDepth from them), copyMaps into level 0 of the
+// frame-side maps, resizeVMap / resizeNMap down the pyramid.  The existing preparation kernels, composed: no new arithmetic.  The
+// depth intervals of cf_odom_init_icp do not describe these maps (zrange_valid = false, as after a caller wrote the maps); a later
+// cf_odom_init_icp restores them.
+int cf_odom_init_icp_maps(cf_odom* od, const float* vertex4, const float* normal4)
+{
+    if (!od || !vertex4 || !normal4) return CF_EINVAL;
+    cf_ctx* ctx = od->ctx; hipStream_t s = ctx->stream;
+    const int W = ctx->cfg.width, H = ctx->cfg.height;
+    HIPCHK(ctx, hipMemcpyAsync(od->vmaps_tmp, vertex4, sizeof(float) * 4 * (size_t)W * H, hipMemcpyDeviceToDevice, s));
+    for (int i = 0; i < CF_NUM_PYRS; ++i) { od->ext_vmap_curr[i] = nullptr; od->ext_nmap_curr[i] = nullptr; od->ext_zrange[i] = nullptr; }
+    launch_copy_maps(s, vertex4, normal4, W, H, od->vmap_curr[0], od->nmap_curr[0]);
+    for (int i = 1; i < CF_NUM_PYRS; ++i) {
+        launch_resize_map(s, od->vmap_curr[i - 1], W >> (i - 1), H >> (i - 1), od->vmap_curr[i], false);
+        launch_resize_map(s, od->nmap_curr[i - 1], W >> (i - 1), H >> (i - 1), od->nmap_curr[i], true);
+    }
+    od->zrange_valid = false;
+    LAUNCHCHK(ctx);
+    return CF_OK;
+}
+
 int cf_odom_set_culling(cf_odom* od, int on)
 {
     if (!od) return CF_EINVAL;

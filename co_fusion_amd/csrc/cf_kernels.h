@@ -447,6 +447,10 @@ bool launch_update_compaction_index_keys(hipStream_t s, const UpdatePassArgs* up
                                          int rows);   // the three stages as two launches (surfel.hip); false = not enqueued, use the separate launches
 void launch_index_resolve_batch(hipStream_t s, const IndexPassArgs* items, int n, cf_cam cam, int cols, int rows);
 void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, int n, cf_cam cam, int cols, int rows);
+// the same pass of one model into the targets of `a`, adding the number of covered texels (time > 0) to the device word a.fill.out2
+// (zero before the launch; a.fill.depth_filt == nullptr) / ModelProjection::synthesizeDepth: a.vertexConf is an f32 plane [rows * cols]
+void launch_predict_counted(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows);
+void launch_synthesize_depth(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows);
 void launch_associate_batch(hipStream_t s, const SurfelFuseArgs* items, int n);   // zeroes the new_flags of every model that is not flags_clean first
 void launch_update_batch(hipStream_t s, const UpdatePassArgs* items, int n);
 void launch_clean_batch(hipStream_t s, const CleanPassArgs* items, int n);

@@ -6,6 +6,7 @@
 //   deform_residual_kernel   residual rows (E_rot, E_reg, E_con) in f32, widened; error = sum r^2 and the mean constraint error
 //   deform_assemble_kernel   A = J^T J in band storage and b = -J^T r: one workgroup per 12x12 block, every entry summed by ONE thread in
 //                            row order (the same bits on every run; no atomics)
+//                            (both take last_deform_time, the graph's local mode: the nodes not younger than it leave the system)
 //   deform_solve_kernel      band Cholesky by block columns in one workgroup (panel in LDS, trailing window in L2), forward substitution
 //                            fused into the factorisation, backward substitution, the parameter update and |delta|
 //   deform_apply_kernel      the map pass: node positions and times in LDS for the search and the 20 distances, the four chosen nodes'
@@ -178,7 +179,7 @@ __global__ void __launch_bounds__(kDeformMaxNodes) deform_init_graph_kernel(Defo
 
 __global__ void __launch_bounds__(kDeformMaxCons) deform_weights_kernel(DeformGraph g, int n, int n_cons)
 {
-    const int l = (int)threadIdx.x;
+    const int l = (int)(blockIdx.x * kDeformMaxCons + threadIdx.x);
     if (l >= n_cons) return;
     const float4 s = g.cons_src[l];
     int ids[4]; float w[4];
@@ -225,6 +226,7 @@ __device__ __forceinline__ float jval_cons(f3 dw, float w, int c, int u)
     return (m == 0 ? dw.x : m == 1 ? dw.y : dw.z) * kSqrtCon;
 }
 __device__ __forceinline__ f3 node_pos(const DeformGraph& g, int i) { const float4 v = g.nodes[i]; return f3{v.x, v.y, v.z}; }
+__device__ __forceinline__ bool node_on(const DeformGraph& g, int i, int ldt) { return (int)g.nodes[i].w > ldt; }
 __device__ __forceinline__ int id_of(int4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 __device__ __forceinline__ float w_of(float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
@@ -242,27 +244,34 @@ __device__ __forceinline__ double block_sum(double v, double* red)
     return red[0];
 }
 
-// residual rows -> g.r; error and mean constraint error -> g.out.  One workgroup of kSolveT threads.
-__global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g, int n, int n_cons)
+// residual rows -> g.r; error, mean constraint error and the number of enabled nodes -> g.out.  One workgroup of kSolveT threads.
+// A dropped row (the rotation rows of a disabled node, an edge between two disabled nodes, a constraint none of whose four nodes is
+// enabled) is written as 0: it adds nothing to the error, and no enabled column of J meets it.  The mean constraint error is over
+// ALL constraints (nonRelativeConstraintError does not look at `enabled`).
+__global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g, int n, int n_cons, int ldt)
 {
     __shared__ double red[kSolveT];
-    __shared__ float norms[kDeformMaxCons];
+    __shared__ float norms[kDeformMaxConsSized];
     const int t = (int)threadIdx.x;
     const float sr = sqrt_reg();
-    if (t < n_cons) {
-        const float4 s = g.cons_src[t], q = g.cons_dst[t], w4 = g.w[t];
-        const int4 i4 = g.ids[t];
+    for (int l = t; l < n_cons; l += kSolveT) {
+        const float4 s = g.cons_src[l], q = g.cons_dst[l], w4 = g.w[l];
+        const int4 i4 = g.ids[l];
         const int ids[4] = {i4.x, i4.y, i4.z, i4.w};
         const float w[4] = {w4.x, w4.y, w4.z, w4.w};
         f3 m = f3{s.x, s.y, s.z};
         if (finite_f(w4.x)) m = move_point(g.nodes, g.params, m, ids, w);
         const float dx = m.x - q.x, dy = m.y - q.y, dz = m.z - q.z;
-        g.r[cons_row(n, t, 0)] = (double)dx * (double)kSqrtCon;
-        g.r[cons_row(n, t, 1)] = (double)dy * (double)kSqrtCon;
-        g.r[cons_row(n, t, 2)] = (double)dz * (double)kSqrtCon;
-        norms[t] = sqrtf((dx * dx + dy * dy) + dz * dz);
+        const bool keep = node_on(g, ids[0], ldt) || node_on(g, ids[1], ldt) || node_on(g, ids[2], ldt) || node_on(g, ids[3], ldt);
+        g.r[cons_row(n, l, 0)] = keep ? (double)dx * (double)kSqrtCon : 0.0;
+        g.r[cons_row(n, l, 1)] = keep ? (double)dy * (double)kSqrtCon : 0.0;
+        g.r[cons_row(n, l, 2)] = keep ? (double)dz * (double)kSqrtCon : 0.0;
+        norms[l] = sqrtf((dx * dx + dy * dy) + dz * dz);
     }
+    int on_count = 0;
     for (int j = t; j < n; j += kSolveT) {
+        const bool on = node_on(g, j, ldt);
+        on_count += on ? 1 : 0;
         const float* P = g.params + (size_t)j * kDeformVars;
         float Pj[12];
 #pragma unroll
@@ -271,7 +280,7 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
         for (int q = 0; q < 6; q++) {
             const int a = q >= 3 ? q - 3 : (q == 2 ? 1 : 0), b = q >= 3 ? q - 3 : (q == 0 ? 1 : 2);
             const float dot = (Pj[3 * a] * Pj[3 * b] + Pj[3 * a + 1] * Pj[3 * b + 1]) + Pj[3 * a + 2] * Pj[3 * b + 2];
-            g.r[rot_row(j, q)] = q >= 3 ? (double)dot - 1.0 : (double)dot;
+            g.r[rot_row(j, q)] = !on ? 0.0 : q >= 3 ? (double)dot - 1.0 : (double)dot;
         }
         const f3 gj = node_pos(g, j);
         const float gv[3] = {gj.x, gj.y, gj.z};
@@ -287,11 +296,11 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
                 v = v + gv[c];
                 v = v + Pj[9 + c];
                 v = v - (gnv[c] + Pn[9 + c]);
-                g.r[edge_row(n, j, k, c)] = (double)v * (double)sr;
+                g.r[edge_row(n, j, k, c)] = on || node_on(g, nb, ldt) ? (double)v * (double)sr : 0.0;
             }
         }
     }
-    __syncthreads();
+    const int enabled = __syncthreads_count(on_count);   // (n <= kSolveT: one node per thread)
     const int rows = 18 * n + 3 * n_cons;
     double s = 0.0;
     for (int i = t; i < rows; i += kSolveT) { const double v = g.r[i]; s = s + v * v; }
@@ -301,18 +310,27 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
         for (int l = 0; l < n_cons; l++) m = m + norms[l];
         g.out->error = (float)e;
         g.out->mean_cons_error = m / (float)n_cons;
+        g.out->enabled = enabled;
     }
 }
 
 // workgroup (I, dj): the 12x12 block of A at block row I, block column J = I - dj, entry (r, c) by thread 12 r + c; the workgroups of
 // dj == 0 also sum b (threads 144..155).  Every sum runs over the rows of J in row order.
-__global__ void __launch_bounds__(192) deform_assemble_kernel(DeformGraph g, int n, int n_cons)
+// A disabled node's columns leave the system: its blocks of A are zero, its diagonal block the identity, its part of b zero.  A block
+// between two enabled nodes sums exactly the rows it summed before (every row that meets an enabled column is kept).
+__global__ void __launch_bounds__(192) deform_assemble_kernel(DeformGraph g, int n, int n_cons, int ldt)
 {
     const int I = (int)blockIdx.x / (kDeformBand / kDeformVars), dj = (int)blockIdx.x % (kDeformBand / kDeformVars), J = I - dj;
     const int t = (int)threadIdx.x;
     if (J < 0 || t >= 156 || (t >= 144 && dj != 0)) return;
     const bool rhs = t >= 144;
     const int r = rhs ? t - 144 : t / 12, c = rhs ? 0 : t % 12;
+    if (!node_on(g, I, ldt) || !node_on(g, J, ldt)) {
+        const int i = kDeformVars * I + r, j = kDeformVars * J + c;
+        if (rhs) g.b[i] = 0.0;
+        else if (j <= i) g.AB[(size_t)i * kDeformBand + (i - j)] = i == j ? 1.0 : 0.0;
+        return;
+    }
     double s = 0.0;
     if (I == J) {
         const float* P = g.params + (size_t)I * kDeformVars;
@@ -461,7 +479,8 @@ __global__ void __launch_bounds__(kSolveT) deform_solve_kernel(DeformGraph g, in
 
 // ------------------------------------------------------------------------------------------------ map and poses
 template <bool kStamp>
-__global__ void __launch_bounds__(kDB) deform_apply_kernel(DeformGraph g, int n, float4* __restrict__ map, unsigned count, DeformReactivate re)
+__global__ void __launch_bounds__(kDB) deform_apply_kernel(DeformGraph g, int n, float4* __restrict__ map, unsigned count, DeformReactivate re,
+                                                           int last_deform_time)
 {
     __shared__ float4 nodes[kDeformMaxNodes];
     for (int i = (int)threadIdx.x; i < n; i += kDB) nodes[i] = g.nodes[i];
@@ -474,7 +493,11 @@ __global__ void __launch_bounds__(kDB) deform_apply_kernel(DeformGraph g, int n,
     for (size_t i = (size_t)blockIdx.x * kDB + threadIdx.x; i < count; i += (size_t)gridDim.x * kDB) {
         float4 pc = map[i * 3], ct = map[i * 3 + 1];
         int ids[4]; float w[4];
-        if (window_weights(nodes, n, f3{pc.x, pc.y, pc.z}, (int)ct.z, ids, w)) {
+        // (the local mode: a surfel none of whose four nodes is enabled keeps its bits -- the identity of disabled nodes would still round
+        // (p - g) + g; with last_deform_time < 0, the global mode, every node time passes)
+        if (window_weights(nodes, n, f3{pc.x, pc.y, pc.z}, (int)ct.z, ids, w) &&
+            ((int)nodes[ids[0]].w > last_deform_time || (int)nodes[ids[1]].w > last_deform_time || (int)nodes[ids[2]].w > last_deform_time ||
+             (int)nodes[ids[3]].w > last_deform_time)) {
             float4 nr = map[i * 3 + 2];
             const f3 p = move_point(nodes, g.params, f3{pc.x, pc.y, pc.z}, ids, w);
             const f3 m = move_normal(g.params, f3{nr.x, nr.y, nr.z}, ids, w);
@@ -563,27 +586,27 @@ void launch_deform_init_graph(hipStream_t s, const DeformGraph& g, int n, bool i
 }
 void launch_deform_weights(hipStream_t s, const DeformGraph& g, int n, int n_cons)
 {
-    if (n_cons > 0) hipLaunchKernelGGL(deform_weights_kernel, dim3(1), dim3(kDeformMaxCons), 0, s, g, n, n_cons);
+    if (n_cons > 0) hipLaunchKernelGGL(deform_weights_kernel, dim3((n_cons + kDeformMaxCons - 1) / kDeformMaxCons), dim3(kDeformMaxCons), 0, s, g, n, n_cons);
 }
-void launch_deform_residual(hipStream_t s, const DeformGraph& g, int n, int n_cons)
+void launch_deform_residual(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time)
 {
-    hipLaunchKernelGGL(deform_residual_kernel, dim3(1), dim3(kSolveT), 0, s, g, n, n_cons);
+    hipLaunchKernelGGL(deform_residual_kernel, dim3(1), dim3(kSolveT), 0, s, g, n, n_cons, last_deform_time);
 }
-void launch_deform_assemble(hipStream_t s, const DeformGraph& g, int n, int n_cons)
+void launch_deform_assemble(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time)
 {
-    hipLaunchKernelGGL(deform_assemble_kernel, dim3(n * (kDeformBand / kDeformVars)), dim3(192), 0, s, g, n, n_cons);
+    hipLaunchKernelGGL(deform_assemble_kernel, dim3(n * (kDeformBand / kDeformVars)), dim3(192), 0, s, g, n, n_cons, last_deform_time);
 }
 void launch_deform_solve(hipStream_t s, const DeformGraph& g, int n)
 {
     hipLaunchKernelGGL(deform_solve_kernel, dim3(1), dim3(kSolveT), 0, s, g, n);
 }
-void launch_deform_apply(hipStream_t s, const DeformGraph& g, int n, float* map, unsigned count, const DeformReactivate* re)
+void launch_deform_apply(hipStream_t s, const DeformGraph& g, int n, float* map, unsigned count, const DeformReactivate* re, int last_deform_time)
 {
     if (!count) return;
     unsigned blocks = (count + kDB - 1) / kDB;
     blocks = blocks > 1024 ? 1024 : blocks;   // every workgroup stages the nodes (16 KB) once
-    if (re) hipLaunchKernelGGL(deform_apply_kernel<true>, dim3(blocks), dim3(kDB), 0, s, g, n, reinterpret_cast<float4*>(map), count, *re);
-    else hipLaunchKernelGGL(deform_apply_kernel<false>, dim3(blocks), dim3(kDB), 0, s, g, n, reinterpret_cast<float4*>(map), count, DeformReactivate{});
+    if (re) hipLaunchKernelGGL(deform_apply_kernel<true>, dim3(blocks), dim3(kDB), 0, s, g, n, reinterpret_cast<float4*>(map), count, *re, last_deform_time);
+    else hipLaunchKernelGGL(deform_apply_kernel<false>, dim3(blocks), dim3(kDB), 0, s, g, n, reinterpret_cast<float4*>(map), count, DeformReactivate{}, last_deform_time);
 }
 void launch_deform_poses(hipStream_t s, const DeformGraph& g, int n, float* poses, const int* times, int n_poses)
 {

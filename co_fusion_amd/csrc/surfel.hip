@@ -603,6 +603,13 @@ int fill_ratio_sample_blocks(int cols, int rows)
 // The resolve of the splat pass.  A model whose arguments carry SplatFillArgs also gets, from the same registers, its fill-in maps and
 // the covered count of CoFusion::requiresFillIn (see SplatFillArgs): such a share runs without early exits, so that every thread of
 // a workgroup meets the barriers of the count.
+// kMode: kSplatFull is combinedPredict.  kSplatCount is the same into another target set (the INACTIVE prediction of local loop closure)
+// and adds the number of covered texels (time > 0) to the word fill.out2 points at, which the host zeroed in front of the launch (integer
+// adds: the same count in any order; like the fill share it relies on the kernel having NO early exit in front of its barrier: the
+// threads past the last texel fall through to __syncthreads_count).  kSplatDepth is synthesizeDepth (splat.vert + depth_splat.frag: the vertex stage, the disc test and
+// the depth range of the colour splat, one output): corrected_pos.z into the f32 plane `vertexConf` points at, 0 where nothing lands.
+enum { kSplatFull = 0, kSplatCount = 1, kSplatDepth = 2 };
+template <int kMode>
 __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs> B, const FrameGeom g)
 {
     const VBlock vb = batch_decode(B.h);
@@ -614,7 +621,7 @@ __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs
     const cf_cam cam = g.cam;
     const int q = vb.bid * kB + threadIdx.x;
     const bool fill = a.fill.depth_filt != nullptr;   // (uniform)
-    bool covered = false, sample = false;
+    bool covered = false, sample = false, timed = false;
     if (q < cols * rows) {
         const int py = q / cols, px = q - py * cols;
         const unsigned long long k = keys[q];
@@ -637,7 +644,12 @@ __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs
             nrad = make_float4(s.n.x, s.n.y, s.n.z, s.rad);
             t16 = (unsigned short)(unsigned)ct.z;
         }
-        image[q] = img; vertexConf[q] = vc; normalRad[q] = nrad; time16[q] = t16;
+        if constexpr (kMode == kSplatDepth) {
+            reinterpret_cast<float*>(vertexConf)[q] = vc.z;
+        } else {
+            image[q] = img; vertexConf[q] = vc; normalRad[q] = nrad; time16[q] = t16;
+        }
+        timed = t16 > 0;
         if (fill) {
             fill_in_px(vc, nrad, img, a.fill.depth_filt, reinterpret_cast<const uchar4*>(a.fill.rgba), cols, rows, px, py, q, cam.cx, cam.cy,
                        a.fill.inv_fx, a.fill.inv_fy, a.fill.pass_geom, a.fill.pass_rgb, reinterpret_cast<float4*>(a.fill.fill_vertex),
@@ -646,6 +658,11 @@ __global__ void __launch_bounds__(kB) splat_resolve_kernel(const Batch<SplatArgs
             sample = dw > 0 && dh > 0 && fill_ratio_sample(py, dh, rows) && fill_ratio_sample(px, dw, cols);
             covered = sample && img.x > 0 && img.y > 0 && img.z > 0;
         }
+    }
+    if constexpr (kMode == kSplatCount) {
+        const int n_timed = __syncthreads_count(timed ? 1 : 0);
+        if (threadIdx.x == 0 && n_timed > 0) atomicAdd(a.fill.out2, (unsigned)n_timed);
+        return;
     }
     if (!fill) return;
     // Only the workgroups that hold a sample position take part (the host counted them: sample_blocks), each with ONE atomic that
@@ -1185,7 +1202,7 @@ void launch_predict_indices(hipStream_t s, const float* surfels, const unsigned*
     launch_index_resolve(s, surfels, t_inv, cols, rows, keys, index, vertConf, colorTime, normRad);
 }
 // ---- combinedPredict ------------------------------------------------------------------------------------------------------------
-void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, int n_items, cf_cam cam, int cols, int rows)
+static void splat_pass(hipStream_t s, const SplatPassArgs* items, int n_items, cf_cam cam, int cols, int rows, int mode)
 {
     const FrameGeom g{cam, cols, rows};
     for (int base = 0; base < n_items; base += kSurfBatch) {
@@ -1202,9 +1219,20 @@ void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, in
         }
         if (any) splat_raster_kernel<<<batch_layout(B, blocks, nb), kB, 0, s>>>(B, g);
         for (int k = 0; k < nb; k++) blocks[k] = gridFor((long long)cols * rows);
-        splat_resolve_kernel<<<batch_layout(B, blocks, nb), kB, 0, s>>>(B, g);
+        const int grid = batch_layout(B, blocks, nb);
+        if (mode == kSplatCount) splat_resolve_kernel<kSplatCount><<<grid, kB, 0, s>>>(B, g);
+        else if (mode == kSplatDepth) splat_resolve_kernel<kSplatDepth><<<grid, kB, 0, s>>>(B, g);
+        else splat_resolve_kernel<kSplatFull><<<grid, kB, 0, s>>>(B, g);
     }
 }
+void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, int n_items, cf_cam cam, int cols, int rows)
+{
+    splat_pass(s, items, n_items, cam, cols, rows, kSplatFull);
+}
+// a.fill.out2: the device word the covered count is added to (zero before the launch); no fill-in (a.fill.depth_filt == nullptr)
+void launch_predict_counted(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows) { splat_pass(s, &a, 1, cam, cols, rows, kSplatCount); }
+// a.vertexConf: the f32 depth plane [rows * cols]; the other targets are not written
+void launch_synthesize_depth(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows) { splat_pass(s, &a, 1, cam, cols, rows, kSplatDepth); }
 void launch_combined_predict(hipStream_t s, const float* surfels, const unsigned* count, unsigned count_bound, const float t_inv[16], cf_cam cam,
                              int cols, int rows, float maxDepth, float confThreshold, int time, int maxTime, int timeDelta,
                              const float* rays, unsigned long long* keys, uint8_t* image, float* vertexConf, float* normalRad,

@@ -1,5 +1,6 @@
 """ctypes binding of the deformation graph (cf_deform_* in include/cofusion_hip.h; csrc/deform.hip): loop closure of one
 surfel map from absolute constraints -- sample the graph, weight the constraint points, optimise, move the map and the keyframe poses.
+The graph's local mode (a last_deform_time: only younger nodes are free) is the *_local calls, behind the same methods.
 Maps are a model.Model or a torch CUDA tensor f32 [S, 12]; poses and times are torch CUDA tensors."""
 from __future__ import annotations
 
@@ -11,6 +12,7 @@ from .api import Cam, _p
 
 MAX_NODES = 1024
 MAX_CONSTRAINTS = 128
+MAX_CONSTRAINTS_SIZED = 1536
 BAND = 240
 VARS = 12
 STEP_FIELDS = ("error", "delta_norm", "failed", "mean_cons_error")
@@ -44,6 +46,10 @@ _V, _I, _F = C.c_void_p, C.c_int, C.c_float
 _PI = C.POINTER(C.c_int)
 SIGNATURES = {
     "cf_deform_create": (_I, [_V, C.POINTER(_V)]),
+    "cf_deform_create_sized": (_I, [_V, _I, C.POINTER(_V)]),
+    "cf_deform_assemble_local": (_I, [_V, _I]),
+    "cf_deform_iterate_local": (_I, [_V, _I, C.POINTER(Step)]),
+    "cf_deform_optimise_local": (_I, [_V, _I, C.POINTER(Thresholds), C.POINTER(Result)]),
     "cf_deform_destroy": (None, [_V]),
     "cf_deform_default_thresholds": (None, [C.POINTER(Thresholds)]),
     "cf_deform_sample": (_I, [_V, _V, C.c_uint32, _I, _PI, _PI, _PI]),
@@ -87,12 +93,15 @@ def _host(a, dtype, shape):
 
 
 class Deform:
-    """cf_deform on an api.Context"""
+    """cf_deform on an api.Context; max_constraints: None (128, cf_deform_create) or a capacity up to MAX_CONSTRAINTS_SIZED"""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, max_constraints=None):
         self.ctx, self.lib = ctx, bind(ctx.lib)
         self.h = C.c_void_p()
-        ctx._check(self.lib.cf_deform_create(ctx.h, C.byref(self.h)))
+        if max_constraints is None:
+            ctx._check(self.lib.cf_deform_create(ctx.h, C.byref(self.h)))
+        else:
+            ctx._check(self.lib.cf_deform_create_sized(ctx.h, int(max_constraints), C.byref(self.h)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -129,17 +138,34 @@ class Deform:
         addr = lambda a: C.c_void_p(a) if isinstance(a, int) else _p(a)
         self.ctx._check(self.lib.cf_deform_weights_device(self.h, addr(src), addr(dst), addr(src_time), int(n)))
 
-    def assemble(self):
-        self.ctx._check(self.lib.cf_deform_assemble(self.h))
+    def assemble(self, last_deform_time=None):
+        """last_deform_time None: every node is free (cf_deform_assemble); an int: the local mode (cf_deform_assemble_local)"""
+        if last_deform_time is None:
+            self.ctx._check(self.lib.cf_deform_assemble(self.h))
+        else:
+            self.ctx._check(self.lib.cf_deform_assemble_local(self.h, int(last_deform_time)))
 
-    def iterate(self):
+    def iterate(self, last_deform_time=None):
         st = Step()
-        self.ctx._check(self.lib.cf_deform_iterate(self.h, C.byref(st)))
+        if last_deform_time is None:
+            self.ctx._check(self.lib.cf_deform_iterate(self.h, C.byref(st)))
+        else:
+            self.ctx._check(self.lib.cf_deform_iterate_local(self.h, int(last_deform_time), C.byref(st)))
         return dict(error=np.float32(st.error), delta_norm=float(st.delta_norm), failed=bool(st.failed), mean_cons_error=np.float32(st.mean_cons_error))
 
     def optimise(self, thresholds=None):
         r = Result()
         self.ctx._check(self.lib.cf_deform_optimise(self.h, None if thresholds is None else C.byref(thresholds), C.byref(r)))
+        return self._result(r)
+
+    def optimise_local(self, last_deform_time, thresholds=None):
+        """the graph's local mode: no 0.06 gate, no `error > 10` stop, accepted unless a step failed or no node is enabled"""
+        r = Result()
+        self.ctx._check(self.lib.cf_deform_optimise_local(self.h, int(last_deform_time), None if thresholds is None else C.byref(thresholds), C.byref(r)))
+        return self._result(r)
+
+    @staticmethod
+    def _result(r):
         out = {k: getattr(r, k) for k in RESULT_FIELDS}
         for k in ("optimised", "accepted", "failed"):
             out[k] = bool(out[k])

@@ -402,6 +402,42 @@ class CoFusion:
         out["last"] = last
         return out
 
+    def set_local_loop_closure(self, on=True, sample_rate=5000, icp_count_thresh=40000, icp_err_thresh=5e-5, cov_thresh=1e-5,
+                               min_inactive_pixels=None):
+        """Local (model-to-model) loop closure in the frame loop (cofusion_set_local_loop_closure): a tracked frame
+        registers the active view of the background map onto the inactive one with a second tracker; an accepted registration deforms
+        the map with a graph sampled at `sample_rate`, reactivates the old surfels in view and corrects the camera pose.
+        min_inactive_pixels: frames with fewer covered inactive texels stop behind the registration (None: icp_count_thresh; 0: no
+        gate).  Needs time_delta > 0; needs no set_relocalisation."""
+        f = C.c_float
+        self._check(self.lib.cofusion_set_local_loop_closure(self.h, int(bool(on)), int(sample_rate), int(icp_count_thresh), f(icp_err_thresh),
+                                                             f(cov_thresh), -1 if min_inactive_pixels is None else int(min_inactive_pixels)))
+
+    def local_loop_stats(self):
+        """-> frames examined / skipped by the pixel gate / accepted by the second tracker, graphs optimised / accepted / failed, the last
+        accept's node and constraint counts, whether it was pinned and its tick, deforms, last_deform_time, and of the last examined
+        frame the covered texels, the accept rule's outcome and figures and the estimated pose [4, 4]; the last optimisation's outcome
+        under `last` (co_fusion_amd.deform.RESULT_FIELDS)"""
+        from . import deform as _deform
+        ints = ("examined", "skipped_by_gate", "tracker_accepts", "optimised", "accepted", "failed", "last_nodes", "last_constraints",
+                "last_pinned", "last_tick", "deforms", "last_deform_time")
+
+        class _Stats(C.Structure):
+            _fields_ = ([(k, C.c_int32) for k in ints] + [("last_covered", C.c_uint32), ("last_tracker_accepted", C.c_int32),
+                        ("last_icp_error", C.c_float), ("last_icp_count", C.c_float), ("last_max_covariance", C.c_double),
+                        ("last_est_pose", C.c_float * 16), ("last", _deform.Result)])
+        assert C.sizeof(_Stats) == 168
+        s = _Stats()
+        self._check(self.lib.cofusion_local_loop_stats(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k in ints + ("last_covered", "last_icp_error", "last_icp_count", "last_max_covariance")}
+        out["last_pinned"] = bool(out["last_pinned"]); out["last_tracker_accepted"] = bool(s.last_tracker_accepted)
+        out["last_est_pose"] = np.array(list(s.last_est_pose), np.float32).reshape(4, 4)
+        last = {k: getattr(s.last, k) for k in _deform.RESULT_FIELDS}
+        for k in ("optimised", "accepted", "failed"):
+            last[k] = bool(last[k])
+        out["last"] = last
+        return out
+
     def set_redetection(self, on=True, min_fit=0.5, min_cover=0.044, depth_tol=0.10, max_candidates=8, keep_min_surfels=4000,
                         keep_conf_threshold=0.3):
         """Re-detection of inactive object models (cofusion_set_redetection): a frame with a new label scores the most

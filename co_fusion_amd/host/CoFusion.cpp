@@ -644,6 +644,7 @@ CoFusion::~CoFusion()
     releaseRenderer();
     if (ferns) cf_ferns_destroy(ferns);
     if (deform) cf_deform_destroy(deform);
+    releaseLocalLoop();
     models.clear(); inactiveModels.clear(); newModel.reset(); globalModel.reset();
     cf_free(ctx, depth_dev);
     for (int b = 0; b < 2; b++) { cf_free(ctx, depthFilteredBuf[b]); cf_free(ctx, depthPyr1Buf[b]); cf_free(ctx, depthPyr2Buf[b]); }
@@ -1265,7 +1266,9 @@ bool CoFusion::processFrame(const FrameData& frame, const Mat4f* inPose, float w
     framePreIndex();
     frameCollect();
     frameFuse(true, 0);
+    fernClosedThisFrame = false;
     if (ferns) fernsAfterPredict();
+    if (closeLocalLoops) localLoopAfterPredict();
     frameEnd();
     if (exportViewsWhich) exportViews(frameTick);   // opt-in (setExportViews): renders after the frame, reads the maps only
     return false;
@@ -1343,7 +1346,7 @@ void CoFusion::fernsAfterPredict()
         fernLastClosest = -1;
         if (rec.match_id >= 0 && rec.overlap > 0.3f) {
             loopSt.candidates++;
-            if (closeLoop(rec)) return;   // (the corrected frame has been offered from the redone fill-in)
+            if (closeLoop(rec)) { fernClosedThisFrame = true; return; }   // (the corrected frame has been offered from the redone fill-in)
         }
         check(ctx, cf_ferns_append(ferns, g.getPose().m, tick, fernThreshold), "cf_ferns_append");
         return;
@@ -1379,16 +1382,18 @@ int CoFusion::deformBackground(const float* src, const float* dst, const float* 
     }
     // the clock has already moved on from the frame the map was last fused in (frameEnd): the stamp and the prediction are that frame's
     cf_deform_result res{};
-    const int nodes = deformMap(sampleRate > 0 ? sampleRate : 25000, [&] { return cf_deform_weights(deform, s.data(), d.data(), t.data(), (int)t.size()); },
-                                lost ? 0 : 1, nullptr, 0, &res);
+    const int nodes = deformMap(deform, sampleRate > 0 ? sampleRate : 25000, [&] { return cf_deform_weights(deform, s.data(), d.data(), t.data(), (int)t.size()); },
+                                lost ? 0 : 1, nullptr, 0, -1, &res);
     if (result) *result = res;
     if (res.accepted) check(ctx, cf_synchronize(ctx), "cf_synchronize");
     return nodes;
 }
 
-int CoFusion::deformMap(int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes,
-                        cf_deform_result* result)
+int CoFusion::deformMap(cf_deform* graph, int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes,
+                        int lastDeformTime, cf_deform_result* result)
 {
+    cf_deform* const deform = graph;
+    const bool local = lastDeformTime >= 0;
     Model& g = *globalModel;
     uint32_t count = 0;
     check(ctx, cf_model_count(g.handle(), &count), "cf_model_count");
@@ -1399,15 +1404,22 @@ int CoFusion::deformMap(int sampleRate, const std::function<int()>& weigh, int c
     if (result) *result = res;
     if (nodes < 5 || !monotone) return nodes;
     check(ctx, weigh(), "cf_deform_weights");
-    check(ctx, cf_deform_optimise(deform, nullptr, &res), "cf_deform_optimise");
+    if (local) check(ctx, cf_deform_optimise_local(deform, lastDeformTime, nullptr, &res), "cf_deform_optimise_local");
+    else check(ctx, cf_deform_optimise(deform, nullptr, &res), "cf_deform_optimise");
     if (result) *result = res;
     if (!res.accepted) return nodes;
+    // a local closure moves the camera a second time in this frame: which surfels are in view at the corrected pose is read from the depth
+    // of the UN-DEFORMED map seen from there (ModelProjection::synthesizeDepth, CoFusion.cpp:481; depthSamplerPrediction of
+    // copy_unstable.vert:327), not from the frame's
+    if (local && correctedPose)
+        check(ctx, cf_model_synthesize_depth(g.handle(), correctedPose->m, maxDepthProcessed, cfg.confGlobalInit, tick - clockAhead,
+                                             tick - clockAhead - cfg.timeDelta, 65535, localDepth), "cf_model_synthesize_depth");
     if (correctedPose) g.overridePose(*correctedPose);
     cf_deform_reactivate re{};
     for (int i = 0; i < 16; i++) re.pose[i] = g.getPose().m[i];
     re.cam = cf_cam{cfg.fx, cfg.fy, cfg.cx, cfg.cy}; re.cols = cfg.width; re.rows = cfg.height; re.max_depth = maxDepthProcessed;
     tick -= clockAhead;
-    re.depth = depthFiltered_dev; re.conf_threshold = g.getConfidenceThreshold(); re.tick = tick;
+    re.depth = local && correctedPose ? localDepth : depthFiltered_dev; re.conf_threshold = g.getConfidenceThreshold(); re.tick = tick;
     struct Restore { int& t; int a; ~Restore() { t += a; } } restore{tick, clockAhead};
     check(ctx, cf_deform_apply(deform, map, count, &re), "cf_deform_apply");
     check(ctx, cf_model_extents_unknown(g.handle()), "cf_model_extents_unknown");   // (the map was rewritten behind the library's back)
@@ -1439,14 +1451,99 @@ bool CoFusion::closeLoop(const cf_ferns_gate& gate)
     Mat4f est;
     for (int i = 0; i < 16; i++) est.m[i] = res.pose[i];
     cf_deform_result dr{};
-    loopSt.lastNodes = deformMap(loopSampleRate, [&] { return cf_deform_weights_device(deform, src, dst, time, cl.n_constraints); }, 0, &est,
-                                 gate.keyframes, &dr);
+    loopSt.lastNodes = deformMap(deform, loopSampleRate, [&] { return cf_deform_weights_device(deform, src, dst, time, cl.n_constraints); }, 0, &est,
+                                 gate.keyframes, -1, &dr);
     loopSt.last = dr;
     loopSt.optimised += dr.optimised; loopSt.accepted += dr.accepted; loopSt.failed += dr.failed;
     if (!dr.accepted) return false;
     check(ctx, cf_ferns_add_async(ferns, static_cast<const float*>(mbuf(ctx, g.handle(), 8)), static_cast<const float*>(mbuf(ctx, g.handle(), 9)),
                                   static_cast<const uint8_t*>(mbuf(ctx, g.handle(), 10)), g.getPose().m, tick, fernThreshold), "cf_ferns_add_async");
     return true;
+}
+
+void CoFusion::releaseLocalLoop()
+{
+    if (localLoop) { cf_local_loop_destroy(localLoop); localLoop = nullptr; }
+    if (localDeform) { cf_deform_destroy(localDeform); localDeform = nullptr; }
+    if (modelToModel) { cf_odom_destroy(modelToModel); modelToModel = nullptr; }
+    if (localDepth) { cf_free(ctx, localDepth); localDepth = nullptr; }
+}
+
+void CoFusion::setLocalLoopClosure(bool on, int sampleRate, int icpCountThresh, float icpErrThresh, float covThresh, int minInactivePixels)
+{
+    if (on && dist.world > 1) throw std::runtime_error("setLocalLoopClosure: a single-GPU option, like reloc");
+    if (on && !ownsCtx) throw std::runtime_error("setLocalLoopClosure: not available for a sequence of a lock-step group");
+    if (on && (cfg.timeDelta <= 0 || cfg.timeDelta >= Config().timeDelta))   // (the C surface's time_delta <= 0 is the open-loop default here)
+        throw std::runtime_error("setLocalLoopClosure: needs Config::timeDelta > 0 (without it there is no inactive map)");
+    if (on && sampleRate < 1) throw std::runtime_error("setLocalLoopClosure: sampleRate >= 1");
+    if (on && !localLoop) {
+        try {
+            check(ctx, cf_local_loop_create(ctx, &localLoop), "cf_local_loop_create");
+            check(ctx, cf_deform_create_sized(ctx, CF_DEFORM_MAX_CONSTRAINTS_SIZED, &localDeform), "cf_deform_create_sized");
+            check(ctx, cf_odom_create(ctx, &modelToModel), "cf_odom_create");
+            void* p = nullptr;
+            check(ctx, cf_malloc(ctx, (uint64_t)cfg.width * cfg.height * 4, &p), "cf_malloc");
+            localDepth = static_cast<float*>(p);
+        } catch (...) { releaseLocalLoop(); throw; }
+    }
+    closeLocalLoops = on;
+    if (on) {
+        localSampleRate = sampleRate;
+        localTh = cf_local_loop_thresholds{covThresh, icpCountThresh, icpErrThresh};
+        localMinInactive = minInactivePixels < 0 ? icpCountThresh : minInactivePixels;
+    }
+    localSt = LocalLoopStats{};   // (deforms and lastDeformTime with it: switching it on starts a new history)
+}
+
+// CoFusion.cpp:386-461 at the end of the frame (the placement of the fern seam): everything up to the constraint launch
+// is enqueued unconditionally behind the end-of-frame prediction, and the host waits once, on that launch's record.
+void CoFusion::localLoopAfterPredict()
+{
+    if (lost || fernClosedThisFrame || !curRgba) return;
+    if (tick - cfg.timeDelta < 1) return;   // (surfel times start at 1: no surfel can be inactive yet, exactly)
+    Model& g = *globalModel;
+    cf_model* m = g.handle();
+    const Mat4f pose = g.getPose();
+    check(ctx, cf_model_predict_inactive(m, pose.m, maxDepthProcessed, g.getConfidenceThreshold(), tick - cfg.timeDelta, cfg.timeDelta), "cf_model_predict_inactive");
+    const float* splatV = static_cast<const float*>(mbuf(ctx, m, 5));
+    const float* splatN = static_cast<const float*>(mbuf(ctx, m, 6));
+    check(ctx, cf_odom_init_icp_model(modelToModel, static_cast<const float*>(mbuf(ctx, m, 16)), static_cast<const float*>(mbuf(ctx, m, 17)), pose.m), "cf_odom_init_icp_model");
+    check(ctx, cf_odom_init_rgb_model(modelToModel, static_cast<const uint8_t*>(mbuf(ctx, m, 15))), "cf_odom_init_rgb_model");
+    check(ctx, cf_odom_init_icp_maps(modelToModel, splatV, splatN), "cf_odom_init_icp_maps");
+    check(ctx, cf_odom_init_rgb(modelToModel, static_cast<const uint8_t*>(mbuf(ctx, m, 4))), "cf_odom_init_rgb");
+    cf_track_opts opts{};   // CoFusion.cpp:405
+    opts.rgb_only = 0; opts.icp_weight = 10.0f; opts.pyramid = cfg.pyramid; opts.fast_odom = cfg.fastOdom; opts.so3 = 0;
+    const float* poses[1] = {pose.m};
+    cf_odom* ods[1] = {modelToModel};
+    check(ctx, cf_odom_track_batch_async(ctx, ods, 1, poses, &opts, nullptr), "cf_odom_track_batch_async");
+    const int pin = localSt.deforms == 0;
+    check(ctx, cf_local_loop_constraints_async(localLoop, modelToModel, nullptr, splatV, static_cast<const uint16_t*>(mbuf(ctx, m, 18)),
+                                               static_cast<const uint32_t*>(mbuf(ctx, m, 19)), pose.m, tick, maxDepthProcessed, pin, &localTh),
+          "cf_local_loop_constraints_async");
+    cf_local_loop_record rec{};
+    check(ctx, cf_local_loop_wait(localLoop, &rec), "cf_local_loop_wait");   // THE host wait of the local branch
+    // (nothing is enqueued behind the record's event: this finds the stream idle, checks the tracker's solve count and frees its state)
+    check(ctx, cf_odom_fetch_result(modelToModel, nullptr, nullptr, nullptr), "cf_odom_fetch_result");
+    localSt.examined++;
+    localSt.lastRecord = rec; localSt.lastCovered = rec.covered;
+    if (rec.covered < (uint32_t)localMinInactive) { localSt.skippedByGate++; return; }
+    if (!rec.accepted || rec.n_constraints < 1) return;
+    localSt.trackerAccepts++;
+    localSt.lastConstraints = rec.n_constraints; localSt.lastPinned = pin; localSt.lastTick = tick;
+    float *src = nullptr, *dst = nullptr, *time = nullptr;
+    check(ctx, cf_local_loop_constraint_buffers(localLoop, &src, &dst, &time), "cf_local_loop_constraint_buffers");
+    Mat4f est;
+    for (int i = 0; i < 16; i++) est.m[i] = rec.est_pose[i];
+    int keyframes = 0, full = 0;
+    if (ferns) check(ctx, cf_ferns_count(ferns, &keyframes, &full), "cf_ferns_count");
+    cf_deform_result dr{};
+    localSt.lastNodes = deformMap(localDeform, localSampleRate, [&] { return cf_deform_weights_device(localDeform, src, dst, time, rec.n_constraints); },
+                                  0, &est, keyframes, localSt.lastDeformTime, &dr);
+    localSt.last = dr;
+    localSt.optimised += dr.optimised; localSt.accepted += dr.accepted; localSt.failed += dr.failed;
+    if (!dr.accepted) return;
+    localSt.deforms++;
+    localSt.lastDeformTime = tick;
 }
 
 // The first index maps of the surfel chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) enqueued BEHIND the

@@ -374,6 +374,29 @@ class CoFusion {
         cf_deform_result last{};
     };
     const LoopStats& loopStats() const { return loopSt; }
+    // Local (model-to-model) loop closure (CoFusion.cpp:386-461, which the reference stubs; ElasticFusion's, DESIGN.md 4.14 "The local
+    // half").  Off by default; with it off the frame loop is what it was, launch for launch.  On: a tracked frame in which the fern seam
+    // closed no loop predicts the INACTIVE part of the background map behind the end-of-frame prediction, registers the ACTIVE
+    // prediction onto it with a second tracker and runs the constraint launch, all enqueued unconditionally, then waits ONCE, on the
+    // constraint launch's record, which also carries the covered-texel count.  Fewer covered texels than minInactivePixels (< 0: the
+    // default, icpCountThresh; 0: the reference, no gate): nothing more.  An accepted registration samples a second, sized graph at
+    // sampleRate, weights the constraints on the device, optimises in the local mode (lastDeformTime), and an accepted graph moves the
+    // map with the reactivation stamp read from the depth synthesized at the estimated pose, moves the keyframe poses if there is a
+    // database, overrides the camera pose and redoes the prediction.  Needs Config::timeDelta > 0 (an inactive map); single process,
+    // not a sequence of a lock-step group.  Needs no fern database.
+    void setLocalLoopClosure(bool on, int sampleRate = 5000, int icpCountThresh = 40000, float icpErrThresh = 5e-5f, float covThresh = 1e-5f,
+                             int minInactivePixels = -1);
+    struct LocalLoopStats {
+        int examined = 0, skippedByGate = 0, trackerAccepts = 0;   // frames examined, stopped by the pixel gate, accept rule passed with >= 1 constraint
+        int optimised = 0, accepted = 0, failed = 0;               // graphs
+        int lastNodes = 0, lastConstraints = 0;                    // of the last tracker accept (constraint rows, pins included)
+        int lastPinned = 0, lastTick = -1;                         // ... whether its rows carried pins, the frame's tick
+        int deforms = 0, lastDeformTime = 0;
+        uint32_t lastCovered = 0;                                  // covered inactive texels of the last examined frame
+        cf_deform_result last{};
+        cf_local_loop_record lastRecord{};                         // of the last examined frame
+    };
+    const LocalLoopStats& localLoopStats() const { return localSt; }
     bool isGroupSequence() const { return !ownsCtx; }
     // Loop closure of the background map from caller-supplied constraints: sample the deformation graph, weight the
     // constraint points, optimise, and on acceptance move the map (cf_deform_*) and redo the prediction.  Returns the node count.
@@ -488,7 +511,22 @@ class CoFusion {
     bool closeLoop(const cf_ferns_gate& gate);
     // the body deformBackground and closeLoop share: sample, weigh (the caller's upload), optimise, and on acceptance the map pass with
     // the reactivation stamp (at *correctedPose when given, which becomes the camera pose), the keyframe poses and the prediction
-    int deformMap(int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes, cf_deform_result* result);
+    // graph: the object that is sampled; lastDeformTime < 0: the global mode (cf_deform_optimise), >= 0: the local mode, whose stamp reads
+    // the depth synthesized from the un-deformed map at the corrected pose instead of the frame's
+    int deformMap(cf_deform* graph, int sampleRate, const std::function<int()>& weigh, int clockAhead, const Mat4f* correctedPose, int keyframes,
+                  int lastDeformTime, cf_deform_result* result);
+    // setLocalLoopClosure
+    bool closeLocalLoops = false;
+    int localSampleRate = 5000, localMinInactive = 40000;
+    cf_local_loop_thresholds localTh{1e-5f, 40000, 5e-5f};
+    cf_local_loop* localLoop = nullptr;
+    cf_deform* localDeform = nullptr;    // the sized graph (CF_DEFORM_MAX_CONSTRAINTS_SIZED)
+    cf_odom* modelToModel = nullptr;     // CoFusion::modelToModel
+    float* localDepth = nullptr;         // device f32 [H * W]: the synthesized depth of an accepted closure
+    LocalLoopStats localSt;
+    bool fernClosedThisFrame = false;
+    void localLoopAfterPredict();
+    void releaseLocalLoop();
     // device frame buffers (CoFusion::textures)
     // filtered depth + its pyramid are double buffered: the filter of frame t+1 runs on an auxiliary stream while the fusion
     // passes of frame t still read frame t's filtered depth (processFrame)

@@ -191,6 +191,32 @@ int cofusion_loop_stats(cofusion_handle* h, cofusion_loop_stats_t* out)
     return 0;
 }
 
+int cofusion_set_local_loop_closure(cofusion_handle* h, int on, int sample_rate, int icp_count_thresh, float icp_err_thresh, float cov_thresh,
+                                    int min_inactive_pixels)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->borrowed) { g_err = "local loop closure is not available for a sequence of a lock-step group"; return -1; }
+    GUARD(h->cf->setLocalLoopClosure(on != 0, sample_rate > 0 ? sample_rate : 5000, icp_count_thresh >= 0 ? icp_count_thresh : 40000,
+                                     icp_err_thresh > 0 ? icp_err_thresh : 5e-5f, cov_thresh > 0 ? cov_thresh : 1e-5f, min_inactive_pixels));
+    return 0;
+}
+int cofusion_local_loop_stats(cofusion_handle* h, cofusion_local_loop_stats_t* out)
+{
+    if (!h || !out) { g_err = "cofusion_local_loop_stats: bad arguments"; return -1; }
+    const CoFusion::LocalLoopStats& s = h->cf->localLoopStats();
+    *out = cofusion_local_loop_stats_t{};
+    out->examined = s.examined; out->skipped_by_gate = s.skippedByGate; out->tracker_accepts = s.trackerAccepts;
+    out->optimised = s.optimised; out->accepted = s.accepted; out->failed = s.failed;
+    out->last_nodes = s.lastNodes; out->last_constraints = s.lastConstraints; out->last_pinned = s.lastPinned; out->last_tick = s.lastTick;
+    out->deforms = s.deforms; out->last_deform_time = s.lastDeformTime; out->last_covered = s.lastCovered;
+    out->last_tracker_accepted = s.lastRecord.accepted; out->last_icp_error = s.lastRecord.icp_error; out->last_icp_count = s.lastRecord.icp_count;
+    out->last_max_covariance = s.lastRecord.max_covariance;
+    memcpy(out->last_est_pose, s.lastRecord.est_pose, sizeof(out->last_est_pose));
+    static_assert(sizeof(s.last) == sizeof(out->last_result), "cf_deform_result is 8 words");
+    memcpy(out->last_result, &s.last, sizeof(out->last_result));
+    return 0;
+}
+
 static Model* model_at(cofusion_handle* h, int index)
 {
     auto& l = h->cf->getModels();

@@ -22,10 +22,10 @@ SYMBOLS = [
     "cf_transform_maps", "cf_vertices_to_depth", "cf_pyrdown_gauss_f32", "cf_pyrdown_gauss_u8",
     "cf_rgba_to_intensity", "cf_sobel", "cf_project_cloud", "cf_icp_step", "cf_icp_step_band", "cf_rgb_residual", "cf_rgb_step",
     "cf_so3_step", "cf_gn_solve_step", "cf_odom_create", "cf_odom_destroy", "cf_odom_init_icp_model", "cf_odom_init_rgb_model",
-    "cf_odom_init_rgb", "cf_odom_init_models_batch", "cf_odom_init_models_batch_frames", "cf_odom_init_models_batch_select", "cf_model_fill_ratio_device", "cf_odom_init_first_rgb", "cf_odom_init_icp", "cf_odom_get_incremental_transformation",
+    "cf_odom_init_rgb", "cf_odom_init_models_batch", "cf_odom_init_models_batch_frames", "cf_odom_init_models_batch_select", "cf_model_fill_ratio_device", "cf_odom_init_first_rgb", "cf_odom_init_icp", "cf_odom_init_icp_maps", "cf_odom_get_incremental_transformation",
     "cf_odom_track_batch_async", "cf_odom_fetch_result", "cf_odom_get_covariance", "cf_odom_bind_frame_maps", "cf_odom_share_frame_maps", "cf_odom_set_culling", "cf_odom_set_band", "cf_set_collective", "cf_model_predict_indices_sharded", "cf_odom_buffer",
     "cf_bilateral", "cf_model_create", "cf_model_destroy", "cf_model_initialise", "cf_model_count",
-    "cf_model_predict_indices", "cf_model_index_keys", "cf_model_index_resolve", "cf_model_combined_predict", "cf_model_prefetch_fill_ratio", "cf_model_perform_fill_in", "cf_model_requires_fill_in",
+    "cf_model_predict_indices", "cf_model_index_keys", "cf_model_index_resolve", "cf_model_combined_predict", "cf_model_predict_inactive", "cf_model_synthesize_depth", "cf_model_prefetch_fill_ratio", "cf_model_perform_fill_in", "cf_model_requires_fill_in",
     "cf_model_fuse", "cf_model_clean", "cf_models_frame_passes", "cf_models_preindex", "cf_model_download_map", "cf_model_upload_map", "cf_model_buffer",
     "cf_set_extent_culling", "cf_model_extents_unknown",
     "cf_redetect_score", "cf_redetect_timing", "cf_relabel",
@@ -41,7 +41,9 @@ SYMBOLS = [
     "cf_png_encoder_create", "cf_png_encoder_destroy", "cf_png_encoder_submit", "cf_png_encoder_acquire", "cf_png_encoder_timing",
     "cf_deform_create", "cf_deform_destroy", "cf_deform_default_thresholds", "cf_deform_sample", "cf_deform_set_nodes", "cf_deform_weights", "cf_deform_assemble",
     "cf_deform_iterate", "cf_deform_optimise", "cf_deform_apply", "cf_deform_apply_poses", "cf_deform_download", "cf_deform_weights_device",
+    "cf_deform_create_sized", "cf_deform_assemble_local", "cf_deform_iterate_local", "cf_deform_optimise_local",
     "cf_ferns_gate_async", "cf_ferns_gate_wait", "cf_ferns_constraints", "cf_ferns_find_frame", "cf_ferns_constraint_buffers", "cf_ferns_keyframe_buffers",
+    "cf_local_loop_create", "cf_local_loop_destroy", "cf_local_loop_constraints_async", "cf_local_loop_wait", "cf_local_loop_constraint_buffers",
 ]
 
 
@@ -66,7 +68,7 @@ HOST_SYMBOLS = [
     "cofusion_model_download", "cofusion_model_icp_stats", "cofusion_model_cull_box", "cofusion_model_level0_visited", "cofusion_model_tracking_inputs", "cofusion_mask_device", "cofusion_context", "cofusion_set_crf", "cofusion_set_seg_early",
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
-    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats", "cofusion_deform_background", "cofusion_set_loop_closure", "cofusion_loop_stats",
+    "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats", "cofusion_deform_background", "cofusion_set_loop_closure", "cofusion_loop_stats", "cofusion_set_local_loop_closure", "cofusion_local_loop_stats",
     "cofusion_set_redetection", "cofusion_redetect_stats", "cofusion_redetect_last", "cofusion_num_inactive_models",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",

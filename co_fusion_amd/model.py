@@ -65,7 +65,8 @@ def set_extent_culling(ctx: Context, on=True):
 
 
 _BUF = {0: (np.uint32, 1), 1: (np.float32, 4), 2: (np.float32, 4), 3: (np.float32, 4), 4: (np.uint8, 4), 5: (np.float32, 4),
-        6: (np.float32, 4), 7: (np.uint16, 1), 8: (np.float32, 4), 9: (np.float32, 4), 10: (np.uint8, 4)}
+        6: (np.float32, 4), 7: (np.uint16, 1), 8: (np.float32, 4), 9: (np.float32, 4), 10: (np.uint8, 4),
+        15: (np.uint8, 4), 16: (np.float32, 4), 17: (np.float32, 4), 18: (np.uint16, 1)}   # 15..18: the inactive prediction
 
 
 def bilateral(ctx: Context, depth, max_d):
@@ -126,6 +127,24 @@ class Model:
     def combined_predict(self, pose, max_depth, conf_threshold, time, max_time, time_delta=TIME_DELTA):
         self.ctx._check(self.ctx.lib.cf_model_combined_predict(self.h, self._pose(pose), C.c_float(max_depth), C.c_float(conf_threshold),
                                                                time, max_time, time_delta))
+
+    def predict_inactive(self, pose, max_depth, conf_threshold, max_time, time_delta):
+        """the INACTIVE prediction (buffers 15..18: image, vertexConf, normalRad, time) and its covered count (inactive_covered)"""
+        self.ctx._check(self.ctx.lib.cf_model_predict_inactive(self.h, self._pose(pose), C.c_float(max_depth), C.c_float(conf_threshold),
+                                                               int(max_time), int(time_delta)))
+
+    def inactive_covered(self):
+        """texels of the last inactive prediction with time > 0 (waits for the stream)"""
+        ptr, nbytes = self.tensor(19)
+        host = np.empty(1, np.uint32)
+        self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, host.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_uint64(nbytes)))
+        return int(host[0])
+
+    def synthesize_depth(self, pose, max_depth, conf_threshold, time, max_time, time_delta, out):
+        """ModelProjection::synthesizeDepth into `out`, a device tensor f32 [rows, cols]; enqueued"""
+        assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() == self.ctx.width * self.ctx.height
+        self.ctx._check(self.ctx.lib.cf_model_synthesize_depth(self.h, self._pose(pose), C.c_float(max_depth), C.c_float(conf_threshold),
+                                                               int(time), int(max_time), int(time_delta), _p(out)))
 
     def perform_fill_in(self, rgba, depth_filt, pass_geom=False, pass_rgb=False):
         self.ctx._check(self.ctx.lib.cf_model_perform_fill_in(self.h, _p(rgba), _p(depth_filt), int(pass_geom), int(pass_rgb)))

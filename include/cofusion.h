@@ -122,6 +122,37 @@ typedef struct {
     int32_t last_result[8];                         /* its cf_deform_result as cofusion_deform_background returns it */
 } cofusion_loop_stats_t;
 int cofusion_loop_stats(cofusion_handle *h, cofusion_loop_stats_t *out);
+/* Local (model-to-model) loop closure in the frame loop (DESIGN.md 4.14 "The local half"; CoFusion.cpp:386-461, ElasticFusion's): with it
+ * on, every tracked frame from tick time_delta + 1 on in which the fern seam closed no loop predicts the INACTIVE part of the background
+ * map (surfels not seen for time_delta ticks) from the current pose, registers the ACTIVE prediction onto it with a second tracker
+ * (rgb_only 0, icp_weight 10, so3 0) and runs one constraint launch behind it -- all enqueued unconditionally at the end of the frame --
+ * and waits ONCE, on that launch's record.  The cost is therefore a second Gauss-Newton loop and a drained queue in every such frame.
+ * Fewer covered inactive texels than min_inactive_pixels: nothing more (a stated departure; < 0: icp_count_thresh, 0: the reference's
+ * behaviour).  A registration that passes the accept rule (every covariance diagonal <= cov_thresh, ICP count > icp_count_thresh, ICP
+ * error < icp_err_thresh) and leaves >= 1 constraint deforms the map with a graph sampled at sample_rate in the graph's local mode (only
+ * nodes younger than the last deformation move); an accepted graph moves the map, reactivates the old surfels in view of the estimated
+ * pose (read from a depth image synthesized from the un-deformed map), moves the keyframe poses when there is a database, overrides the
+ * camera pose and redoes the prediction.  Pins are added while no local closure has been accepted yet.  Values <= 0 of sample_rate,
+ * icp_err_thresh, cov_thresh and < 0 of icp_count_thresh select the defaults 5000, 5e-5, 1e-5, 40000.  Needs time_delta > 0 and
+ * (width / 20) * (height / 20) <= 768; needs no fern database; world == 1; refused for a sequence handle of a lock-step group.  Calling
+ * it resets the statistics, deforms and last_deform_time included.  Off (the default): the frame loop is unchanged.  Not built: relative
+ * constraints, the pose graph, object models. */
+int cofusion_set_local_loop_closure(cofusion_handle *h, int on, int sample_rate, int icp_count_thresh, float icp_err_thresh, float cov_thresh,
+                                    int min_inactive_pixels);
+typedef struct {
+    int32_t examined, skipped_by_gate, tracker_accepts;   /* frames examined, stopped by the pixel gate, accept rule passed with >= 1 constraint */
+    int32_t optimised, accepted, failed;                  /* deformation graphs */
+    int32_t last_nodes, last_constraints, last_pinned, last_tick;   /* of the last tracker accept: graph nodes, constraint rows (pins included),
+                                                                      * whether they carried pins, the frame's tick (-1: none) */
+    int32_t deforms, last_deform_time;                    /* accepted local closures, the tick of the last one (0: none) */
+    uint32_t last_covered;                                /* covered inactive texels of the last examined frame */
+    int32_t last_tracker_accepted;                        /* the accept rule in the last examined frame, and its three figures: */
+    float last_icp_error, last_icp_count;
+    double last_max_covariance;
+    float last_est_pose[16];                              /* the second tracker's pose in the last examined frame, row-major */
+    int32_t last_result[8];                               /* cf_deform_result of the last optimised graph */
+} cofusion_local_loop_stats_t;                            /* 168 bytes */
+int cofusion_local_loop_stats(cofusion_handle *h, cofusion_local_loop_stats_t *out);
 /* Re-detection of inactive object models (the reference's CoFusion::redetectModels is an empty hook, CoFusion.cpp:599-602).
  * A model whose label gets no superpixels is deactivated; kept models (surfel count >= keep_min_surfels and confidence threshold >
  * keep_conf_threshold -- 4000 / 0.3, the reference's rule) wait in a list.  Off (the default) nothing reads that list: an object that

@@ -350,6 +350,12 @@ int cf_odom_share_frame_maps(cf_odom *od, cf_odom *owner);
  *   16  aabb           six u32 order-preserving keys, level must be 0: bounding frustum of the prediction (x0, y0, z0 complemented,
  *                      x1, y1, z1; all zero = empty or culling off); latched and zeroed by the next tracking call */
 int cf_odom_buffer(cf_odom *od, int which, int level, void **dptr, uint64_t *bytes);
+/* initICP(predictedVertices, predictedNormals, cutoff), RGBDOdometry.cpp:120-141: the frame side of a model-to-model tracker from
+ * device maps (f32x4 [rows * cols] each, e.g. the ACTIVE splat vertexConf / normalRad) instead of a depth pyramid: copyMaps into level
+ * 0, resizeVMap / resizeNMap down the pyramid.  The vertices also become what the next cf_odom_init_rgb derives nextDepth from, so in
+ * the reference's order (init_icp_model, init_rgb_model, init_icp_maps, init_rgb) nextDepth is the frame side's own depth, not the
+ * model's.  A later cf_odom_init_icp replaces the frame side as before. */
+int cf_odom_init_icp_maps(cf_odom *od, const float *vertex4, const float *normal4);
 /* Model::generateCUDATextures depth half (Model.cpp:341-343): l1/l2 device outputs */
 int cf_depth_pyramid(cf_ctx *ctx, const float *depth_filtered, int cols, int rows, float *l1, float *l2);
 
@@ -380,6 +386,15 @@ int cf_model_predict_indices_sharded(cf_model *m, const float pose[16], int time
 /* Model::combinedPredict -> ModelProjection::combinedPredict (ModelProjection.cpp:192-273), ACTIVE prediction */
 int cf_model_combined_predict(cf_model *m, const float pose[16], float maxDepth, float confThreshold, int time, int maxTime,
                               int timeDelta);
+/* The INACTIVE prediction of local loop closure (ModelProjection::combinedPredict(..., INACTIVE) as CoFusion.cpp:390 calls it: time = 0,
+ * maxTime = tick - timeDelta) into a second target set, the reference's oldFrameBuffer (cf_model_buffer 15..18, allocated by the first
+ * call); the ACTIVE targets are not touched.  The resolve also leaves the number of covered texels (time > 0) in a device word
+ * (cf_model_buffer 19).  Enqueued only. */
+int cf_model_predict_inactive(cf_model *m, const float pose[16], float maxDepth, float confThreshold, int maxTime, int timeDelta);
+/* ModelProjection::synthesizeDepth (splat.vert + depth_splat.frag: the acceptance rule of the colour splat, one output): corrected_pos.z
+ * per texel into depth_out_dev (device, f32 [rows * cols]), 0 where nothing lands.  No other buffer of the model is written.  Enqueued only. */
+int cf_model_synthesize_depth(cf_model *m, const float pose[16], float maxDepth, float confThreshold, int time, int maxTime, int timeDelta,
+                              float *depth_out_dev);
 /* optional: count the covered pixels of the latest splat prediction now and read them back asynchronously, so that the
  * next cf_model_requires_fill_in does not wait (call it after the frame's last cf_model_combined_predict) */
 int cf_model_prefetch_fill_ratio(cf_model *m);
@@ -931,12 +946,17 @@ int cf_profile_read(cf_ctx *ctx, cf_profile *out, int reset);
 
 /* ------------------------------------------------------------- loop closure: deformation graph ---- */
 /* ElasticFusion's deformation graph (Core/Model/Deformation.*, Core/Utils/DeformationGraph.*, the node branch of copy_unstable.vert),
- * device resident: global closure of ONE surfel map from absolute constraints (DESIGN.md 4.14 states every rule and every order of
- * operations; tests/deform_ref.py restates them in numpy).  Everything is allocated at creation, for CF_DEFORM_MAX_NODES nodes and
- * CF_DEFORM_MAX_CONSTRAINTS constraints (pins included): about 24 MB, nearly all of it the band of the normal matrix.  The calls are
- * rare and synchronous (each waits for the context's stream) except cf_deform_apply and cf_deform_apply_poses, which only enqueue. */
+ * device resident: closure of ONE surfel map from absolute constraints, in the global mode (a fern match: every node is free) and in
+ * the graph's local mode (the *_local calls: only the nodes younger than the last deformation are free).  DESIGN.md 4.14 states every
+ * rule and every order of operations; tests/deform_ref.py and tests/local_loop_ref.py restate them in numpy.  Everything is allocated at
+ * creation, for CF_DEFORM_MAX_NODES nodes and CF_DEFORM_MAX_CONSTRAINTS constraints (pins included; cf_deform_create_sized: up to
+ * CF_DEFORM_MAX_CONSTRAINTS_SIZED): about 24 MB, nearly all of it the band of the normal matrix.  The calls are rare and synchronous
+ * (each waits for the context's stream) except cf_deform_apply and cf_deform_apply_poses, which only enqueue.  The constraints of a local
+ * closure come from cf_local_loop_* (cofusion_loop.h) behind the model-to-model tracker (cf_odom_init_icp_maps); the frame loop that strings
+ * them together is CoFusion::setLocalLoopClosure.  Not built: relative constraints, the pose graph, object models. */
 #define CF_DEFORM_MAX_NODES 1024
 #define CF_DEFORM_MAX_CONSTRAINTS 128
+#define CF_DEFORM_MAX_CONSTRAINTS_SIZED 1536   /* a local closure at 640x480: 768 constraints and 768 pins */
 #define CF_DEFORM_BAND 240          /* band entries per row of A, diagonal included: A_band[i][d] = A[i][i - d] */
 typedef struct cf_deform cf_deform;
 typedef struct {                    /* the reference's figures: 0.06, 3, 1e-2, 1e-3, 1e-5, 10, 3e-4, 0.12 */
@@ -956,6 +976,8 @@ typedef struct {                    /* the reactivation stamp of cf_deform_apply
     int tick;
 } cf_deform_reactivate;
 int cf_deform_create(cf_ctx *ctx, cf_deform **out);
+/* the same object with room for max_constraints (1 .. CF_DEFORM_MAX_CONSTRAINTS_SIZED) constraints; every call takes either kind */
+int cf_deform_create_sized(cf_ctx *ctx, int max_constraints, cf_deform **out);
 void cf_deform_destroy(cf_deform *d);
 void cf_deform_default_thresholds(cf_deform_thresholds *out);
 /* every surfel of map_dev (device, `count` records of 12 f32) whose index is a multiple of stride becomes a node; stride = the smallest
@@ -974,7 +996,21 @@ int cf_deform_assemble(cf_deform *d);
 int cf_deform_iterate(cf_deform *d, cf_deform_step *out);
 /* optimiseGraphSparse (fernMatch) from the current parameters + the acceptance of Deformation::constrain; th NULL: the defaults */
 int cf_deform_optimise(cf_deform *d, const cf_deform_thresholds *th, cf_deform_result *out);
-/* the map pass over map_dev in place; re NULL: no reactivation stamp.  Enqueued only. */
+/* The local mode (lastDeformTime, DeformationGraph.cpp:401-410): node i is enabled iff int(time_i) > last_deform_time.  A disabled
+ * node's 12 unknowns leave the system (its blocks of A_band are zero, its diagonal block the identity, its part of b zero: delta = 0
+ * there); the rotation rows of a disabled node, an edge between two disabled nodes and a constraint none of whose four nodes is
+ * enabled are dropped from J and from `error`; mean_cons_error stays the mean over all constraints.  With every node enabled the
+ * three calls compute what cf_deform_assemble / cf_deform_iterate compute, bit for bit. */
+int cf_deform_assemble_local(cf_deform *d, int last_deform_time);
+int cf_deform_iterate_local(cf_deform *d, int last_deform_time, cf_deform_step *out);
+/* optimiseGraphSparse (fernMatch = false) + the acceptance of Deformation::constrain for it: no min_cons_error gate, no
+ * max_first_error stop (both fields of th are ignored), the other stop rules as in cf_deform_optimise; accepted = 1 unless a step
+ * failed on a pivot <= 0 (failed = 1) or no node is enabled (optimised = 0).  Those two leave the parameters as they were at the call. */
+int cf_deform_optimise_local(cf_deform *d, int last_deform_time, const cf_deform_thresholds *th, cf_deform_result *out);
+/* the map pass over map_dev in place; re NULL: no reactivation stamp.  Enqueued only.  When the parameters were left by
+ * cf_deform_optimise_local (no cf_deform_sample / cf_deform_set_nodes / cf_deform_optimise since), a surfel none of whose four nodes is
+ * enabled keeps position and normal bit for bit (a stated departure: the identity of its nodes would still round (p - g) + g); the
+ * stamp is applied to it as to every other. */
 int cf_deform_apply(cf_deform *d, float *map_dev, uint32_t count, const cf_deform_reactivate *re);
 /* applyGraphToPoses over device arrays: poses [n][16] row-major, times [n].  Enqueued only. */
 int cf_deform_apply_poses(cf_deform *d, float *poses_dev, const int32_t *times_dev, int n);

@@ -57,4 +57,43 @@ int cf_ferns_constraint_buffers(cf_ferns *f, float **src, float **dst, float **t
 /* the database's pose [capacity][16] and srcTime [capacity] arrays on the device, for cf_deform_apply_poses */
 int cf_ferns_keyframe_buffers(cf_ferns *f, float **poses, int32_t **times);
 
+/* ---- local (model-to-model) loop closure: the constraint stage (csrc/local_loop.hip, DESIGN.md 4.14 "The local half") ---- */
+typedef struct cf_local_loop cf_local_loop;
+typedef struct { float cov_thresh; int32_t icp_count_thresh; float icp_err_thresh; } cf_local_loop_thresholds;   /* 1e-5, 40000, 5e-5 */
+typedef struct {             /* a tracker result handed in from the host instead of a cf_odom (tests) */
+    float rot[9], trans[3];  /* the estimated pose, rotation row-major */
+    float icp_error, icp_count;
+    double lastA[36];
+} cf_local_loop_track;
+typedef struct {
+    int32_t accepted;        /* every diagonal entry of inverse(lastA) <= cov_thresh (a NaN rejects) && icp_count > icp_count_thresh &&
+                              * icp_error < icp_err_thresh */
+    int32_t n_constraints;   /* rows written to the constraint buffers, pins included (0 when rejected) */
+    double max_covariance;   /* the largest diagonal entry (a NaN if there is one) */
+    float icp_error, icp_count;
+    float est_pose[16];      /* the tracker's pose, row-major */
+    uint32_t covered;        /* the word covered_dev points at when the kernel ran (0 without one) */
+    uint32_t serial;         /* written last, behind a system fence */
+} cf_local_loop_record;      /* 96 bytes */
+/* (width / 20) * (height / 20) must lie in 1..768: one workgroup takes one sample per thread, and with pins the rows fill a graph object
+ * of CF_DEFORM_MAX_CONSTRAINTS_SIZED */
+int cf_local_loop_create(cf_ctx *ctx, cf_local_loop **out);
+void cf_local_loop_destroy(cf_local_loop *l);
+/* ONE launch of one workgroup on the context's MAIN stream -- the one the tracker's calls enqueue on, also from a thread bound to a lane
+ * (cf_thread_lane): the maps handed in must have been written on that stream or be complete -- and an event behind it.  The tracker's result is read in device memory: from
+ * `od` (its last tracking call, enqueued on the same stream) or, with od NULL, from `track` (copied up; test access); exactly one of
+ * the two.  vertex_conf_dev: f32x4 [rows * cols], the ACTIVE splat vertexConf; old_time_dev: u16 [rows * cols], the inactive
+ * prediction's time; covered_dev: nullable.  Accept rule: above.  Accepted: both maps are sampled at texel (20 x + 10, 20 y + 10),
+ * x < cols / 20, y < rows / 20, visited column by column (x outer); a sample is valid when z > 0 && z < max_depth && old time > 0; row
+ * k of the valid samples in that order is src = curr_pose * p, dst = est_pose * p (each coordinate ((m0 x + m1 y) + m2 z) + m3 in f32),
+ * time = tick; with pin != 0 rows are interleaved as (constraint, pin): row 2k as before, row 2k + 1 = (dst, dst, the old time).  The
+ * layout is the one cf_deform_weights_device reads. */
+int cf_local_loop_constraints_async(cf_local_loop *l, const cf_odom *od, const cf_local_loop_track *track, const float *vertex_conf_dev,
+                                    const uint16_t *old_time_dev, const uint32_t *covered_dev, const float curr_pose[16], int tick,
+                                    float max_depth, int pin, const cf_local_loop_thresholds *th);
+/* waits for THAT event (not for the stream) and copies the record out */
+int cf_local_loop_wait(cf_local_loop *l, cf_local_loop_record *out);
+/* device arrays the kernel writes: src, dst f32 [1536][3], time f32 [1536] */
+int cf_local_loop_constraint_buffers(cf_local_loop *l, float **src, float **dst, float **time);
+
 #endif /* COFUSION_LOOP_H_ */

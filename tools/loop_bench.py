@@ -16,7 +16,15 @@ bench.py's objects4 workload with loop closure on against relocalisation alone a
 process; the price of the per-frame wait in microseconds beside the relocalisation leg's own spread), and the wall time of the frame
 that closes the loop in the scenario of tests/test_loop_closure_gpu.py.
 
+With --local, the built legs of local loop closure, merged into the same file under "local" (medians of 20 by in-stream events): the
+inactive prediction and the depth synthesis of a 640x480 map of 307 200 surfels, and assemble / iterate of a graph object sized for 1536
+constraints at 768 + 768 constraints for 40 / 200 / 1024 nodes, beside the same object's and the 128-capacity object's figures at 100
+constraints; the model-to-model tracker (preparation through cf_odom_init_icp_maps + the Gauss-Newton loop) on two views of the room of
+the smoke test at 640x480, and the constraint launch + the wait on its record.  (The frame loop is not built: no closing frame, no
+objects4 leg.)
+
     python tools/loop_bench.py [--iters 30] [--no-frames]
+    python tools/loop_bench.py --local
     python tools/loop_bench.py --seam [--steps 300] [--warmup 30] [--rounds 3] [--min-age 30]
 """
 import argparse
@@ -85,6 +93,159 @@ def stages(torch, iters):
             apply[f"{n}_nodes_{s}_surfels"] = dict(ms=ms, bytes=80 * s, share_of_peak=80 * s / (ms * 1e-3) / PEAK_BPS)
     d.close(); ctx.close()
     return dict(stages=out, apply=apply)
+
+
+def local_legs(torch, iters=20):
+    import deform_cases as dc
+    import local_loop_cases as lc
+    from co_fusion_amd import api, deform, model as M
+    ctx = api.Context(640, 480, 528.0, 528.0, 320.0, 240.0, max_models=2, max_surfels=1 << 19)
+    out = {}
+    # a wall of one surfel per texel, every second one inactive
+    rng = np.random.default_rng(5)
+    wall = lc.layer(rng, 640, 480, 2.0, np.where(np.arange(640 * 480) % 2 == 0, 50, 130), -1.2, 1.2, -0.9, 0.9, radius=0.004)
+    m = M.Model(ctx, 1 << 19)
+    m.upload_map(wall)
+    pose = np.eye(4, dtype=np.float32)
+    depth = ctx.empty((480, 640))
+    m.combined_predict(pose, 20.0, 10.0, 140, 140, 40)
+    out["active_prediction_ms"] = median_ms(torch, lambda: m.combined_predict(pose, 20.0, 10.0, 140, 140, 40), iters)
+    out["inactive_prediction_ms"] = median_ms(torch, lambda: m.predict_inactive(pose, 20.0, 10.0, 100, 40), iters)
+    out["inactive_covered"] = m.inactive_covered()
+    out["depth_synthesis_ms"] = median_ms(torch, lambda: m.synthesize_depth(pose, 20.0, 10.0, 140, 100, 65535, depth), iters)
+    out["surfels"] = int(len(wall))
+    m.close()
+    out.update(local_tracker(torch, ctx, iters))
+    small, big = deform.Deform(ctx), deform.Deform(ctx, deform.MAX_CONSTRAINTS_SIZED)
+    graph = {}
+    for n in (40, 200, 1024):
+        nodes = dc.make_nodes(n)
+        row = {}
+        for name, d, cons, ldt in (("100_cap128", small, dc.constraints("shift", nodes), None), ("100_cap1536", big, dc.constraints("shift", nodes), None),
+                                   ("1536_cap1536", big, lc.big_constraints(nodes), 0)):
+            src, dst, tm = cons
+            d.set_nodes(nodes)
+            row[name + "_weights_ms"] = median_ms(torch, lambda: d.weights(src, dst, tm), iters)
+            row[name + "_assemble_ms"] = median_ms(torch, lambda: d.assemble(ldt), iters)
+            reset = lambda: d.set_nodes(nodes) or d.weights(src, dst, tm)
+            row[name + "_iterate_ms"] = median_ms(torch, lambda: d.iterate(ldt), iters, before=reset)
+        graph[str(n)] = row
+    out["graph"] = graph
+    small.close(); big.close(); ctx.close()
+    return out
+
+
+def local_scenario(torch):
+    """wall time of the frames of tests/test_local_loop_closure_gpu.py up to its first closure, by what the local branch did in them"""
+    import local_loop_scene as sc
+    import test_local_loop_closure_gpu as t
+    from co_fusion_amd import facade
+    views = sc.make_views()
+    cf = facade.CoFusion(**t.KW)
+    try:
+        cf.set_local_loop_closure(True, sample_rate=sc.RATE)
+        rows = []
+        for k in range(t.MAX_FRAMES):
+            d, rgb = views(k)
+            before = cf.local_loop_stats()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            cf.process_frame(d, rgb, timestamp=k, in_pose=sc.yaw_pose(sc.DRIFT * sc.TURN_DEG * k))
+            torch.cuda.synchronize(); ms = (time.perf_counter() - t0) * 1e3
+            after = cf.local_loop_stats()
+            kind = ("closing" if after["deforms"] > before["deforms"] else "skipped_by_gate" if after["skipped_by_gate"] > before["skipped_by_gate"] else
+                    "tracker_rejected" if after["examined"] > before["examined"] else "not_examined")
+            rows.append((kind, ms))
+            if kind == "closing":
+                break
+        out = {k: dict(frames=sum(1 for a, _ in rows if a == k), median_wall_ms=float(np.median([m for a, m in rows if a == k])))
+               for k in ("not_examined", "skipped_by_gate", "tracker_rejected", "closing") if any(a == k for a, _ in rows)}
+        st = cf.local_loop_stats(); st["last_est_pose"] = st["last_est_pose"].tolist()
+        out["stats"] = st; out["surfels"] = cf.model_info(0)["count"]
+        return out
+    finally:
+        cf.close()
+
+
+def local_objects4(torch, steps, warmup, rounds):
+    """frames/s of bench.py's objects4 workload in ONE process, the legs alternated `rounds` times: with the relocalisation switch and a
+    time_delta of 100 ticks, and with local loop closure on top (every measured frame examined: the pre-roll and the warm-up are longer
+    than time_delta)"""
+    import bench
+    from co_fusion_amd import facade
+    wl = bench.WORKLOADS["objects4"]
+    W, H = wl["size"]
+    n_frames, n_obj = 16, wl["n_obj"]
+    cam, fr = bench.make_stream(W, H, n_frames, n_obj=n_obj, seed=1234)
+    dev = torch.device("cuda", 0)
+    resident = [dict(depth=torch.from_numpy(f["depth"]).to(dev), rgba=torch.from_numpy(f["rgba"]).to(dev)) for f in fr]
+    P = 24 * n_obj + 30
+    legs = (("relocalisation_on", False), ("local_loop_closure_on", True))
+    out = {name: dict(frames_per_s=[]) for name, _ in legs}
+    for _ in range(rounds):
+        for name, local in legs:
+            cf = facade.CoFusion(W, H, cam.fx, cam.fy, cam.cx, cam.cy, enable_multiple_models=1, device_frames_complete=1, reloc=1, time_delta=100)
+            cf.set_relocalisation(True, min_age=30)
+            if local:
+                cf.set_local_loop_closure(True)
+            for i in range(P):   # the pre-roll of bench.py: ground-truth masks until the object models exist
+                f = fr[bench.frame_index(i, n_frames)]
+                cf.process_frame(f["depth"], f["rgb"], mask=(f["label"] * 40).astype(np.uint8), timestamp=i)
+            def run(lo, hi):
+                for i in range(lo, hi):
+                    r = resident[bench.frame_index(i, n_frames)]
+                    cf.process_frame_device(r["depth"], r["rgba"], timestamp=i)
+            run(P, P + warmup)
+            torch.cuda.synchronize()
+            e0 = cf.local_loop_stats()["examined"]
+            t0 = time.perf_counter()
+            run(P + warmup, P + warmup + steps)
+            torch.cuda.synchronize()
+            out[name]["frames_per_s"].append(round(steps / (time.perf_counter() - t0), 1))
+            if local:
+                st = cf.local_loop_stats(); st["last_est_pose"] = st["last_est_pose"].tolist()
+                out[name]["stats"] = st; out[name]["examined_in_measured_frames"] = st["examined"] - e0
+            cf.close()
+    med = {k: float(np.median(v["frames_per_s"])) for k, v in out.items()}
+    out["per_frame_price_us_vs_relocalisation_on"] = round((1.0 / med["local_loop_closure_on"] - 1.0 / med["relocalisation_on"]) * 1e6, 1)
+    out["relocalisation_on_spread_us"] = round((1.0 / min(out["relocalisation_on"]["frames_per_s"]) - 1.0 / max(out["relocalisation_on"]["frames_per_s"])) * 1e6, 1)
+    return out
+
+
+def local_tracker(torch, ctx, iters):
+    """the model-to-model tracker in the reference's call order, and the constraint launch behind it with the wait on its record"""
+    import common
+    from co_fusion_amd import api, local_loop, synth
+    fp = common.frame_pair(640, 480, noise=True)
+    v4b, n4b, imgb = synth.ideal_prediction(fp["cam"], fp["d1"], fp["rgb1"])
+    cam = fp["cam"]
+    c2 = api.Context(640, 480, cam.fx, cam.fy, cam.cx, cam.cy)
+    g, l = api.Odometry(c2), local_loop.LocalLoop(c2)
+    d = c2.to_device
+    pose = common.perturbed_pose(2)
+    dev = dict(v4=d(fp["v4"]), n4=d(fp["n4"]), img=d(fp["img"]), v4b=d(np.float32(v4b)), n4b=d(np.float32(n4b)), imgb=d(imgb))
+    old_time = d(np.full((480, 640), 7, np.uint16))
+
+    def prepare():
+        g.init_icp_model(dev["v4"], dev["n4"], pose)
+        g.init_rgb_model(dev["img"])
+        g.init_icp_maps(dev["v4b"], dev["n4b"])
+        g.init_rgb(dev["imgb"])
+
+    def track():
+        prepare()
+        return g.track(pose[:3, 3], pose[:3, :3], rgb_only=False, icp_weight=10.0, pyramid=True, fast_odom=False, so3=False)
+
+    def constraints():
+        l.constraints_async(dev["v4b"], old_time, pose, 9, 20.0, True, odom=g, cov_thresh=1.0, icp_count_thresh=1000, icp_err_thresh=1.0)
+        return l.wait()
+
+    out = dict(tracker_preparation_ms=median_ms(torch, prepare, iters), tracker_preparation_and_loop_ms=median_ms(torch, track, iters))
+    track()
+    out["constraints_launch_and_wait_ms"] = median_ms(torch, constraints, iters)
+    rec = constraints()
+    out["constraints"] = dict(accepted=rec["accepted"], n_constraints=rec["n_constraints"])
+    l.close(); g.close(); c2.close()
+    return out
 
 
 def frames(torch):
@@ -229,6 +390,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--no-frames", action="store_true")
     ap.add_argument("--seam", action="store_true", help="only the legs of the fern seam (written to the 'seam' entry of profiles/loop_bench.json)")
+    ap.add_argument("--local", action="store_true", help="only the legs of local loop closure (the 'local' entry of profiles/loop_bench.json)")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
@@ -236,6 +398,16 @@ def main():
     a = ap.parse_args()
     import torch
     path = os.path.join(ROOT, "profiles", "loop_bench.json")
+    if a.local:
+        out = json.load(open(path)) if os.path.exists(path) else {}
+        out["local"] = local_legs(torch)
+        out["local"]["scenario"] = local_scenario(torch)
+        if not a.no_frames:
+            out["local"]["objects4"] = local_objects4(torch, a.steps, a.warmup, a.rounds)
+        print(json.dumps(out["local"]))
+        with open(path, "w") as f:
+            f.write(json.dumps(out) + "\n")
+        return
     if a.seam:
         out = json.load(open(path)) if os.path.exists(path) else {}
         out["seam"] = dict(kernels=seam_kernels(torch, a.iters), scenario=seam_scenario(torch))

@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--close-loops", action="store_true", help="global loop closure: a view that returns with drift corrects the background map "
                                                                 "(implies --relocalise)")
     ap.add_argument("--loop-sample-rate", type=int, default=25000, help="every N-th surfel of the background map is a node of the deformation graph")
+    ap.add_argument("--close-local-loops", action="store_true", help="local loop closure: the active view of the background map is registered onto "
+                                                                      "the inactive one in every frame (a second tracking loop per frame); needs no --relocalise")
+    ap.add_argument("--local-sample-rate", type=int, default=5000, help="every N-th surfel is a node of the local deformation graph")
     ap.add_argument("--time-delta", type=int, default=0, help="ticks after which an unseen surfel is inactive (0: never; ElasticFusion's 200 with "
                                                               "--close-loops)")
     ap.add_argument("--redetect", action="store_true", help="an object that is labelled again resumes its kept inactive model (old id and map) "
@@ -101,13 +104,15 @@ def main():
     else:
         log = None if a.player else klg.KlgReader(a.log, a.width, a.height, flip_colors=a.flip_colors)
     a.relocalise = a.relocalise or a.close_loops
-    time_delta = a.time_delta if a.time_delta > 0 else 200 if a.close_loops else 0
+    time_delta = a.time_delta if a.time_delta > 0 else 200 if a.close_loops or a.close_local_loops else 0
     cf = facade.CoFusion(a.width, a.height, a.fx, a.fy, a.cx, a.cy, max_surfels=a.max_surfels, enable_multiple_models=int(not a.static),
                          enable_pose_logging=1, reloc=int(a.relocalise), time_delta=time_delta)
     if a.relocalise:
         cf.set_relocalisation(True, fern_threshold=a.fern_threshold, photo_threshold=a.photo_threshold, min_age=a.fern_min_age, seed=a.fern_seed)
     if a.close_loops:
         cf.set_loop_closure(True, sample_rate=a.loop_sample_rate)
+    if a.close_local_loops:
+        cf.set_local_loop_closure(True, sample_rate=a.local_sample_rate)
     if a.redetect:
         if a.static:
             raise SystemExit("--redetect needs the multi-model mode (no --static)")
@@ -180,6 +185,8 @@ def main():
         print(f"relocalisation: {cf.reloc_stats()}, lost at the end: {cf.lost}")
     if a.close_loops:
         print(f"loop closure: {cf.loop_stats()}")
+    if a.close_local_loops:
+        print(f"local loop closure: {cf.local_loop_stats()}")
     if a.redetect:
         print(f"re-detection: {cf.redetect_stats()}, {cf.num_inactive_models} inactive model(s) kept")
     if a.export_async:
