@@ -28,6 +28,20 @@ struct DeformGraph {          // device pointers of a cf_deform object
     DeformOut* out;
 };
 
+// relative constraints (cf_deform_enable_relative): the ring of pairs a local closure leaves, and what a global step with them needs
+constexpr int kDeformRelMax = 128;     // pairs of the ring at most
+constexpr int kDeformRelMin = 8;       // ... at least (one pick appends up to 5)
+constexpr int kDeformRelSlots = 8;     // node blocks of a relative row: the source set, then the target set's other nodes
+constexpr int kDeformRelLd = 400;      // leading dimension of C: 3 * 128 relative rows and the row of Y^T y, rounded up to 16
+struct DeformRel {
+    float4 *src, *dst;        // the ring [capacity]: moved source x y z srcTime, target x y z dstTime
+    int4* ids; float4* w;     // [2 capacity] weight sets: of the sources, then (from capacity) of the targets
+    int* uid; double* uval;   // U in compact form: [capacity][8] node ids (-1: unused), [capacity][8][4] the entries of a block
+    double* Y;                // [3 capacity][12 kDeformMaxNodes]: L^-1 U^T, one column of it per row here
+    double *C, *Lc;           // [kDeformRelLd][kDeformRelLd] lower: I + Y^T Y with Y^T y in row m; its factor with t in row m
+    int capacity;
+};
+
 struct DeformReactivate {
     float t_inv[16]; cf_cam cam; int cols, rows; float max_depth; const float* depth; float threshold; float tick;
 };
@@ -39,6 +53,22 @@ void launch_deform_weights(hipStream_t s, const DeformGraph& g, int n, int n_con
 void launch_deform_residual(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time);
 void launch_deform_assemble(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time);
 void launch_deform_solve(hipStream_t s, const DeformGraph& g, int n);
+// n_rel pairs of the ring (slot order) as relative rows behind the absolute ones; the global mode only.  A step with them is
+//   residual_rel, assemble, rel_rhs, solve_factor, rel_y, rel_gram, rel_c, rel_correct, solve_finish, residual_rel
+// each stage a launch: the stages meet at kernel boundaries.
+void launch_deform_rel_weights(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel);   // weight sets and U
+void launch_deform_residual_rel(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_cons, int n_rel);
+void launch_deform_rel_rhs(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_cons, int n_rel);   // b -= U^T r_rel
+void launch_deform_solve_factor(hipStream_t s, const DeformGraph& g, int n);    // B = L L^T in place, b <- L^-1 b; failed = 0 or 1
+void launch_deform_rel_y(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel);
+void launch_deform_rel_gram(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel);
+void launch_deform_rel_c(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n_rel);
+void launch_deform_rel_correct(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel);   // b <- b - Y t
+void launch_deform_solve_finish(hipStream_t s, const DeformGraph& g, int n);    // b <- L^-T b, the update, |delta|; nothing after a failure
+// the picks 0, s, 2s, .. < n_cons (s = max(1, n_cons / 3)) of the constraint rows (row = row_stride * index), the sources moved by the
+// graph `from` (its map rule, local_time as cf_deform_apply has it), into the ring from slot `head` on
+void launch_deform_rel_pick(hipStream_t s, const DeformGraph& from, int n_nodes, int local_time, const float* src, const float* dst, const float* time,
+                            const float* dst_time, int n_cons, int row_stride, const DeformRel& rel, int head);
 // last_deform_time >= 0: surfels none of whose four nodes is enabled (node time > last_deform_time) are not moved; < 0: every surfel is
 void launch_deform_apply(hipStream_t s, const DeformGraph& g, int n, float* map, unsigned count, const DeformReactivate* re, int last_deform_time);
 void launch_deform_poses(hipStream_t s, const DeformGraph& g, int n, float* poses, const int* times, int n_poses);

@@ -9,6 +9,9 @@
 //                            (both take last_deform_time, the graph's local mode: the nodes not younger than it leave the system)
 //   deform_solve_kernel      band Cholesky by block columns in one workgroup (panel in LDS, trailing window in L2), forward substitution
 //                            fused into the factorisation, backward substitution, the parameter update and |delta|
+//                            (<1> / <2>: its two halves, for the step with relative rows)
+//   deform_rel_*_kernel      relative constraints ("relative constraints" below): U in compact form, b -= U^T r, Y = L^-1 U^T by columns,
+//                            C = I + Y^T Y and Y^T y, C's Cholesky and t, y - Y t; the pick of an accepted local closure into the ring
 //   deform_apply_kernel      the map pass: node positions and times in LDS for the search and the 20 distances, the four chosen nodes'
 //                            parameters from L2, whole 16 B records; the reactivation stamp when asked
 //   deform_poses_kernel      one lane per keyframe pose: translation by the map rule, 3x3 -> polar factor (Newton in f64)
@@ -248,7 +251,10 @@ __device__ __forceinline__ double block_sum(double v, double* red)
 // A dropped row (the rotation rows of a disabled node, an edge between two disabled nodes, a constraint none of whose four nodes is
 // enabled) is written as 0: it adds nothing to the error, and no enabled column of J meets it.  The mean constraint error is over
 // ALL constraints (nonRelativeConstraintError does not look at `enabled`).
-__global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g, int n, int n_cons, int ldt)
+// kRel: the n_rel pairs of the ring follow the absolute constraints as rows f32(phi(src) - phi(tgt)) * 10 (the global mode only: ldt
+// enables every node); they count in the error and in the DENOMINATOR of the mean constraint error (nonRelativeConstraintError).
+template <bool kRel>
+__global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g, int n, int n_cons, int ldt, DeformRel rel, int n_rel)
 {
     __shared__ double red[kSolveT];
     __shared__ float norms[kDeformMaxConsSized];
@@ -267,6 +273,24 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
         g.r[cons_row(n, l, 1)] = keep ? (double)dy * (double)kSqrtCon : 0.0;
         g.r[cons_row(n, l, 2)] = keep ? (double)dz * (double)kSqrtCon : 0.0;
         norms[l] = sqrtf((dx * dx + dy * dy) + dz * dz);
+    }
+    if (kRel) {
+        for (int p = t; p < n_rel; p += kSolveT) {
+            f3 m[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const float4 s = e ? rel.dst[p] : rel.src[p], w4 = rel.w[e * rel.capacity + p];
+                const int4 i4 = rel.ids[e * rel.capacity + p];
+                const int ids[4] = {i4.x, i4.y, i4.z, i4.w};
+                const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+                m[e] = f3{s.x, s.y, s.z};
+                if (finite_f(w4.x)) m[e] = move_point(g.nodes, g.params, m[e], ids, w);
+            }
+            const float dx = m[0].x - m[1].x, dy = m[0].y - m[1].y, dz = m[0].z - m[1].z;
+            g.r[cons_row(n, n_cons + p, 0)] = (double)dx * (double)kSqrtCon;
+            g.r[cons_row(n, n_cons + p, 1)] = (double)dy * (double)kSqrtCon;
+            g.r[cons_row(n, n_cons + p, 2)] = (double)dz * (double)kSqrtCon;
+        }
     }
     int on_count = 0;
     for (int j = t; j < n; j += kSolveT) {
@@ -301,7 +325,7 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
         }
     }
     const int enabled = __syncthreads_count(on_count);   // (n <= kSolveT: one node per thread)
-    const int rows = 18 * n + 3 * n_cons;
+    const int rows = 18 * n + 3 * n_cons + (kRel ? 3 * n_rel : 0);
     double s = 0.0;
     for (int i = t; i < rows; i += kSolveT) { const double v = g.r[i]; s = s + v * v; }
     const double e = block_sum(s, red);
@@ -309,7 +333,7 @@ __global__ void __launch_bounds__(kSolveT) deform_residual_kernel(DeformGraph g,
         float m = 0.f;
         for (int l = 0; l < n_cons; l++) m = m + norms[l];
         g.out->error = (float)e;
-        g.out->mean_cons_error = m / (float)n_cons;
+        g.out->mean_cons_error = m / (float)(kRel ? n_cons + n_rel : n_cons);
         g.out->enabled = enabled;
     }
 }
@@ -379,6 +403,9 @@ __global__ void __launch_bounds__(192) deform_assemble_kernel(DeformGraph g, int
 }
 
 // A = L L^T in place (band storage, AB[i][d] = A[i][i - d]), L y = b, L^T x = y, params += x.  One workgroup of kSolveT threads.
+// kPart 0: the whole step.  The step with relative rows works on y between the two halves: kPart 1 ends behind the forward substitution
+// (L in AB, y in b, failed = 0 or 1), kPart 2 starts at the backward substitution and does nothing after a failure.
+template <int kPart>
 __global__ void __launch_bounds__(kSolveT) deform_solve_kernel(DeformGraph g, int n)
 {
     constexpr int V = kDeformVars, BW = kDeformBand;
@@ -388,7 +415,11 @@ __global__ void __launch_bounds__(kSolveT) deform_solve_kernel(DeformGraph g, in
     const int t = (int)threadIdx.x;
     const int nv = V * n;
     double* AB = g.AB; double* b = g.b;   // (workgroup-shared through the barriers: not restrict)
-    for (int c0 = 0; c0 < nv; c0 += V) {
+    if (kPart == 2 && g.out->failed) {   // (the same value in every thread)
+        if (t == 0) g.out->delta_norm = 0.0;
+        return;
+    }
+    for (int c0 = 0; kPart != 2 && c0 < nv; c0 += V) {
         const int rows = nv - c0 < BW ? nv - c0 : BW;
         for (int e = t; e < rows * V; e += kSolveT) {
             const int ri = e / V, c = e - ri * V;
@@ -440,6 +471,10 @@ __global__ void __launch_bounds__(kSolveT) deform_solve_kernel(DeformGraph g, in
             AB[at] = v;
         }
         __syncthreads();
+    }
+    if (kPart == 1) {
+        if (t == 0) g.out->failed = 0;
+        return;
     }
     // L^T x = y, last block column first
     for (int c0 = nv - V; c0 >= 0; c0 -= V) {
@@ -575,7 +610,336 @@ __global__ void __launch_bounds__(kDB) deform_poses_kernel(DeformGraph g, int n,
     M[3] = q.x; M[7] = q.y; M[11] = q.z;
 }
 
+// ------------------------------------------------------------------------------------------------ relative constraints
+// A = B + U^T U with B the band system and U the 3 n_rel relative rows, solved on the band factor ("Relative rows"):
+//   L L^T = B, y = L^-1 b, Y = L^-1 U^T, C = I + Y^T Y, t = C^-1 (Y^T y), delta = L^-T (y - Y t)
+// Every sum has one fixed order and no stage uses atomics: the same bytes on every run.  The stages meet at kernel boundaries.
+
+// U in compact form, one thread per pair: the entries of a row do not depend on its component c -- node block o = 12 id holds
+// e.x, e.y, e.z at o + c, o + 3 + c, o + 6 + c and w * 10 at o + 9 + c with e = ((p - g) * w) * 10 in f32 -- so a pair keeps eight node
+// slots of four values: the source set, then the target set negated, a node of both in one slot (f64 sum, source first).
+__global__ void __launch_bounds__(kDeformRelMax) deform_rel_rows_kernel(DeformGraph g, DeformRel rel, int n_rel)
+{
+    const int p = (int)threadIdx.x;
+    if (p >= n_rel) return;
+    int* uid = rel.uid + (size_t)p * kDeformRelSlots;
+    double* uval = rel.uval + (size_t)p * kDeformRelSlots * 4;
+    for (int s = 0; s < kDeformRelSlots; s++) {
+        uid[s] = -1;
+        for (int q = 0; q < 4; q++) uval[4 * s + q] = 0.0;
+    }
+    if (!finite_f(rel.w[p].x) || !finite_f(rel.w[rel.capacity + p].x)) return;   // a NaN set: the rows stay empty
+    int used = 0;
+    for (int e = 0; e < 2; e++) {
+        const float4 pt = e ? rel.dst[p] : rel.src[p], w4 = rel.w[e * rel.capacity + p];
+        const int4 i4 = rel.ids[e * rel.capacity + p];
+        for (int k = 0; k < kDeformK; k++) {
+            const int id = id_of(i4, k);
+            const float w = w_of(w4, k);
+            const f3 gp = node_pos(g, id);
+            const float v[4] = {((pt.x - gp.x) * w) * kSqrtCon, ((pt.y - gp.y) * w) * kSqrtCon, ((pt.z - gp.z) * w) * kSqrtCon, w * kSqrtCon};
+            int at = used;
+            for (int s = 0; s < used; s++) at = uid[s] == id ? s : at;
+            if (at == used) { uid[at] = id; used++; }
+            for (int q = 0; q < 4; q++) uval[4 * at + q] = uval[4 * at + q] + (e ? -(double)v[q] : (double)v[q]);
+        }
+    }
+}
+
+// unknown u of a node -> (component c of the rows that meet it, which of the block's four values)
+__device__ __forceinline__ int rel_comp(int u) { return u < 9 ? u % 3 : u - 9; }
+__device__ __forceinline__ int rel_quad(int u) { return u < 9 ? u / 3 : 3; }
+
+// b <- b - U^T r_rel, one thread per unknown, the sum over the rows in row order from 0
+__global__ void __launch_bounds__(kDB) deform_rel_rhs_kernel(DeformGraph g, DeformRel rel, int n, int n_cons, int n_rel)
+{
+    const int i = (int)(blockIdx.x * kDB + threadIdx.x);
+    if (i >= kDeformVars * n) return;
+    const int I = i / kDeformVars, u = i - kDeformVars * I, c = rel_comp(u), q = rel_quad(u);
+    double s = 0.0;
+    for (int p = 0; p < n_rel; p++)
+        for (int k = 0; k < kDeformRelSlots; k++)
+            if (rel.uid[p * kDeformRelSlots + k] == I) s = s + rel.uval[(size_t)(p * kDeformRelSlots + k) * 4 + q] * g.r[cons_row(n, n_cons + p, c)];
+    g.b[i] = g.b[i] - s;
+}
+
+// Y = L^-1 U^T: workgroup j (one wave) substitutes row j of U forward through the band factor, block row by block row, from the first
+// node block the row touches (everything above it is zero).  The last 239 entries are all a row needs: they live in an LDS ring.
+// Per block row the 64 lanes share the 12 dot products with the earlier entries (lane l takes d = r + 1 + l, + 64, ...; xor tree), then
+// every lane solves the 12 x 12 triangle (staged in LDS) for itself.
+__global__ void __launch_bounds__(64) deform_rel_y_kernel(DeformGraph g, DeformRel rel, int n)
+{
+    constexpr int V = kDeformVars, BW = kDeformBand, kRing = 256;
+    __shared__ double win[kRing];
+    __shared__ double tri[V][V + 1];
+    if (g.out->failed) return;   // (the same value in every thread)
+    const int col = (int)blockIdx.x, p = col / 3, c = col - 3 * p, lane = (int)threadIdx.x;
+    double* __restrict__ Y = rel.Y + (size_t)col * (V * kDeformMaxNodes);
+    const double* __restrict__ AB = g.AB;
+    const int* uid = rel.uid + (size_t)p * kDeformRelSlots;
+    const double* uval = rel.uval + (size_t)p * kDeformRelSlots * 4;
+    int first = n;
+    for (int s = 0; s < kDeformRelSlots; s++) { const int id = uid[s]; first = id >= 0 && id < first ? id : first; }
+    for (int i = lane; i < V * first; i += 64) Y[i] = 0.0;
+    for (int i = lane; i < kRing; i += 64) win[i] = 0.0;
+    __syncthreads();
+    for (int I = first; I < n; I++) {
+        const int c0 = V * I;
+        int slot = -1;
+        for (int s = 0; s < kDeformRelSlots; s++) slot = uid[s] == I ? s : slot;
+        // every load of the block row is issued before the first use: the row is bound by memory latency, not by arithmetic
+        double tl[3];
+#pragma unroll
+        for (int q = 0; q < 3; q++) {   // the diagonal block of L, entry (r, k <= r) by lane 12 r + k - 64 q
+            const int e = lane + 64 * q, r = e / V, k = e - V * r;
+            tl[q] = e < V * V && k <= r ? AB[(size_t)(c0 + r) * BW + (r - k)] : 0.0;
+        }
+        double lv[V][4];
+#pragma unroll
+        for (int r = 0; r < V; r++) {
+            const int i = c0 + r;
+            const int dmax = min(i - V * first, r + (BW - V));   // the block band: row r of a block holds L back to offset r + 228
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int d = r + 1 + lane + 64 * q;
+                lv[r][q] = d <= dmax ? AB[(size_t)i * BW + d] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const int e = lane + 64 * q;
+            if (e < V * V) tri[e / V][e % V] = tl[q];
+        }
+        double acc[V];
+#pragma unroll
+        for (int r = 0; r < V; r++) {
+            const int i = c0 + r;
+            const int dmax = min(i - V * first, r + (BW - V));   // the block band: row r of a block holds L back to offset r + 228
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {   // (d ascending, as a loop over d = r + 1 + lane, + 64, .. <= dmax sums)
+                const int d = r + 1 + lane + 64 * q;
+                if (d <= dmax) s = s + lv[r][q] * win[(i - d) & (kRing - 1)];
+            }
+            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+            acc[r] = s;
+        }
+        __syncthreads();   // (the diagonal block is in LDS)
+        double y[V];
+#pragma unroll
+        for (int r = 0; r < V; r++) {
+            double v = slot >= 0 && rel_comp(r) == c ? uval[4 * slot + rel_quad(r)] : 0.0;
+            v = v - acc[r];
+#pragma unroll
+            for (int k = 0; k < r; k++) v = v - tri[r][k] * y[k];
+            y[r] = v / tri[r][r];
+        }
+        __syncthreads();   // (every lane has read the ring and the diagonal block for this block row)
+#pragma unroll
+        for (int r = 0; r < V; r++)
+            if (lane == r) { win[(c0 + r) & (kRing - 1)] = y[r]; Y[c0 + r] = y[r]; }
+        __syncthreads();
+    }
+}
+
+// G[a][b] = v_a . v_b for b <= a over the vectors v_0 .. v_{m-1} = the rows of Y and v_m = y (g.b): C = I + G in rows 0 .. m-1, Y^T y in
+// row m.  One workgroup per 16 x 16 tile of the lower triangle, 64 entries of the 32 vectors staged in LDS at a time; every entry is
+// summed by ONE thread over i ascending.  The sum is compensated -- each product with its rounding error (fma), each addition with
+// its own (two-sum), the errors summed beside it and added once at the end: where B alone is soft along the pairs (a loop whose old
+// end hangs on regularisation edges only) Y^T Y reaches 1e3 .. 1e7 and y - Y t cancels that many digits of whatever error C and Y^T y
+// carry; a plain f64 sum here cost five times the error of the whole step.
+__global__ void __launch_bounds__(256) deform_rel_gram_kernel(DeformGraph g, DeformRel rel, int n, int m)
+{
+    constexpr int T = 16, CH = 64;
+    __shared__ double A[T][CH + 1], B[T][CH + 1];
+    if (g.out->failed) return;
+    const int bi = (int)blockIdx.y, bj = (int)blockIdx.x;
+    if (bj > bi) return;
+    const int t = (int)threadIdx.x, ty = t / T, tx = t % T, nv = kDeformVars * n;
+    const size_t ldy = (size_t)kDeformVars * kDeformMaxNodes;
+    double acc = 0.0, low = 0.0;
+    for (int i0 = 0; i0 < nv; i0 += CH) {
+        for (int e = t; e < T * CH; e += 256) {
+            const int row = e / CH, ii = e - row * CH, i = i0 + ii, a = T * bi + row, b = T * bj + row;
+            A[row][ii] = i < nv && a <= m ? (a == m ? g.b[i] : rel.Y[a * ldy + i]) : 0.0;
+            B[row][ii] = i < nv && b < m ? rel.Y[b * ldy + i] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int ii = 0; ii < CH; ii++) {
+            const double x = A[ty][ii], y = B[tx][ii];
+            const double p = x * y, pe = fma(x, y, -p);
+            const double s = acc + p, v = s - acc;
+            low = low + (((acc - (s - v)) + (p - v)) + pe);
+            acc = s;
+        }
+        __syncthreads();
+    }
+    const int a = T * bi + ty, b = T * bj + tx;
+    if (a == b) {   // the identity joins the sum the same way
+        const double s = acc + 1.0, v = s - acc;
+        low = low + ((acc - (s - v)) + (1.0 - v));
+        acc = s;
+    }
+    if (a <= m && b < m && b <= a) rel.C[(size_t)a * kDeformRelLd + b] = acc + low;
+}
+
+// C = Lc Lc^T by panels of 16 columns (the panel in LDS, the trailing matrix through L2: 384^2 doubles do not fit in LDS), then
+// Lc w = Y^T y and Lc^T t = w by columns; t replaces row m.  C itself is kept (cf_deform_download_relative); the work is done on a copy.
+// One workgroup of kSolveT threads.  A pivot <= 0 fails the step.
+__global__ void __launch_bounds__(kSolveT) deform_rel_c_kernel(DeformGraph g, DeformRel rel, int m)
+{
+    constexpr int W = 16, LD = kDeformRelLd;
+    __shared__ double P[3 * kDeformRelMax][W + 1];
+    __shared__ double tv[3 * kDeformRelMax];
+    if (g.out->failed) return;
+    const int t = (int)threadIdx.x;
+    double* L = rel.Lc;   // (workgroup-shared through the barriers: not restrict)
+    for (int e = t; e < (m + 1) * m; e += kSolveT) {
+        const int i = e / m, j = e - i * m;
+        if (j <= i) L[(size_t)i * LD + j] = rel.C[(size_t)i * LD + j];
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < m; c0 += W) {
+        const int rows = m - c0, w = rows < W ? rows : W;
+        for (int e = t; e < rows * W; e += kSolveT) {
+            const int ri = e / W, c = e - ri * W;
+            P[ri][c] = c < w && ri >= c ? L[(size_t)(c0 + ri) * LD + c0 + c] : 0.0;
+        }
+        __syncthreads();
+        for (int c = 0; c < w; c++) {
+            const double piv = P[c][c];
+            if (!(piv > 0.0)) {   // (the same value in every thread: the whole workgroup leaves)
+                if (t == 0) { g.out->failed = 1; g.out->delta_norm = 0.0; }
+                return;
+            }
+            const double l = sqrt(piv);
+            __syncthreads();
+            for (int ri = c + t; ri < rows; ri += kSolveT) P[ri][c] = ri == c ? l : P[ri][c] / l;
+            __syncthreads();
+            const int wr = w - 1 - c;   // columns c+1 .. w-1
+            for (int e = t; e < (rows - c - 1) * wr; e += kSolveT) {
+                const int ri = c + 1 + e / wr, cc = c + 1 + e % wr;
+                if (ri >= cc) P[ri][cc] = P[ri][cc] - P[ri][c] * P[cc][c];
+            }
+            __syncthreads();
+        }
+        for (int e = t; e < rows * W; e += kSolveT) {
+            const int ri = e / W, c = e - ri * W;
+            if (c < w && ri >= c) L[(size_t)(c0 + ri) * LD + c0 + c] = P[ri][c];
+        }
+        const int mr = rows - w;   // the trailing matrix: rows and columns c0 + w .. m - 1
+        for (int e = t; e < mr * mr; e += kSolveT) {
+            const int i = w + e / mr, j = w + e % mr;
+            if (j > i) continue;
+            const size_t at = (size_t)(c0 + i) * LD + c0 + j;
+            double v = L[at];
+            for (int c = 0; c < w; c++) v = v - P[i][c] * P[j][c];
+            L[at] = v;
+        }
+        __syncthreads();
+    }
+    for (int i = t; i < m; i += kSolveT) tv[i] = L[(size_t)m * LD + i];
+    __syncthreads();
+    for (int j = 0; j < m; j++) {
+        if (t == 0) tv[j] = tv[j] / L[(size_t)j * LD + j];
+        __syncthreads();
+        for (int i = j + 1 + t; i < m; i += kSolveT) tv[i] = tv[i] - L[(size_t)i * LD + j] * tv[j];
+        __syncthreads();
+    }
+    for (int j = m - 1; j >= 0; j--) {
+        if (t == 0) tv[j] = tv[j] / L[(size_t)j * LD + j];
+        __syncthreads();
+        for (int i = t; i < j; i += kSolveT) tv[i] = tv[i] - L[(size_t)j * LD + i] * tv[j];
+        __syncthreads();
+    }
+    for (int i = t; i < m; i += kSolveT) L[(size_t)m * LD + i] = tv[i];
+}
+
+// b <- y - Y t, one thread per unknown, the sum over the rows of U ascending
+__global__ void __launch_bounds__(kDB) deform_rel_correct_kernel(DeformGraph g, DeformRel rel, int n, int m)
+{
+    if (g.out->failed) return;
+    const int i = (int)(blockIdx.x * kDB + threadIdx.x);
+    if (i >= kDeformVars * n) return;
+    const size_t ldy = (size_t)kDeformVars * kDeformMaxNodes;
+    const double* __restrict__ tv = rel.Lc + (size_t)m * kDeformRelLd;
+    double s = 0.0;
+    for (int j = 0; j < m; j++) s = s + rel.Y[j * ldy + i] * tv[j];
+    g.b[i] = g.b[i] - s;
+}
+
+// what an accepted local closure leaves (CoFusion.cpp:445-458): lane k takes constraint k s of n, s = max(1, n / 3) (the reference's
+// i += n / 3 never ends for n < 3), moves its source by the closure's graph as the map pass would and writes the pair into the ring
+__global__ void __launch_bounds__(64) deform_rel_pick_kernel(DeformGraph from, int n_nodes, int local_time, const float* __restrict__ src,
+                                                             const float* __restrict__ dst, const float* __restrict__ time,
+                                                             const float* __restrict__ dst_time, int n, int row_stride, DeformRel rel, int head)
+{
+    const int k = (int)threadIdx.x, step = n / 3 > 1 ? n / 3 : 1;
+    if ((long long)k * step >= n) return;
+    const int idx = k * step;
+    const size_t row = (size_t)idx * row_stride;
+    f3 p = f3{src[3 * row], src[3 * row + 1], src[3 * row + 2]};
+    const float tm = time[row];
+    int ids[4]; float w[4];
+    if (window_weights(from.nodes, n_nodes, p, (int)tm, ids, w) &&
+        ((int)from.nodes[ids[0]].w > local_time || (int)from.nodes[ids[1]].w > local_time || (int)from.nodes[ids[2]].w > local_time ||
+         (int)from.nodes[ids[3]].w > local_time))
+        p = move_point(from.nodes, from.params, p, ids, w);
+    const int slot = (head + k) % rel.capacity;
+    rel.src[slot] = make_float4(p.x, p.y, p.z, tm);
+    rel.dst[slot] = make_float4(dst[3 * row], dst[3 * row + 1], dst[3 * row + 2], dst_time[idx]);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
+void launch_deform_rel_weights(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel)
+{
+    if (n_rel <= 0) return;
+    DeformGraph a = g, b = g;   // the window rule over the ring: the sources at srcTime, the targets at dstTime
+    a.cons_src = rel.src; a.ids = rel.ids; a.w = rel.w;
+    b.cons_src = rel.dst; b.ids = rel.ids + rel.capacity; b.w = rel.w + rel.capacity;
+    launch_deform_weights(s, a, n, n_rel);
+    launch_deform_weights(s, b, n, n_rel);
+    hipLaunchKernelGGL(deform_rel_rows_kernel, dim3(1), dim3(kDeformRelMax), 0, s, g, rel, n_rel);
+}
+void launch_deform_residual_rel(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_cons, int n_rel)
+{
+    hipLaunchKernelGGL(deform_residual_kernel<true>, dim3(1), dim3(kSolveT), 0, s, g, n, n_cons, kDeformAllEnabled, rel, n_rel);
+}
+void launch_deform_rel_rhs(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_cons, int n_rel)
+{
+    hipLaunchKernelGGL(deform_rel_rhs_kernel, dim3((kDeformVars * n + kDB - 1) / kDB), dim3(kDB), 0, s, g, rel, n, n_cons, n_rel);
+}
+void launch_deform_solve_factor(hipStream_t s, const DeformGraph& g, int n)
+{
+    hipLaunchKernelGGL(deform_solve_kernel<1>, dim3(1), dim3(kSolveT), 0, s, g, n);
+}
+void launch_deform_rel_y(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel)
+{
+    hipLaunchKernelGGL(deform_rel_y_kernel, dim3(3 * n_rel), dim3(64), 0, s, g, rel, n);
+}
+void launch_deform_rel_gram(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel)
+{
+    const int tiles = (3 * n_rel + 1 + 15) / 16;
+    hipLaunchKernelGGL(deform_rel_gram_kernel, dim3(tiles, tiles), dim3(256), 0, s, g, rel, n, 3 * n_rel);
+}
+void launch_deform_rel_c(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n_rel)
+{
+    hipLaunchKernelGGL(deform_rel_c_kernel, dim3(1), dim3(kSolveT), 0, s, g, rel, 3 * n_rel);
+}
+void launch_deform_rel_correct(hipStream_t s, const DeformGraph& g, const DeformRel& rel, int n, int n_rel)
+{
+    hipLaunchKernelGGL(deform_rel_correct_kernel, dim3((kDeformVars * n + kDB - 1) / kDB), dim3(kDB), 0, s, g, rel, n, 3 * n_rel);
+}
+void launch_deform_solve_finish(hipStream_t s, const DeformGraph& g, int n)
+{
+    hipLaunchKernelGGL(deform_solve_kernel<2>, dim3(1), dim3(kSolveT), 0, s, g, n);
+}
+void launch_deform_rel_pick(hipStream_t s, const DeformGraph& from, int n_nodes, int local_time, const float* src, const float* dst, const float* time,
+                            const float* dst_time, int n_cons, int row_stride, const DeformRel& rel, int head)
+{
+    if (n_cons > 0) hipLaunchKernelGGL(deform_rel_pick_kernel, dim3(1), dim3(64), 0, s, from, n_nodes, local_time, src, dst, time, dst_time, n_cons, row_stride, rel, head);
+}
 void launch_deform_sample(hipStream_t s, const float* map, unsigned count, unsigned stride, const DeformGraph& g, DeformMeta* meta)
 {
     hipLaunchKernelGGL(deform_sample_kernel, dim3(1), dim3(kDeformMaxNodes), 0, s, reinterpret_cast<const float4*>(map), count, stride, g, meta);
@@ -590,7 +954,7 @@ void launch_deform_weights(hipStream_t s, const DeformGraph& g, int n, int n_con
 }
 void launch_deform_residual(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time)
 {
-    hipLaunchKernelGGL(deform_residual_kernel, dim3(1), dim3(kSolveT), 0, s, g, n, n_cons, last_deform_time);
+    hipLaunchKernelGGL(deform_residual_kernel<false>, dim3(1), dim3(kSolveT), 0, s, g, n, n_cons, last_deform_time, DeformRel{}, 0);
 }
 void launch_deform_assemble(hipStream_t s, const DeformGraph& g, int n, int n_cons, int last_deform_time)
 {
@@ -598,7 +962,7 @@ void launch_deform_assemble(hipStream_t s, const DeformGraph& g, int n, int n_co
 }
 void launch_deform_solve(hipStream_t s, const DeformGraph& g, int n)
 {
-    hipLaunchKernelGGL(deform_solve_kernel, dim3(1), dim3(kSolveT), 0, s, g, n);
+    hipLaunchKernelGGL(deform_solve_kernel<0>, dim3(1), dim3(kSolveT), 0, s, g, n);
 }
 void launch_deform_apply(hipStream_t s, const DeformGraph& g, int n, float* map, unsigned count, const DeformReactivate* re, int last_deform_time)
 {

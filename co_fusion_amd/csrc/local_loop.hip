@@ -31,6 +31,7 @@ struct LocalArgs {
     int cols, rows, tick, pin;
     float max_depth, cov_thresh, icp_err_thresh; int icp_count_thresh;
     float *src, *dst, *time;               // f32 [1536][3], [1536][3], [1536]
+    float* ttime;                          // f32 [768]: the old time of every constraint (pin rows excluded), pinned or not
     unsigned serial;
 };
 
@@ -127,6 +128,7 @@ __global__ void __launch_bounds__(kLocalT) local_constraints_kernel(const LocalA
         float* ps = a.src + 3 * row; float* pd = a.dst + 3 * row;
         ps[0] = s.x; ps[1] = s.y; ps[2] = s.z; pd[0] = d.x; pd[1] = d.y; pd[2] = d.z;
         a.time[row] = (float)a.tick;
+        a.ttime[row / stride] = (float)ot;
         if (a.pin) {
             ps[3] = d.x; ps[4] = d.y; ps[5] = d.z; pd[3] = d.x; pd[4] = d.y; pd[5] = d.z;
             a.time[row + 1] = (float)ot;
@@ -144,7 +146,7 @@ __global__ void __launch_bounds__(kLocalT) local_constraints_kernel(const LocalA
 struct cf_local_loop {
     cf_ctx* ctx = nullptr;
     cf_local_loop_record* h_rec = nullptr;   // pinned: written by the kernel
-    float *src = nullptr, *dst = nullptr, *time = nullptr;
+    float *src = nullptr, *dst = nullptr, *time = nullptr, *ttime = nullptr;
     void* d_in = nullptr;                    // [R 9 | t 3 f32][cf_track_stats]: a tracker result handed in from the host (tests)
     hipEvent_t event = nullptr;
     unsigned serial = 0;
@@ -159,7 +161,7 @@ void cf_local_loop_destroy(cf_local_loop* l)
 {
     if (!l) return;
     (void)hipStreamSynchronize(l->ctx->stream);
-    (void)hipFree(l->src); (void)hipFree(l->dst); (void)hipFree(l->time); (void)hipFree(l->d_in);
+    (void)hipFree(l->src); (void)hipFree(l->dst); (void)hipFree(l->time); (void)hipFree(l->ttime); (void)hipFree(l->d_in);
     (void)hipHostFree(l->h_rec);
     if (l->event) (void)hipEventDestroy(l->event);
     delete l;
@@ -180,6 +182,7 @@ int cf_local_loop_create(cf_ctx* ctx, cf_local_loop** out)
     int r = dmalloc(ctx, &l->src, rows * 3);
     if (!r) r = dmalloc(ctx, &l->dst, rows * 3);
     if (!r) r = dmalloc(ctx, &l->time, rows);
+    if (!r) r = dmalloc(ctx, &l->ttime, (size_t)kLocalMaxSamples);
     if (!r && hipMalloc(&l->d_in, kInStats + sizeof(cf_track_stats)) != hipSuccess) r = CF_ENOMEM;
     if (!r && hipHostMalloc(reinterpret_cast<void**>(&l->h_rec), sizeof(cf_local_loop_record)) != hipSuccess) r = CF_ENOMEM;
     if (!r && hipEventCreateWithFlags(&l->event, hipEventDisableTiming) != hipSuccess) r = CF_EHIP;
@@ -215,7 +218,7 @@ int cf_local_loop_constraints_async(cf_local_loop* l, const cf_odom* od, const c
     memcpy(a.curr, curr_pose, sizeof(a.curr));
     a.cols = ctx->cfg.width; a.rows = ctx->cfg.height; a.tick = tick; a.pin = pin ? 1 : 0;
     a.max_depth = max_depth; a.cov_thresh = th->cov_thresh; a.icp_err_thresh = th->icp_err_thresh; a.icp_count_thresh = th->icp_count_thresh;
-    a.src = l->src; a.dst = l->dst; a.time = l->time;
+    a.src = l->src; a.dst = l->dst; a.time = l->time; a.ttime = l->ttime;
     a.serial = ++l->serial;
     hipLaunchKernelGGL(local_constraints_kernel, dim3(1), dim3(kLocalT), 0, s, a, l->h_rec);
     LAUNCHCHK(ctx);
@@ -241,6 +244,13 @@ int cf_local_loop_constraint_buffers(cf_local_loop* l, float** src, float** dst,
     if (src) *src = l->src;
     if (dst) *dst = l->dst;
     if (time) *time = l->time;
+    return CF_OK;
+}
+
+int cf_local_loop_target_times(cf_local_loop* l, float** target_time)
+{
+    if (!l || !target_time) return CF_EINVAL;
+    *target_time = l->ttime;
     return CF_OK;
 }
 

@@ -13,6 +13,7 @@ from .api import Cam, _p
 MAX_NODES = 1024
 MAX_CONSTRAINTS = 128
 MAX_CONSTRAINTS_SIZED = 1536
+MAX_RELATIVE = 128
 BAND = 240
 VARS = 12
 STEP_FIELDS = ("error", "delta_norm", "failed", "mean_cons_error")
@@ -62,6 +63,13 @@ SIGNATURES = {
     "cf_deform_apply": (_I, [_V, _V, C.c_uint32, C.POINTER(Reactivate)]),
     "cf_deform_apply_poses": (_I, [_V, _V, _V, _I]),
     "cf_deform_download": (_I, [_V, _PI, _PI, _V, _V, _V, _V, _V, _V, _V]),
+    "cf_deform_enable_relative": (_I, [_V, _I]),
+    "cf_deform_set_relative": (_I, [_V, _V, _V, _V, _V, _I, _I]),
+    "cf_deform_set_relative_device": (_I, [_V, _V, _V, _V, _V, _I, _I]),
+    "cf_deform_pick_relative": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _PI]),
+    "cf_deform_download_out": (_I, [_V, _V]),
+    "cf_deform_bench_relative_y": (_I, [_V]),
+    "cf_deform_download_relative": (_I, [_V, _PI, _PI, C.POINTER(C.c_int64), _PI, _V, _V, _V, _V, _V, _V, _V]),
 }
 
 
@@ -209,3 +217,58 @@ class Deform:
         if system:
             out.update(A=A, b=b)
         return out
+
+    # ---------------------------------------------------------------------------------------------- relative constraints
+    def enable_relative(self, capacity=MAX_RELATIVE):
+        """allocate the ring of relative pairs and the storage of the step that takes them (cf_deform_enable_relative)"""
+        self.ctx._check(self.lib.cf_deform_enable_relative(self.h, int(capacity)))
+
+    def set_relative(self, pairs, append=False):
+        """pairs [n, 8] (source xyz, srcTime, target xyz, dstTime) from the host; append False: the ring is emptied first"""
+        p = np.ascontiguousarray(pairs, np.float32).reshape(-1, 8)
+        cols = [np.ascontiguousarray(p[:, 0:3]), np.ascontiguousarray(p[:, 4:7]), np.ascontiguousarray(p[:, 3]), np.ascontiguousarray(p[:, 7])]
+        ptr = [a.ctypes.data_as(C.c_void_p) for a in cols]
+        self.ctx._check(self.lib.cf_deform_set_relative(self.h, ptr[0], ptr[1], ptr[2], ptr[3], len(p), 1 if append else 0))
+
+    def set_relative_device(self, src, dst, src_time, dst_time, n, append=False):
+        """the same from device tensors f32 [>= n, 3], [>= n, 3], [>= n], [>= n]"""
+        self.ctx._check(self.lib.cf_deform_set_relative_device(self.h, _p(src), _p(dst), _p(src_time), _p(dst_time), int(n), 1 if append else 0))
+
+    def pick_relative(self, closure, src, dst, time, dst_time, n, row_stride=1):
+        """append what the accepted closure `closure` (a Deform) leaves of its n constraints (device tensors; rows row_stride * i of src, dst,
+        time; dst_time one per constraint) -> the number of pairs appended"""
+        k = C.c_int()
+        self.ctx._check(self.lib.cf_deform_pick_relative(self.h, closure.h, _p(src), _p(dst), _p(time), _p(dst_time), int(n), int(row_stride), C.byref(k)))
+        return k.value
+
+    def relative_counts(self):
+        """-> dict(capacity, count, appended, used)"""
+        cap, cnt, used, app = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        self.ctx._check(self.lib.cf_deform_download_relative(self.h, C.byref(cap), C.byref(cnt), C.byref(app), C.byref(used), None, None, None, None, None, None, None))
+        return dict(capacity=cap.value, count=cnt.value, appended=app.value, used=used.value)
+
+    def download_relative(self, system=False):
+        """pairs [count, 8]; with system (after assemble / iterate): the weight sets of sources and targets, U in compact form, the relative
+        residuals and C = I + Y^T Y [3 count, 3 count] with Y^T y [3 count]"""
+        c = self.relative_counts()["count"]
+        pairs = np.zeros((c, 8), np.float32)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        ids = w = uid = uval = rr = Cm = None
+        if system:
+            ids = np.zeros((2, c, 4), np.int32); w = np.zeros((2, c, 4), np.float32); uid = np.zeros((c, 8), np.int32)
+            uval = np.zeros((c, 8, 4)); rr = np.zeros(3 * c); Cm = np.zeros((3 * c + 1, 3 * c))
+        self.ctx._check(self.lib.cf_deform_download_relative(self.h, None, None, None, None, vp(pairs), vp(ids), vp(w), vp(uid), vp(uval), vp(rr), vp(Cm)))
+        out = dict(pairs=pairs)
+        if system:
+            out.update(ids=ids, weights=w, u_ids=uid, u_vals=uval, r_rel=rr, C=Cm[:3 * c], z=Cm[3 * c])
+        return out
+
+    def download_out(self):
+        """the 32-byte record the last residual pass / solve left on the device, as bytes"""
+        buf = (C.c_ubyte * 32)()
+        self.ctx._check(self.lib.cf_deform_download_out(self.h, buf))
+        return bytes(buf)
+
+    def bench_relative_y(self):
+        """benchmark access: only the launch Y = L^-1 U^T, on the state the last iterate with pairs left.  Enqueued only."""
+        self.ctx._check(self.lib.cf_deform_bench_relative_y(self.h))

@@ -438,6 +438,52 @@ class CoFusion:
         out["last"] = last
         return out
 
+    def set_relative_constraints(self, on=True):
+        """Relative constraints (cofusion_set_relative_constraints): an accepted local closure leaves a few point pairs in
+        a device ring of 128, and every later global closure (the fern seam's, deform_background's) keeps each pair together, so it
+        cannot pull apart what a local closure registered.  Off, or with an empty store, every closure is what it was."""
+        self._check(self.lib.cofusion_set_relative_constraints(self.h, int(bool(on))))
+
+    def add_relative_constraints(self, src, dst, src_time, dst_time):
+        """append caller-supplied pairs: src, dst [n, 3], src_time, dst_time [n]"""
+        src = np.ascontiguousarray(src, np.float32).reshape(-1, 3); dst = np.ascontiguousarray(dst, np.float32).reshape(-1, 3)
+        ts = np.ascontiguousarray(src_time, np.float32).reshape(-1); td = np.ascontiguousarray(dst_time, np.float32).reshape(-1)
+        assert len(src) == len(dst) == len(ts) == len(td)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.cofusion_add_relative_constraints(self.h, vp(src), vp(dst), vp(ts), vp(td), len(src)))
+
+    def relative_constraints(self):
+        """the stored pairs in store order -> f32 [n, 8]: source xyz, srcTime, target xyz, dstTime"""
+        n = C.c_int()
+        out = np.zeros((128, 8), np.float32)
+        self._check(self.lib.cofusion_relative_constraints(self.h, out.ctypes.data_as(C.c_void_p), 128, C.byref(n)))
+        return out[:n.value].copy()
+
+    def local_closure(self):
+        """test access: the last accepted local closure, until the next frame -> None, or dict(pinned, last_deform_time, src [rows, 3],
+        dst [rows, 3], time [rows], target_time [constraints], nodes [n, 4], params [n, 12])"""
+        found, rows, pinned, ldt, n = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        src = np.zeros((1536, 3), np.float32); dst = np.zeros((1536, 3), np.float32); tm = np.zeros(1536, np.float32); tt = np.zeros(1536, np.float32)
+        nodes = np.zeros((1024, 4), np.float32); params = np.zeros((1024, 12), np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.cofusion_local_closure_download(self.h, C.byref(found), C.byref(rows), C.byref(pinned), C.byref(ldt), vp(src), vp(dst), vp(tm),
+                                                             vp(tt), 1536, C.byref(n), vp(nodes), vp(params), 1024))
+        if not found.value:
+            return None
+        r, c = rows.value, rows.value // (2 if pinned.value else 1)
+        return dict(pinned=bool(pinned.value), last_deform_time=ldt.value, src=src[:r].copy(), dst=dst[:r].copy(), time=tm[:r].copy(),
+                    target_time=tt[:c].copy(), nodes=nodes[:n.value].copy(), params=params[:n.value].copy())
+
+    def relative_stats(self):
+        """-> dict(appended, overwritten, stored, used_by_last_closure, last_picked)"""
+        class _Stats(C.Structure):
+            _fields_ = [("appended", C.c_int64), ("overwritten", C.c_int64), ("stored", C.c_int32), ("used_by_last_closure", C.c_int32),
+                        ("last_picked", C.c_int32), ("pad", C.c_int32)]
+        assert C.sizeof(_Stats) == 32
+        s = _Stats()
+        self._check(self.lib.cofusion_relative_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in _Stats._fields_[:-1]}
+
     def set_redetection(self, on=True, min_fit=0.5, min_cover=0.044, depth_tol=0.10, max_candidates=8, keep_min_surfels=4000,
                         keep_conf_threshold=0.3):
         """Re-detection of inactive object models (cofusion_set_redetection): a frame with a new label scores the most

@@ -1543,7 +1543,88 @@ void CoFusion::localLoopAfterPredict()
     localSt.optimised += dr.optimised; localSt.accepted += dr.accepted; localSt.failed += dr.failed;
     if (!dr.accepted) return;
     localSt.deforms++;
+    localClosureLdt = localSt.lastDeformTime; localClosureRows = rec.n_constraints; localClosurePinned = pin;
     localSt.lastDeformTime = tick;
+    if (relativeOn) {   // CoFusion.cpp:445-458: the closure's own graph moves the picked sources; the pairs go to the GLOBAL graph's ring
+        float* targetTime = nullptr;
+        check(ctx, cf_local_loop_target_times(localLoop, &targetTime), "cf_local_loop_target_times");
+        const int stride = pin ? 2 : 1;
+        check(ctx, cf_deform_pick_relative(deform, localDeform, src, dst, time, targetTime, rec.n_constraints / stride, stride, &relLastPicked),
+              "cf_deform_pick_relative");
+    }
+}
+
+bool CoFusion::localClosureDownload(int* rows, int* pinned, int* lastDeformTime, float* src, float* dst, float* time, float* targetTime, int rowCapacity,
+                                    int* nodes, float* nodePos, float* params, int nodeCapacity)
+{
+    if (!localLoop || !localDeform || localSt.deforms == 0) return false;
+    const int n = localClosureRows, cons = n / (localClosurePinned ? 2 : 1);
+    if (rows) *rows = n;
+    if (pinned) *pinned = localClosurePinned;
+    if (lastDeformTime) *lastDeformTime = localClosureLdt;
+    check(ctx, cf_synchronize(ctx), "cf_synchronize");
+    float *s = nullptr, *d = nullptr, *t = nullptr, *tt = nullptr;
+    check(ctx, cf_local_loop_constraint_buffers(localLoop, &s, &d, &t), "cf_local_loop_constraint_buffers");
+    check(ctx, cf_local_loop_target_times(localLoop, &tt), "cf_local_loop_target_times");
+    if ((src || dst || time || targetTime) && rowCapacity < n) throw std::runtime_error("localClosureDownload: the row arrays are too small");
+    if (src && n) check(ctx, cf_memcpy_d2h(ctx, src, s, sizeof(float) * 3 * (uint64_t)n), "cf_memcpy_d2h");
+    if (dst && n) check(ctx, cf_memcpy_d2h(ctx, dst, d, sizeof(float) * 3 * (uint64_t)n), "cf_memcpy_d2h");
+    if (time && n) check(ctx, cf_memcpy_d2h(ctx, time, t, sizeof(float) * (uint64_t)n), "cf_memcpy_d2h");
+    if (targetTime && cons) check(ctx, cf_memcpy_d2h(ctx, targetTime, tt, sizeof(float) * (uint64_t)cons), "cf_memcpy_d2h");
+    int gn = 0;
+    check(ctx, cf_deform_download(localDeform, &gn, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "cf_deform_download");
+    if (nodes) *nodes = gn;
+    if (nodePos || params) {
+        if (nodeCapacity < gn) throw std::runtime_error("localClosureDownload: the node arrays are too small");
+        check(ctx, cf_deform_download(localDeform, nullptr, nullptr, nodePos, params, nullptr, nullptr, nullptr, nullptr, nullptr), "cf_deform_download");
+    }
+    return true;
+}
+
+void CoFusion::setRelativeConstraints(bool on)
+{
+    if (on && dist.world > 1) throw std::runtime_error("setRelativeConstraints: a single-GPU option, like reloc");
+    if (on && !ownsCtx) throw std::runtime_error("setRelativeConstraints: not available for a sequence of a lock-step group");
+    if (on) {
+        if (!deform) check(ctx, cf_deform_create(ctx, &deform), "cf_deform_create");
+        check(ctx, cf_deform_enable_relative(deform, CF_DEFORM_MAX_RELATIVE), "cf_deform_enable_relative");
+    } else if (relativeOn) check(ctx, cf_deform_set_relative(deform, nullptr, nullptr, nullptr, nullptr, 0, 0), "cf_deform_set_relative");
+    relativeOn = on;
+    relLastPicked = 0;
+}
+
+void CoFusion::addRelativeConstraints(const float* src, const float* dst, const float* srcTime, const float* dstTime, int n)
+{
+    if (!relativeOn) throw std::runtime_error("addRelativeConstraints: setRelativeConstraints first");
+    if (n < 0 || n > CF_DEFORM_MAX_RELATIVE || (n && (!src || !dst || !srcTime || !dstTime)))
+        throw std::runtime_error("addRelativeConstraints: 0..128 pairs, with their times");
+    check(ctx, cf_deform_set_relative(deform, src, dst, srcTime, dstTime, n, 1), "cf_deform_set_relative");
+}
+
+int CoFusion::relativeConstraints(float* out, int capacity)
+{
+    if (!relativeOn) return 0;
+    int count = 0;
+    check(ctx, cf_deform_download_relative(deform, nullptr, &count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+          "cf_deform_download_relative");
+    if (out && count) {
+        if (capacity < count) throw std::runtime_error("relativeConstraints: the output holds fewer pairs than the store");
+        check(ctx, cf_deform_download_relative(deform, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+              "cf_deform_download_relative");
+    }
+    return count;
+}
+
+CoFusion::RelativeStats CoFusion::relativeStats()
+{
+    RelativeStats s;
+    if (!relativeOn) return s;
+    int count = 0, used = 0;
+    int64_t appended = 0;
+    check(ctx, cf_deform_download_relative(deform, nullptr, &count, &appended, &used, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+          "cf_deform_download_relative");
+    s.appended = appended; s.stored = count; s.overwritten = appended - count; s.usedByLastClosure = used; s.lastPicked = relLastPicked;
+    return s;
 }
 
 // The first index maps of the surfel chain (Model::predictIndices before Model::fuse, CoFusion.cpp:316-318) enqueued BEHIND the

@@ -397,6 +397,25 @@ class CoFusion {
         cf_local_loop_record lastRecord{};                         // of the last examined frame
     };
     const LocalLoopStats& localLoopStats() const { return localSt; }
+    // Relative constraints (CoFusion.cpp:373, 445-458; DESIGN.md 4.14 "Relative rows"): what makes the two closures cooperate.  Off by
+    // default; with it off, or with no pair stored, every closure is what it was, launch for launch.  On: an accepted LOCAL closure
+    // leaves a few of its constraints behind as pairs (moved source, target, their times) in a device ring of 128 on the global graph
+    // (cf_deform_pick_relative, no host round trip), and every later GLOBAL closure -- the fern seam's and deformBackground's -- takes
+    // the stored pairs as rows 10 (phi(src) - phi(tgt)), so that it cannot pull apart what a local closure registered.  Switching it
+    // off keeps the allocation and empties the store.  Single process, not a sequence of a lock-step group.
+    void setRelativeConstraints(bool on);
+    // caller-supplied pairs, appended to the store as deformBackground takes caller-supplied constraints (host arrays [n][3], [n])
+    void addRelativeConstraints(const float* src, const float* dst, const float* srcTime, const float* dstTime, int n);
+    // the stored pairs in store order: out [capacity][8] (source xyz, srcTime, target xyz, dstTime); returns how many the store holds
+    int relativeConstraints(float* out, int capacity);
+    struct RelativeStats { long long appended = 0; long long overwritten = 0; int stored = 0; int usedByLastClosure = 0; int lastPicked = 0; };
+    RelativeStats relativeStats();
+    // test access: what the last accepted local closure worked on, readable until the next frame is processed -- its constraint rows
+    // (src, dst [rows][3], time [rows]; pinned: rows 2 k and 2 k + 1), the old time of every constraint (targetTime [rows or rows / 2]),
+    // the last_deform_time its graph was optimised with, and that graph (nodes [n][4], accepted params [n][12]).  Outputs nullable;
+    // rowCapacity / nodeCapacity: what the arrays hold.  Returns false when no local closure has been accepted.
+    bool localClosureDownload(int* rows, int* pinned, int* lastDeformTime, float* src, float* dst, float* time, float* targetTime, int rowCapacity,
+                              int* nodes, float* nodePos, float* params, int nodeCapacity);
     bool isGroupSequence() const { return !ownsCtx; }
     // Loop closure of the background map from caller-supplied constraints: sample the deformation graph, weight the
     // constraint points, optimise, and on acceptance move the map (cf_deform_*) and redo the prediction.  Returns the node count.
@@ -526,6 +545,9 @@ class CoFusion {
     LocalLoopStats localSt;
     bool fernClosedThisFrame = false;
     void localLoopAfterPredict();
+    bool relativeOn = false;        // setRelativeConstraints
+    int relLastPicked = 0;
+    int localClosureLdt = 0, localClosureRows = 0, localClosurePinned = 0;   // of the last accepted local closure (localClosureDownload)
     void releaseLocalLoop();
     // device frame buffers (CoFusion::textures)
     // filtered depth + its pyramid are double buffered: the filter of frame t+1 runs on an auxiliary stream while the fusion

@@ -217,6 +217,42 @@ int cofusion_local_loop_stats(cofusion_handle* h, cofusion_local_loop_stats_t* o
     return 0;
 }
 
+int cofusion_set_relative_constraints(cofusion_handle* h, int on)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->borrowed) { g_err = "relative constraints are not available for a sequence of a lock-step group"; return -1; }
+    GUARD(h->cf->setRelativeConstraints(on != 0));
+    return 0;
+}
+int cofusion_add_relative_constraints(cofusion_handle* h, const float* src, const float* dst, const float* src_time, const float* dst_time, int n)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    GUARD(h->cf->addRelativeConstraints(src, dst, src_time, dst_time, n));
+    return 0;
+}
+int cofusion_relative_constraints(cofusion_handle* h, float* out, int capacity, int* n)
+{
+    if (!h || !n) { g_err = "cofusion_relative_constraints: bad arguments"; return -1; }
+    GUARD(*n = h->cf->relativeConstraints(out, capacity));
+    return 0;
+}
+int cofusion_local_closure_download(cofusion_handle* h, int* found, int* rows, int* pinned, int* last_deform_time, float* src, float* dst, float* time,
+                                    float* target_time, int row_capacity, int* nodes, float* node_pos, float* params, int node_capacity)
+{
+    if (!h || !found) { g_err = "cofusion_local_closure_download: bad arguments"; return -1; }
+    GUARD(*found = h->cf->localClosureDownload(rows, pinned, last_deform_time, src, dst, time, target_time, row_capacity, nodes, node_pos, params,
+                                               node_capacity) ? 1 : 0);
+    return 0;
+}
+int cofusion_relative_stats(cofusion_handle* h, cofusion_relative_stats_t* out)
+{
+    if (!h || !out) { g_err = "cofusion_relative_stats: bad arguments"; return -1; }
+    CoFusion::RelativeStats s;
+    GUARD(s = h->cf->relativeStats());
+    *out = cofusion_relative_stats_t{s.appended, s.overwritten, s.stored, s.usedByLastClosure, s.lastPicked, 0};
+    return 0;
+}
+
 static Model* model_at(cofusion_handle* h, int index)
 {
     auto& l = h->cf->getModels();

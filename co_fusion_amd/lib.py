@@ -42,8 +42,11 @@ SYMBOLS = [
     "cf_deform_create", "cf_deform_destroy", "cf_deform_default_thresholds", "cf_deform_sample", "cf_deform_set_nodes", "cf_deform_weights", "cf_deform_assemble",
     "cf_deform_iterate", "cf_deform_optimise", "cf_deform_apply", "cf_deform_apply_poses", "cf_deform_download", "cf_deform_weights_device",
     "cf_deform_create_sized", "cf_deform_assemble_local", "cf_deform_iterate_local", "cf_deform_optimise_local",
+    "cf_deform_enable_relative", "cf_deform_set_relative", "cf_deform_set_relative_device", "cf_deform_pick_relative", "cf_deform_download_relative",
+    "cf_deform_download_out", "cf_deform_bench_relative_y",
     "cf_ferns_gate_async", "cf_ferns_gate_wait", "cf_ferns_constraints", "cf_ferns_find_frame", "cf_ferns_constraint_buffers", "cf_ferns_keyframe_buffers",
     "cf_local_loop_create", "cf_local_loop_destroy", "cf_local_loop_constraints_async", "cf_local_loop_wait", "cf_local_loop_constraint_buffers",
+    "cf_local_loop_target_times",
 ]
 
 
@@ -69,6 +72,7 @@ HOST_SYMBOLS = [
     "cofusion_save_ply", "cofusion_export_poses", "cofusion_set_export_segmentation", "cofusion_klg_open", "cofusion_klg_next", "cofusion_klg_set_reference_compatible", "cofusion_klg_close",
     "cofusion_klg_create", "cofusion_klg_write", "cofusion_klg_finish", "cofusion_debug_phase_ms", "cofusion_set_allreduce", "cofusion_set_allreduce_device", "cofusion_group_create", "cofusion_group_destroy", "cofusion_group_size", "cofusion_group_sequence", "cofusion_group_set_stream", "cofusion_group_process_frames", "cofusion_group_process_frames_device", "cofusion_rccl_unique_id", "cofusion_init_rccl", "cofusion_broadcast", "cofusion_model_owned", "cofusion_is_lost",
     "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats", "cofusion_deform_background", "cofusion_set_loop_closure", "cofusion_loop_stats", "cofusion_set_local_loop_closure", "cofusion_local_loop_stats",
+    "cofusion_set_relative_constraints", "cofusion_add_relative_constraints", "cofusion_relative_constraints", "cofusion_relative_stats", "cofusion_local_closure_download",
     "cofusion_set_redetection", "cofusion_redetect_stats", "cofusion_redetect_last", "cofusion_num_inactive_models",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",

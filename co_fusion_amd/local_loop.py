@@ -32,6 +32,7 @@ SIGNATURES = {
     "cf_local_loop_constraints_async": (_I, [_V, _V, C.POINTER(Track), _V, _V, _V, C.POINTER(C.c_float), _I, C.c_float, _I, C.POINTER(Thresholds)]),
     "cf_local_loop_wait": (_I, [_V, C.POINTER(Record)]),
     "cf_local_loop_constraint_buffers": (_I, [_V, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V)]),
+    "cf_local_loop_target_times": (_I, [_V, C.POINTER(_V)]),
 }
 
 
@@ -90,6 +91,18 @@ class LocalLoop:
         s, d, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx._check(self.lib.cf_local_loop_constraint_buffers(self.h, C.byref(s), C.byref(d), C.byref(t)))
         return s.value, d.value, t.value
+
+    def target_times_buffer(self):
+        """device address of target_time [768]: the old time of every constraint (pin rows not counted)"""
+        t = C.c_void_p()
+        self.ctx._check(self.lib.cf_local_loop_target_times(self.h, C.byref(t)))
+        return t.value
+
+    def target_times(self, n):
+        """the old times of the first n constraints, downloaded"""
+        host = np.zeros(max(n, 1), np.float32)
+        self.ctx._check(self.ctx.lib.cf_memcpy_d2h(self.ctx.h, host.ctypes.data_as(C.c_void_p), C.c_void_p(self.target_times_buffer()), C.c_uint64(4 * max(n, 1))))
+        return host[:n]
 
     def rows(self, n):
         """the first n rows, downloaded: src [n, 3], dst [n, 3], time [n]"""

@@ -135,8 +135,8 @@ int cofusion_loop_stats(cofusion_handle *h, cofusion_loop_stats_t *out);
  * camera pose and redoes the prediction.  Pins are added while no local closure has been accepted yet.  Values <= 0 of sample_rate,
  * icp_err_thresh, cov_thresh and < 0 of icp_count_thresh select the defaults 5000, 5e-5, 1e-5, 40000.  Needs time_delta > 0 and
  * (width / 20) * (height / 20) <= 768; needs no fern database; world == 1; refused for a sequence handle of a lock-step group.  Calling
- * it resets the statistics, deforms and last_deform_time included.  Off (the default): the frame loop is unchanged.  Not built: relative
- * constraints, the pose graph, object models. */
+ * it resets the statistics, deforms and last_deform_time included.  Off (the default): the frame loop is unchanged.  Relative
+ * constraints: cofusion_set_relative_constraints.  Not built: the pose graph, object models. */
 int cofusion_set_local_loop_closure(cofusion_handle *h, int on, int sample_rate, int icp_count_thresh, float icp_err_thresh, float cov_thresh,
                                     int min_inactive_pixels);
 typedef struct {
@@ -153,6 +153,37 @@ typedef struct {
     int32_t last_result[8];                               /* cf_deform_result of the last optimised graph */
 } cofusion_local_loop_stats_t;                            /* 168 bytes */
 int cofusion_local_loop_stats(cofusion_handle *h, cofusion_local_loop_stats_t *out);
+/* Relative constraints (DESIGN.md 4.14 "Relative rows"; CoFusion.cpp:373, 445-458): what makes the two closures cooperate.  With it on,
+ * every accepted LOCAL closure leaves a few of its constraints behind -- of its n constraints the indices 0, s, 2s, .. < n with
+ * s = max(1, n / 3), as pairs (source moved by the accepted graph, target, srcTime, the old time of the target's texel) -- in a store
+ * on the device: a ring of 128 pairs in which the newest overwrites the oldest.  Every later GLOBAL closure (the fern seam's and
+ * cofusion_deform_background's) adds the stored pairs as rows 10 (phi(src) - phi(tgt)) to its system, so it cannot pull apart surfaces
+ * a local closure has registered; its mean constraint error then divides by the number of ALL constraints, the stored pairs included
+ * (the reference's nonRelativeConstraintError), which lowers what the 0.06 gate and the 3e-4 accept rule see.  The pairs are world
+ * points and are not moved by later deformations, as in the reference.  Off (the default), or with an empty store: every closure is
+ * what it is without this call, launch for launch.  Switching it off empties the store.  The first call allocates 38 MB.  world == 1;
+ * refused for a sequence handle of a lock-step group. */
+int cofusion_set_relative_constraints(cofusion_handle *h, int on);
+/* caller-supplied pairs, appended to the store as cofusion_deform_background takes caller-supplied constraints: src, dst host [n][3],
+ * src_time, dst_time host [n], n <= 128.  Needs cofusion_set_relative_constraints on. */
+int cofusion_add_relative_constraints(cofusion_handle *h, const float *src, const float *dst, const float *src_time, const float *dst_time, int n);
+/* the stored pairs in store order: out (nullable) [capacity][8] = source xyz, srcTime, target xyz, dstTime; *n = how many the store holds */
+int cofusion_relative_constraints(cofusion_handle *h, float *out, int capacity, int *n);
+typedef struct {
+    int64_t appended, overwritten;       /* pairs ever appended; of those, lost to newer ones */
+    int32_t stored;                      /* pairs the store holds */
+    int32_t used_by_last_closure;        /* pairs in the system of the last global closure that reached the optimiser */
+    int32_t last_picked;                 /* pairs the last accepted local closure left */
+    int32_t pad;
+} cofusion_relative_stats_t;             /* 32 bytes */
+int cofusion_relative_stats(cofusion_handle *h, cofusion_relative_stats_t *out);
+/* Test access: what the last accepted local closure worked on, readable until the next frame is processed.  Host outputs, each nullable:
+ * rows (constraint rows, pins included), pinned (rows 2 k are constraints, 2 k + 1 their pins), last_deform_time (what its graph was
+ * optimised with), src, dst [row_capacity][3], time [row_capacity], target_time [row_capacity] (the old time of every constraint: rows
+ * or rows / 2 values), nodes (the graph's node count), node_pos [node_capacity][4], params [node_capacity][12] (the accepted ones).
+ * *found = 0 and nothing written when no local closure has been accepted. */
+int cofusion_local_closure_download(cofusion_handle *h, int *found, int *rows, int *pinned, int *last_deform_time, float *src, float *dst, float *time,
+                                    float *target_time, int row_capacity, int *nodes, float *node_pos, float *params, int node_capacity);
 /* Re-detection of inactive object models (the reference's CoFusion::redetectModels is an empty hook, CoFusion.cpp:599-602).
  * A model whose label gets no superpixels is deactivated; kept models (surfel count >= keep_min_surfels and confidence threshold >
  * keep_conf_threshold -- 4000 / 0.3, the reference's rule) wait in a list.  Off (the default) nothing reads that list: an object that

@@ -953,7 +953,8 @@ int cf_profile_read(cf_ctx *ctx, cf_profile *out, int reset);
  * CF_DEFORM_MAX_CONSTRAINTS_SIZED): about 24 MB, nearly all of it the band of the normal matrix.  The calls are rare and synchronous
  * (each waits for the context's stream) except cf_deform_apply and cf_deform_apply_poses, which only enqueue.  The constraints of a local
  * closure come from cf_local_loop_* (cofusion_loop.h) behind the model-to-model tracker (cf_odom_init_icp_maps); the frame loop that strings
- * them together is CoFusion::setLocalLoopClosure.  Not built: relative constraints, the pose graph, object models. */
+ * them together is CoFusion::setLocalLoopClosure.  Relative constraints: below cf_deform_download.  Not built: the pose graph, object
+ * models. */
 #define CF_DEFORM_MAX_NODES 1024
 #define CF_DEFORM_MAX_CONSTRAINTS 128
 #define CF_DEFORM_MAX_CONSTRAINTS_SIZED 1536   /* a local closure at 640x480: 768 constraints and 768 pins */
@@ -1019,6 +1020,44 @@ int cf_deform_apply_poses(cf_deform *d, float *poses_dev, const int32_t *times_d
  * cf_deform_iterate: delta) */
 int cf_deform_download(cf_deform *d, int *n_nodes, int *n_constraints, float *nodes, float *params, int32_t *edges, int32_t *ids, float *weights,
                        double *A_band, double *b);
+
+/* Relative constraints (CoFusion.cpp:373, 445-458; DeformationGraph.cpp:578-654): every accepted LOCAL closure leaves a few pairs
+ * (moved source, target, srcTime, dstTime) behind, and every later GLOBAL step takes them as rows 10 (phi(src) - phi(tgt)) behind the
+ * absolute constraints, so that a fern closure cannot pull apart what a local closure registered.  The pairs live in a device ring of
+ * `capacity` (CF_DEFORM_MIN_RELATIVE .. CF_DEFORM_MAX_RELATIVE) slots: pair number k ever appended is in slot k mod capacity, the
+ * newest overwrites the oldest, and the rows follow slot order.  The pairs are world points; later deformations do not move them.
+ * A relative row couples node groups arbitrarily far apart, which the band cannot hold: with pairs in the ring cf_deform_assemble /
+ * cf_deform_iterate / cf_deform_optimise solve A = B + U^T U on the band factor of B (y = L^-1 b, Y = L^-1 U^T, C = I + Y^T Y,
+ * t = C^-1 Y^T y, delta = L^-T (y - Y t)); error counts the relative rows, and mean_cons_error divides the sum over the absolute
+ * constraints by the number of ALL constraints (nonRelativeConstraintError).  With the ring empty every launch is the one of an
+ * object without it.  The *_local calls answer CF_EINVAL while the ring holds pairs.  Off until enabled: the storage (38 MB at 128
+ * pairs, nearly all of it Y) is allocated by this call, not by cf_deform_create. */
+#define CF_DEFORM_MAX_RELATIVE 128
+#define CF_DEFORM_MIN_RELATIVE 8
+int cf_deform_enable_relative(cf_deform *d, int capacity);
+/* n pairs from host arrays (src, dst [n][3], src_time, dst_time [n]); append = 0: the ring is emptied first (n = 0 only empties it) */
+int cf_deform_set_relative(cf_deform *d, const float *src, const float *dst, const float *src_time, const float *dst_time, int n, int append);
+/* the same from device arrays: one scatter launch, no copy through the host.  Enqueued only. */
+int cf_deform_set_relative_device(cf_deform *d, const float *src_dev, const float *dst_dev, const float *src_time_dev, const float *dst_time_dev,
+                                  int n, int append);
+/* what an accepted closure of the graph `from` leaves, no host round trip: of its n constraints (device rows row_stride * i of src, dst
+ * [.][3] and time [.]; dst_time_dev [n], one per constraint) the indices 0, s, 2s, .. < n with s = max(1, n / 3); each source is moved by
+ * `from` as cf_deform_apply would move a surfel there and appended to d's ring with its target.  Enqueued only.  picked: how many. */
+int cf_deform_pick_relative(cf_deform *d, cf_deform *from, const float *src_dev, const float *dst_dev, const float *time_dev, const float *dst_time_dev,
+                            int n, int row_stride, int *picked);
+/* test access, host outputs, each nullable: the ring's capacity, the pairs it holds, the pairs ever appended, the pairs in the system of
+ * the last cf_deform_optimise; pairs [count][8] (source xyz, srcTime, target xyz, dstTime) in slot order; after cf_deform_assemble or
+ * later: ids and weights [2][count][4] (sources, then targets), U in compact form u_ids [count][8] (node of each slot, -1: unused) and
+ * u_vals [count][8][4], r_rel [3 count]; after cf_deform_iterate: C [3 count + 1][3 count] = I + Y^T Y (symmetric) with Y^T y as its
+ * last row */
+int cf_deform_download_relative(cf_deform *d, int *capacity, int *count, int64_t *appended, int *used, float *pairs, int32_t *ids, float *weights,
+                                int32_t *u_ids, double *u_vals, double *r_rel, double *C);
+/* test access: the 32-byte record the last residual pass / solve left on the device (error, mean_cons_error f32; delta_norm f64;
+ * failed, enabled i32; two words of padding), copied out as it stands */
+int cf_deform_download_out(cf_deform *d, void *out32);
+/* benchmark access: only the launch Y = L^-1 U^T of a step with relative rows, on the state the last cf_deform_iterate left (its band
+ * factor and its rows); it rewrites Y with the same bytes.  Enqueued only. */
+int cf_deform_bench_relative_y(cf_deform *d);
 
 #ifdef __cplusplus
 }

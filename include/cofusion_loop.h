@@ -95,5 +95,8 @@ int cf_local_loop_constraints_async(cf_local_loop *l, const cf_odom *od, const c
 int cf_local_loop_wait(cf_local_loop *l, cf_local_loop_record *out);
 /* device arrays the kernel writes: src, dst f32 [1536][3], time f32 [1536] */
 int cf_local_loop_constraint_buffers(cf_local_loop *l, float **src, float **dst, float **time);
+/* a fourth device array of the same launch: target_time f32 [768], the old time of constraint k (one per constraint, pin rows not
+ * counted), written with or without pins -- what cf_deform_pick_relative keeps as dstTime */
+int cf_local_loop_target_times(cf_local_loop *l, float **target_time);
 
 #endif /* COFUSION_LOOP_H_ */

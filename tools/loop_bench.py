@@ -23,7 +23,15 @@ constraints; the model-to-model tracker (preparation through cf_odom_init_icp_ma
 the smoke test at 640x480, and the constraint launch + the wait on its record.  (The frame loop is not built: no closing frame, no
 objects4 leg.)
 
+With --relative, the step with relative constraints, merged into the same file under "relative" (medians of --iters by in-stream
+events, read-back included): assemble and iterate at 40 / 200 / 1024 nodes with the 100 shift constraints and 0 / 16 / 128 stored pairs
+between the newest and the oldest nodes, on an object with the ring enabled, beside iterate on an object without it (0 pairs launches
+the same kernels: the two must agree within the run-to-run spread, which the repeated "plain" figure shows), and the launch
+Y = L^-1 U^T on its own (cf_deform_bench_relative_y on the state an iteration left).  The other kernels' own times come from a kernel
+trace of this leg taken in a run of its own.
+
     python tools/loop_bench.py [--iters 30] [--no-frames]
+    python tools/loop_bench.py --relative
     python tools/loop_bench.py --local
     python tools/loop_bench.py --seam [--steps 300] [--warmup 30] [--rounds 3] [--min-age 30]
 """
@@ -93,6 +101,36 @@ def stages(torch, iters):
             apply[f"{n}_nodes_{s}_surfels"] = dict(ms=ms, bytes=80 * s, share_of_peak=80 * s / (ms * 1e-3) / PEAK_BPS)
     d.close(); ctx.close()
     return dict(stages=out, apply=apply)
+
+
+def relative_legs(torch, iters):
+    import deform_cases as dc
+    import deform_rel_cases as rc
+    from co_fusion_amd import api, deform
+    ctx = api.Context(640, 480, 528.0, 528.0, 320.0, 240.0, max_models=2, max_surfels=1 << 16)
+    plain, d = deform.Deform(ctx), deform.Deform(ctx)
+    d.enable_relative()
+    out = {}
+    for n in (40, 200, 1024):
+        nodes = dc.make_nodes(n)
+        src, dst, tm = dc.constraints("shift", nodes)
+        row = {}
+        for name, obj, pairs in (("plain", plain, None), ("0_pairs", d, 0), ("16_pairs", d, 16), ("128_pairs", d, 128), ("plain_again", plain, None)):
+            def reset():
+                obj.set_nodes(nodes); obj.weights(src, dst, tm)
+                if pairs is not None:
+                    obj.set_relative(rc.pairs_between(nodes, np.arange(n - 8, n), np.arange(8), pairs))
+            reset()
+            row[name + "_assemble_ms"] = median_ms(torch, obj.assemble, iters)
+            row[name + "_iterate_ms"] = median_ms(torch, obj.iterate, iters, before=reset)
+            reset()
+            step = obj.iterate()
+            row[name + "_step"] = dict(error=float(step["error"]), failed=bool(step["failed"]))
+            if pairs:   # the Y launch on its own, on the factor and the rows that step left
+                row[name + "_y_launch_ms"] = median_ms(torch, obj.bench_relative_y, iters)
+        out[str(n)] = row
+    plain.close(); d.close(); ctx.close()
+    return out
 
 
 def local_legs(torch, iters=20):
@@ -391,6 +429,7 @@ def main():
     ap.add_argument("--no-frames", action="store_true")
     ap.add_argument("--seam", action="store_true", help="only the legs of the fern seam (written to the 'seam' entry of profiles/loop_bench.json)")
     ap.add_argument("--local", action="store_true", help="only the legs of local loop closure (the 'local' entry of profiles/loop_bench.json)")
+    ap.add_argument("--relative", action="store_true", help="only the step with relative constraints (the 'relative' entry of profiles/loop_bench.json)")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
@@ -398,6 +437,13 @@ def main():
     a = ap.parse_args()
     import torch
     path = os.path.join(ROOT, "profiles", "loop_bench.json")
+    if a.relative:
+        out = json.load(open(path)) if os.path.exists(path) else {}
+        out["relative"] = relative_legs(torch, a.iters)
+        print(json.dumps(out["relative"]))
+        with open(path, "w") as f:
+            f.write(json.dumps(out) + "\n")
+        return
     if a.local:
         out = json.load(open(path)) if os.path.exists(path) else {}
         out["local"] = local_legs(torch)

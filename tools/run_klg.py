@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--close-local-loops", action="store_true", help="local loop closure: the active view of the background map is registered onto "
                                                                       "the inactive one in every frame (a second tracking loop per frame); needs no --relocalise")
     ap.add_argument("--local-sample-rate", type=int, default=5000, help="every N-th surfel is a node of the local deformation graph")
+    ap.add_argument("--relative-constraints", action="store_true", help="an accepted local closure leaves pairs behind that every later global "
+                                                                         "closure keeps together (with --close-loops and --close-local-loops)")
     ap.add_argument("--time-delta", type=int, default=0, help="ticks after which an unseen surfel is inactive (0: never; ElasticFusion's 200 with "
                                                               "--close-loops)")
     ap.add_argument("--redetect", action="store_true", help="an object that is labelled again resumes its kept inactive model (old id and map) "
@@ -113,6 +115,8 @@ def main():
         cf.set_loop_closure(True, sample_rate=a.loop_sample_rate)
     if a.close_local_loops:
         cf.set_local_loop_closure(True, sample_rate=a.local_sample_rate)
+    if a.relative_constraints:
+        cf.set_relative_constraints(True)
     if a.redetect:
         if a.static:
             raise SystemExit("--redetect needs the multi-model mode (no --static)")
@@ -187,6 +191,8 @@ def main():
         print(f"loop closure: {cf.loop_stats()}")
     if a.close_local_loops:
         print(f"local loop closure: {cf.local_loop_stats()}")
+    if a.relative_constraints:
+        print(f"relative constraints: {cf.relative_stats()}")
     if a.redetect:
         print(f"re-detection: {cf.redetect_stats()}, {cf.num_inactive_models} inactive model(s) kept")
     if a.export_async:
