@@ -58,6 +58,13 @@ class GnSystem(C.Structure):
                 ("hot", C.c_uint32 * 48)]
 
 
+class So3System(C.Structure):
+    """cf_so3_system: one system of cf_so3_prealign_step (the two level-2 images on the device, the state in and out, the derived hot
+    block, the system's sync block as the launch left it)"""
+    _fields_ = [("last_next_image", C.c_void_p), ("next_image", C.c_void_p), ("state_in", GnState), ("state_out", GnState), ("hot", C.c_uint32 * 48),
+                ("sync", C.c_uint64 * 418)]
+
+
 class Profile(C.Structure):
     _fields_ = [("icp_ms_total", C.c_double), ("icp_launches", C.c_uint64), ("icp_bytes", C.c_uint64),
                 ("surfel_ms_total", C.c_double), ("surfel_calls", C.c_uint64), ("surfel_bytes", C.c_uint64)]
@@ -281,6 +288,14 @@ class Context:
         block and both accumulators as the kernel left them"""
         arr = systems if isinstance(systems, C.Array) else (GnSystem * len(systems))(*systems)
         self._check(self.lib.cf_gn_solve_step(self.h, len(arr), arr, int(next_level), int(bool(last_of_level)), int(icp_fix)))
+        return arr
+
+    def so3_prealign_step(self, systems, do_so3=True, first_level=2):
+        """cf_so3_prealign_step: the first launch of a tracking call on its own -- state hand-over and, when do_so3, the SO(3)
+        pre-alignment loop, 16 workgroups per system.  systems: a ctypes array of So3System (updated in place) or a sequence of
+        them (copied); returns the array with the device state, the hot block and the sync block of every system"""
+        arr = systems if isinstance(systems, C.Array) else (So3System * len(systems))(*systems)
+        self._check(self.lib.cf_so3_prealign_step(self.h, len(arr), arr, int(bool(do_so3)), int(first_level)))
         return arr
 
     def set_icp_launch(self, threads, ppt):

@@ -1,5 +1,6 @@
 // cabi_steps.hip -- C-ABI: the single-function entries.  Map-preparation wrappers, the stand-alone reduction steps on the context's
-// scratch state (C-ABI parity with icpStep / computeRgbResidual / rgbStep / so3Step) and one Gauss-Newton solve on its own.
+// scratch state (C-ABI parity with icpStep / computeRgbResidual / rgbStep / so3Step), one Gauss-Newton solve and the SO3 pre-alignment
+// launch on their own.
 #include <math.h>
 #include <string.h>
 
@@ -100,7 +101,7 @@ void gn_state_from_dev(const OdomDev* h, cf_gn_state* g)  // every word back, th
     g->lastRGBError = h->lastRGBError; g->level_done = h->level_done; g->solves = h->solves; memcpy(g->residual, h->residual, 8);
     memcpy(g->cull_z, h->cull_z, 8); memcpy(g->pose_inv, h->pose_inv, sizeof(g->pose_inv)); g->stats = h->stats;
 }
-struct GnStepBuffers {   // temporaries of one cf_gn_solve_step call
+struct GnStepBuffers {   // temporaries of one cf_gn_solve_step / cf_so3_prealign_step call
     hipStream_t stream = nullptr;
     OdomDev* d_states = nullptr; unsigned long long* d_acc = nullptr; OdomDev* h_twins = nullptr;
     // (an entry that fails half way returns with copies and the launch still enqueued: nothing they touch is released before the stream is idle)
@@ -308,6 +309,44 @@ int cf_gn_solve_step(cf_ctx* ctx, int n, cf_gn_system* systems, int next_level, 
         gn_state_from_dev(&h[(size_t)k], &systems[k].state);
         gn_state_from_dev(&buf.h_twins[k], &systems[k].twin);
         memcpy(systems[k].hot, &h[(size_t)k].hot, sizeof(GnHot));
+    }
+    return CF_OK;
+}
+
+// The first launch of a tracking call on its own: so3_prealign_kernel as the schedule launches it (launch_so3_prealign), on temporary
+// pinned host states filled from the caller's words and temporary device states filled with a pattern -- the launch uploads them.
+int cf_so3_prealign_step(cf_ctx* ctx, int n, cf_so3_system* systems, int do_so3, int first_level)
+{
+    if (!ctx || !systems || n < 1 || n > kMaxBatch || n > ctx->cfg.max_models || first_level < 0 || first_level > 2) return CF_EINVAL;
+    static_assert(sizeof(systems->sync) == sizeof(So3Sync) && sizeof(systems->hot) == sizeof(GnHot), "cf_so3_system mirrors the sync and the hot block");
+    for (int k = 0; k < n; k++) {
+        const cf_gn_state& g = systems[k].state_in;
+        if (g.width <= 0 || g.height <= 0 || (g.width % 16) || (g.height % 4)) return CF_EINVAL;
+        if (do_so3 && (!systems[k].last_next_image || !systems[k].next_image)) return CF_EINVAL;
+    }
+    std::vector<OdomDev> back((size_t)n);   // (declared in front of buf: destroyed behind its synchronisation)
+    GnStepBuffers buf;
+    buf.stream = ctx->stream;
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_states), sizeof(OdomDev) * n));
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&buf.h_twins), sizeof(OdomDev) * n, hipHostMallocCoherent));  // the launch reads them
+    HIPCHK(ctx, hipMemsetAsync(buf.d_states, 0xA5, sizeof(OdomDev) * n, ctx->stream));   // a word the launch does not upload keeps the pattern
+    TrackerStates states{};
+    for (int k = 0; k < n; k++) {
+        OdomDev* s = &buf.h_twins[k];
+        memset(s, 0, sizeof(*s));   // (cull 0, no bounding-box accumulator)
+        gn_state_to_dev(systems[k].state_in, s);
+        s->lastNextImage[2] = systems[k].last_next_image; s->nextImage[2] = systems[k].next_image;
+        states.dev[k] = buf.d_states + k; states.host[k] = s;
+    }
+    launch_so3_prealign(ctx->stream, states, ctx->d_so3_sync, n, do_so3 != 0, first_level, nullptr);
+    LAUNCHCHK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(back.data(), buf.d_states, sizeof(OdomDev) * n, hipMemcpyDeviceToHost, ctx->stream));
+    for (int k = 0; k < n; k++)
+        HIPCHK(ctx, hipMemcpyAsync(systems[k].sync, ctx->d_so3_sync + k, sizeof(So3Sync), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) {
+        gn_state_from_dev(&back[(size_t)k], &systems[k].state_out);
+        memcpy(systems[k].hot, &back[(size_t)k].hot, sizeof(GnHot));
     }
     return CF_OK;
 }

@@ -351,6 +351,9 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
                      OdomDev* const* h_states = nullptr /* [n] pinned host copies the last solve publishes to */,
                      const RgbPrepBatch* prep = nullptr /* n <= kPrepBatch models' RGB preparation (levels filled: rgb_prep_levels), run in the
                                                            first launch beside the SO3 pre-alignment */);
+// the first launch of that schedule on its own (cf_so3_prealign_step): so3_prealign_kernel as launch_gn_track launches it
+void launch_so3_prealign(hipStream_t s, const TrackerStates& states, So3Sync* so3_syncs /* [n] */, int n, bool so3, int first_level,
+                         const RgbPrepBatch* prep /* nullable */);
 void rgb_prep_levels(RgbPrepBatch& b, int n, int W, int H);
 float replay_icp_level0(hipStream_t s, IcpLaunch cfg, const IcpArgs& a0, const RgbArgs& r0, int n, int slots, int ablate, int reps, hipEvent_t e0, hipEvent_t e1);
 #ifdef CF_ABLATE

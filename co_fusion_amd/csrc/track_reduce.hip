@@ -873,6 +873,16 @@ void launch_icp_level(hipStream_t s, IcpLaunch cfg, const IcpArgs& args, int n, 
 // grid barrier, a chain of about five device-scope memory round trips of ~1.5 us each across the XCDs, whereas a dependent
 // launch costs ~2.5 us (tools/microbench/launch_floor.hip).  On this part the kernel boundary IS the cheapest grid barrier.
 // Kept as separate launches.
+// The first launch of the schedule (so3_prealign_kernel): state hand-over, the SO3 pre-alignment when `so3`, the RGB preparation of
+// `prep` beside it.  On its own behind cf_so3_prealign_step.
+void launch_so3_prealign(hipStream_t s, const TrackerStates& states, So3Sync* so3_syncs, int n, bool so3, int first_level, const RgbPrepBatch* prep)
+{
+    const int gx = so3 ? 8 * kSo3Blocks : 1;  // (8x: one XCD per model)
+    static const RgbPrepBatch none{};
+    const int prep_bx = prep ? prep->m[0].L.blk_end[2] : 0;
+    so3_prealign_kernel<<<gx * n + prep_bx * n, 256, 0, s>>>(states, so3_syncs, so3 ? 1 : 0, first_level, gx, gx * n, prep ? *prep : none, prep_bx);
+}
+
 bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, So3Sync* so3_syncs, const GnHook* hook, const IcpArgs icp_args[3],
                      const RgbArgs rgb_args[3], int n, int width, int height, bool so3, bool pyramid, bool fast_odom, bool rgb, bool icp, int mode,
                      ProfSink* prof, OdomDev* const* h_states, const RgbPrepBatch* prep)
@@ -883,12 +893,7 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
     iterations[2] = pyramid ? 4 : 0;
     int first_level = 2;
     while (first_level > 0 && iterations[first_level] == 0) first_level--;
-    {
-        const int gx = so3 ? 8 * kSo3Blocks : 1;  // (8x: one XCD per model)
-        static const RgbPrepBatch none{};
-        const int prep_bx = prep ? prep->m[0].L.blk_end[2] : 0;
-        so3_prealign_kernel<<<gx * n + prep_bx * n, 256, 0, s>>>(states, so3_syncs, so3 ? 1 : 0, first_level, gx, gx * n, prep ? *prep : none, prep_bx);
-    }
+    launch_so3_prealign(s, states, so3_syncs, n, so3, first_level, prep);
     GnArgs gn{};
     gn.icp_gram = cfg.gram;
     gn.slot_px = cfg.threads * 4;

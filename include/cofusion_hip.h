@@ -287,6 +287,23 @@ typedef struct {
  * evaluated); last_of_level: the iteration ends its level (re-arms the RGB-only stop rule); icp_fix: fraction bits of the ICP sums
  * (CF_FIX_ICP), or -1 for the Gram form's per-word bits.  Synchronous.  n out of range or a null pointer: CF_EINVAL, nothing enqueued. */
 int cf_gn_solve_step(cf_ctx *ctx, int n, cf_gn_system *systems, int next_level, int last_of_level, int icp_fix);
+/* The first launch of a tracking call on its own: the SO(3) pre-alignment (RGBDOdometry.cpp:239-310) with the state hand-over around
+ * it, as the schedule launches it -- 16 workgroups per system on one XCD, meeting at the context's sync blocks -- without the RGB
+ * preparation workgroups that share the launch in production, screen-box culling off. */
+typedef struct {
+    const uint8_t *last_next_image;   /* device, level 2: (width >> 2) x (height >> 2) intensities (lastNextImage[2]); not read unless do_so3 */
+    const uint8_t *next_image;        /* ... nextImage[2] */
+    cf_gn_state state_in;             /* what the tracker's pinned host state holds: width, height and intr (level 0) are read, every word
+                                       * is handed to the device state */
+    cf_gn_state state_out;            /* out: the device state after the launch (pre-filled with a pattern before it) */
+    uint32_t hot[48];                 /* out: the derived block of that state */
+    uint64_t sync[418];               /* out: this system's sync block as the launch left it, every word (all zero between launches) */
+} cf_so3_system;
+/* One launch for `n` systems, 1 <= n <= min(16, max_models), system k on sync block k of the context.  do_so3 == 0: the launch of a
+ * tracking call without pre-alignment (one workgroup per system: hand-over and seeding only).  first_level: the pyramid level (0..2)
+ * krkInv / kt are prepared for.  Synchronous.  n or first_level out of range, a null pointer (the images when do_so3), a width that is
+ * no multiple of 16 or a height that is no multiple of 4: CF_EINVAL, nothing enqueued. */
+int cf_so3_prealign_step(cf_ctx *ctx, int n, cf_so3_system *systems, int do_so3, int first_level);
 /* pixels the level-0 {ICP reduction || RGB residual} launch of the last fetched tracking call visited for this tracker: the 64-pixel
  * runs inside its final screen box and the record slots between its first and last RGB candidate (the whole image for a tracker
  * that is not culled) -- the physical byte count of a roofline figure, as opposed to SURVEY 8(d)'s every-pixel-to-every-tracker */

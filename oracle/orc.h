@@ -172,6 +172,25 @@ typedef struct {
  * of the ICP totals, or -1 for the Gram form's per-word bits; trace nullable */
 void orc_gn_solve_step(orc_gn_state *s, const int64_t icp_tot[32], const int64_t rgb_tot[32], int next_level, int last_of_level,
                        int icp_fix, orc_gn_trace *trace);
+/* The SO(3) pre-alignment on its own (RGBDOdometry.cpp:239-310), as orc_odom_get_incremental_transformation runs it under the exact
+ * arithmetic: up to ten passes of orc_so3_step over the level-2 intensity images `last` / `next` ((width >> 2) x (height >> 2)), each
+ * followed by the f32 3x3 LDL^T, Rodrigues in f64 and the f32 product into the accumulated rotation.  intr / width / height: level 0.
+ * resultR (row-major f64, out) starts from the identity; stats receives so3_iterations, last_so3_error and last_so3_count and nothing
+ * else.  The optional trace says what every iteration saw and did: its error and count as computed (before a revert replaces them with
+ * the previous iteration's), the branch taken and the pivots its solve took as zero. */
+enum { ORC_SO3_STEP = 0, ORC_SO3_CONVERGED = 1, ORC_SO3_REVERTED = 2 };
+typedef struct {
+    float err[10], count[10];
+    int32_t branch[10];               /* ORC_SO3_STEP: solved and went on; _CONVERGED / _REVERTED: the iteration the loop left at */
+    int32_t zero_pivots[10];          /* of the three pivots of a STEP's solve */
+    int32_t iterations;
+} orc_so3_trace;
+void orc_so3_prealign(const uint8_t *last, const uint8_t *next, orc_cam intr, int width, int height, double resultR[9],
+                      orc_track_stats *stats, orc_so3_trace *trace);
+/* ... and what the device's first launch of a tracking call leaves in the state besides: resultRt (identity, or the rotation when
+ * do_so3), krkInv / kt of the first iteration at `first_level`, lastRGBError = FLT_MAX, level_done = 0, residual = {0, 0}, and the
+ * three SO(3) statistics (zero when !do_so3).  Reads intr, width, height of *s; last / next are not read when !do_so3. */
+void orc_so3_prealign_state(orc_gn_state *s, const uint8_t *last, const uint8_t *next, int do_so3, int first_level);
 /* the host algebra of the reference-order mode (ORC_ICP_ARITH_REFERENCE): the left-looking pivoted LDL^T solve, N <= 6, row-major */
 void eig_ldlt_solve_d(int N, const double *A, const double *b, double *x);
 void eig_ldlt_solve_f(int N, const float *A, const float *b, float *x);

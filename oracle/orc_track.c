@@ -1186,6 +1186,76 @@ void orc_gn_solve_step(orc_gn_state *s, const int64_t icp_tot[32], const int64_t
     trace->active = active; trace->stop = stop;
 }
 
+/* The SO(3) pre-alignment loop, RGBDOdometry.cpp:239-310 (orc.h) */
+void orc_so3_prealign(const uint8_t *last, const uint8_t *next, orc_cam intr, int width, int height, double resultR[9],
+                      orc_track_stats *st, orc_so3_trace *trace)
+{
+    const int L = 2, cols = width >> L, rows = height >> L;
+    orc_so3_trace local; if (!trace) trace = &local;
+    memset(trace, 0, sizeof(*trace));
+    for (int k = 0; k < 9; k++) resultR[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    float R_lr[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double K[9], Kinv[9];
+    k_matrix(cam_level(intr, L), K);
+    orc_inv33d(K, Kinv);
+    float lastError = FLT_MAX / 2, lastCount = FLT_MAX / 2;
+    double lastResultR[9]; memcpy(lastResultR, resultR, sizeof(lastResultR));
+    for (int it = 0; it < 10; it++) {
+        double tmp[9], H[9], KR[9];
+        orc_mul33d(K, resultR, tmp); orc_mul33d(tmp, Kinv, H);
+        memcpy(KR, tmp, sizeof(tmp));
+        float basis[9], kinvf[9], krlr[9];
+        for (int k = 0; k < 9; k++) { basis[k] = (float)H[k]; kinvf[k] = (float)Kinv[k]; krlr[k] = (float)KR[k]; }
+        int64_t sums[ORC_SO3_WORDS];
+        float jtj[9], jtr[3], residual[2];
+        orc_so3_step(last, next, basis, kinvf, krlr, cols, rows, sums);
+        orc_so3_sums_to_host(sums, ORC_FIX_SO3, jtj, jtr, residual);
+        st->so3_iterations = it + 1;
+        st->last_so3_error = sqrtf(residual[0]) / residual[1];
+        st->last_so3_count = residual[1];
+        trace->iterations = it + 1;
+        trace->err[it] = st->last_so3_error; trace->count[it] = st->last_so3_count;
+        /* "Converged": compares lastError with lastSO3Count (sic), :285 */
+        if (st->last_so3_error < lastError && (double)fabsf(lastError - st->last_so3_count) < 0.001) { trace->branch[it] = ORC_SO3_CONVERGED; break; }
+        else if ((double)st->last_so3_error > (double)lastError + 0.001) {
+            st->last_so3_error = lastError; st->last_so3_count = lastCount;
+            memcpy(resultR, lastResultR, sizeof(lastResultR));
+            trace->branch[it] = ORC_SO3_REVERTED;
+            break;
+        }
+        trace->branch[it] = ORC_SO3_STEP;
+        lastError = st->last_so3_error; lastCount = st->last_so3_count;
+        memcpy(lastResultR, resultR, sizeof(lastResultR));
+        float delta[3];
+        orc_ldlt_trace lt;
+        orc_ldlt_f(3, jtj, jtr, delta, &lt);
+        trace->zero_pivots[it] = lt.zero[0] + lt.zero[1] + lt.zero[2];
+        double dd[3] = {delta[0], delta[1], delta[2]}, rotUpdate[9];
+        orc_rodrigues(dd, rotUpdate);
+        float ru[9], nr[9];
+        for (int k = 0; k < 9; k++) ru[k] = (float)rotUpdate[k];
+        orc_mul33f(ru, R_lr, nr);
+        memcpy(R_lr, nr, sizeof(nr));
+        for (int k = 0; k < 9; k++) resultR[k] = R_lr[k];
+    }
+}
+
+/* What the first launch of a tracking call leaves behind for the Gauss-Newton loop (orc.h) */
+void orc_so3_prealign_state(orc_gn_state *s, const uint8_t *last, const uint8_t *next, int do_so3, int first_level)
+{
+    double resultR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    s->stats.so3_iterations = 0; s->stats.last_so3_error = 0; s->stats.last_so3_count = 0;
+    if (do_so3) orc_so3_prealign(last, next, s->intr, s->width, s->height, resultR, &s->stats, 0);
+    for (int k = 0; k < 16; k++) s->resultRt[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    if (do_so3)
+        for (int x = 0; x < 3; x++)
+            for (int y = 0; y < 3; y++) s->resultRt[x * 4 + y] = resultR[x * 3 + y];
+    s->lastRGBError = FLT_MAX;
+    s->level_done = 0;
+    s->residual[0] = 0; s->residual[1] = 0;
+    gn_prepare_iteration(s, first_level);
+}
+
 /* RGBDOdometry::getIncrementalTransformation, RGBDOdometry.cpp:217-477 */
 void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], float rot[9], const orc_track_opts *opts,
                                              float *icp_err_surface, orc_track_stats *st)
@@ -1206,47 +1276,7 @@ void orc_odom_get_incremental_transformation(orc_odometry *o, float trans[3], fl
 
     double resultR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
-    if (opts->so3) { /* :239-310 */
-        const int L = 2, cols = o->width >> L, rows = o->height >> L;
-        float R_lr[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        double K[9], Kinv[9];
-        k_matrix(cam_level(o->intr, L), K);
-        orc_inv33d(K, Kinv);
-        float lastError = FLT_MAX / 2, lastCount = FLT_MAX / 2;
-        double lastResultR[9]; memcpy(lastResultR, resultR, sizeof(resultR));
-        for (int it = 0; it < 10; it++) {
-            double tmp[9], H[9], KR[9];
-            orc_mul33d(K, resultR, tmp); orc_mul33d(tmp, Kinv, H);
-            memcpy(KR, tmp, sizeof(tmp));
-            float basis[9], kinvf[9], krlr[9];
-            for (int k = 0; k < 9; k++) { basis[k] = (float)H[k]; kinvf[k] = (float)Kinv[k]; krlr[k] = (float)KR[k]; }
-            int64_t sums[ORC_SO3_WORDS];
-            float jtj[9], jtr[3], residual[2];
-            orc_so3_step(o->lastNextImage[L], o->nextImage[L], basis, kinvf, krlr, cols, rows, sums);
-            orc_so3_sums_to_host(sums, ORC_FIX_SO3, jtj, jtr, residual);
-            st->so3_iterations = it + 1;
-            st->last_so3_error = sqrtf(residual[0]) / residual[1];
-            st->last_so3_count = residual[1];
-            /* "Converged": compares lastError with lastSO3Count (sic), :285 */
-            if (st->last_so3_error < lastError && (double)fabsf(lastError - st->last_so3_count) < 0.001) break;
-            else if ((double)st->last_so3_error > (double)lastError + 0.001) {
-                st->last_so3_error = lastError; st->last_so3_count = lastCount;
-                memcpy(resultR, lastResultR, sizeof(resultR));
-                break;
-            }
-            lastError = st->last_so3_error; lastCount = st->last_so3_count;
-            memcpy(lastResultR, resultR, sizeof(resultR));
-            float delta[3];
-            orc_ldlt_f(3, jtj, jtr, delta, 0);
-            double dd[3] = {delta[0], delta[1], delta[2]}, rotUpdate[9];
-            orc_rodrigues(dd, rotUpdate);
-            float ru[9], nr[9];
-            for (int k = 0; k < 9; k++) ru[k] = (float)rotUpdate[k];
-            orc_mul33f(ru, R_lr, nr);
-            memcpy(R_lr, nr, sizeof(nr));
-            for (int k = 0; k < 9; k++) resultR[k] = R_lr[k];
-        }
-    }
+    if (opts->so3) orc_so3_prealign(o->lastNextImage[2], o->nextImage[2], o->intr, o->width, o->height, resultR, st, 0);   /* :239-310 */
 
     int iterations[ORC_NUM_PYRS];
     iterations[0] = opts->fast_odom ? 3 : 10;

@@ -389,6 +389,42 @@ def gn_solve_step(state, icp_tot, rgb_tot, next_level, last_of_level, icp_fix=32
     return out, tr
 
 
+# ---------------------------------------------------------------- the SO(3) pre-alignment loop (orc_so3_prealign) ----
+SO3_BRANCHES = ("step", "converged", "reverted")
+
+
+class So3Trace(C.Structure):
+    _fields_ = [("err", C.c_float * 10), ("count", C.c_float * 10), ("branch", C.c_int32 * 10), ("zero_pivots", C.c_int32 * 10),
+                ("iterations", C.c_int32)]
+
+
+lib.orc_so3_prealign.restype = None
+lib.orc_so3_prealign.argtypes = [C.c_void_p, C.c_void_p, Cam, C.c_int, C.c_int, C.c_void_p, C.POINTER(TrackStats), C.POINTER(So3Trace)]
+lib.orc_so3_prealign_state.restype = None
+lib.orc_so3_prealign_state.argtypes = [C.POINTER(GnState), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+
+
+def so3_prealign(last_image, next_image, intr, width, height):
+    """The whole pre-alignment loop on two level-2 images [(height >> 2), (width >> 2)] under the level-0 camera `intr` (Cam) ->
+    (resultR float64 [3, 3], TrackStats with the three SO(3) words, trace: one {err, count, branch, zero_pivots} per iteration)"""
+    assert last_image.shape == next_image.shape == (height >> 2, width >> 2)
+    R = np.zeros(9, np.float64)
+    st, tr = TrackStats(), So3Trace()
+    lib.orc_so3_prealign(P(u8(last_image)), P(u8(next_image)), intr, int(width), int(height), P(R), C.byref(st), C.byref(tr))
+    trace = [dict(err=tr.err[k], count=tr.count[k], branch=SO3_BRANCHES[tr.branch[k]], zero_pivots=tr.zero_pivots[k]) for k in range(tr.iterations)]
+    return R.reshape(3, 3), st, trace
+
+
+def so3_prealign_state(state, last_image, next_image, do_so3, first_level):
+    """What the launch of the pre-alignment leaves behind, on a COPY of `state` (GnState; intr, width, height are read)"""
+    out = GnState.from_buffer_copy(state)
+    if do_so3:
+        assert last_image.shape == next_image.shape == (out.height >> 2, out.width >> 2)
+    lib.orc_so3_prealign_state(C.byref(out), P(u8(last_image)) if do_so3 else None, P(u8(next_image)) if do_so3 else None,
+                               int(bool(do_so3)), int(first_level))
+    return out
+
+
 def inverse_pose(pose):
     out = np.empty(16, np.float32)
     lib.orc_inverse_pose(P(f32(pose).reshape(16)), P(out))

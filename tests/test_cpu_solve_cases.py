@@ -209,7 +209,7 @@ def test_struct_mirrors_match_the_header(tmp_path):
     from co_fusion_amd import api
     cc = shutil.which("cc") or shutil.which("gcc")
     assert cc, "no C compiler (the build of the oracle needs one too)"
-    mirrors = {"cf_gn_state": api.GnState, "cf_gn_system": api.GnSystem, "cf_track_stats": api.TrackStats}
+    mirrors = {"cf_gn_state": api.GnState, "cf_gn_system": api.GnSystem, "cf_track_stats": api.TrackStats, "cf_so3_system": api.So3System}
     src = "#include <stdio.h>\n#include <stddef.h>\n#include \"cofusion_hip.h\"\nint main(void) {\n"
     for s, m in mirrors.items():
         src += f'  printf("{s} %zu\\n", sizeof({s}));\n'

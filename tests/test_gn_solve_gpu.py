@@ -18,6 +18,7 @@ import pytest
 import orc
 import solve_cases as sc
 from co_fusion_amd import api
+from gn_compare import expected_hot, raw as _raw, same as _same, show as _show
 
 pytestmark = pytest.mark.gpu
 
@@ -35,28 +36,6 @@ def ctx():
     c = api.Context(160, 120, 132.0, 132.0, 79.5, 59.5)
     yield c
     c.close()
-
-
-def _raw(v):
-    return bytes(v) if isinstance(v, (C.Array, C.Structure)) else np.asarray(v).tobytes()
-
-
-def _show(v):
-    return list(v) if isinstance(v, C.Array) else v
-
-
-def _same(a, b):
-    """bit equality of two ctypes values (float / int scalars or arrays), NaN equal to NaN"""
-    if isinstance(a, C.Array):
-        t = {C.c_float: np.float32, C.c_double: np.float64, C.c_int32: np.int32, C.c_int: np.int32}[a._type_]
-        x, y = np.frombuffer(bytes(a), t), np.frombuffer(bytes(b), t)
-    else:
-        t = np.float32 if isinstance(a, float) else np.int64
-        x, y = np.array([a], t), np.array([b], t)
-    if x.dtype.kind == "f":
-        u = {4: np.uint32, 8: np.uint64}[x.dtype.itemsize]
-        return bool(np.all((x.view(u) == y.view(u)) | (np.isnan(x) & np.isnan(y))))
-    return bool(np.array_equal(x, y))
 
 
 def cf_state(d):
@@ -100,15 +79,6 @@ def make_system(state, step):
     C.memset(C.byref(g.twin), 0x5A, C.sizeof(api.GnState))
     C.memset(g.hot, 0xA5, C.sizeof(g.hot))
     return g
-
-
-def expected_hot(s):
-    """refresh_hot (csrc/cf_kernels.h, GnHot) of a state, as 48 words: line 0 {icp, level_done, cull_z[2], Rcurr[9], tcurr[3]}, line 1
-    {Rprev_inv[9], tprev[3], cull_box[4]}, line 2 {rgb, rgbOnly, level_done, 0, krkInv[9], kt[3]}"""
-    i32 = lambda *v: np.array(v, np.int32).view(np.uint32)
-    f32 = lambda a: np.frombuffer(bytes(a), np.uint32)
-    return np.concatenate([i32(s.icp, s.level_done), f32(s.cull_z), f32(s.Rcurr), f32(s.tcurr), f32(s.Rprev_inv), f32(s.tprev), f32(s.stats.cull_box),
-                           i32(s.rgb, s.rgbOnly, s.level_done, 0), f32(s.krkInv), f32(s.kt)])
 
 
 def check(tag, before, after, want, step):

@@ -114,6 +114,9 @@ def _same_as_oracle(case, k, s, got, err, what):
     assert st.last_icp_count == o["icp_count"], f"{what}: ICP count {st.last_icp_count} != {o['icp_count']}"
     assert st.last_rgb_count == o["rgb_count"], f"{what}: RGB count {st.last_rgb_count} != {o['rgb_count']}"
     assert st.so3_iterations == o["so3_iterations"], what
+    if tc.track_opts(case).get("so3", True):   # the pre-alignment's statistics, bit for bit (0 / 0 where it does not run)
+        assert np.float32(st.last_so3_error).tobytes() == o["so3_error"].tobytes(), f"{what}: SO3 error {st.last_so3_error} != {o['so3_error']}"
+        assert np.float32(st.last_so3_count).tobytes() == o["so3_count"].tobytes(), f"{what}: SO3 count {st.last_so3_count} != {o['so3_count']}"
     assert np.array_equal(np.array(st.lastA), o["lastA"]), f"{what}: lastA"
     assert np.array_equal(np.array(st.lastb), o["lastb"]), f"{what}: lastb"
     np.testing.assert_allclose(st.last_icp_error, o["icp_error"], rtol=1e-6, err_msg=what)

@@ -187,6 +187,10 @@ def test_get_incremental_transformation(ctx, opts):
     np.testing.assert_allclose(tr, otr, atol=1e-6, rtol=0)
     np.testing.assert_allclose(rot, orot, atol=1e-6, rtol=0)
     assert st.so3_iterations == ost.so3_iterations
+    if opts.get("so3", True):   # the pre-alignment's statistics, bit for bit
+        assert st.so3_iterations > 0
+        assert np.float32(st.last_so3_error).tobytes() == np.float32(ost.last_so3_error).tobytes(), (st.last_so3_error, ost.last_so3_error)
+        assert np.float32(st.last_so3_count).tobytes() == np.float32(ost.last_so3_count).tobytes(), (st.last_so3_count, ost.last_so3_count)
     if not opts.get("rgb_only"):
         assert st.last_icp_count == ost.last_icp_count
         np.testing.assert_allclose(st.last_icp_error, ost.last_icp_error, rtol=1e-6)

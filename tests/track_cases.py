@@ -241,6 +241,7 @@ def oracle_step(case, k, s):
     t, r, st = od.track(ti["start"][:3, 3], ti["start"][:3, :3], err_surface=err, **track_opts(case))
     out = dict(trans=np.asarray(t, np.float32).copy(), rot=np.asarray(r, np.float32).copy(), icp_count=float(st.last_icp_count),
                rgb_count=float(st.last_rgb_count), icp_error=float(st.last_icp_error), so3_iterations=int(st.so3_iterations),
+               so3_error=np.float32(st.last_so3_error), so3_count=np.float32(st.last_so3_count),
                lastA=np.array(st.lastA, np.float64), lastb=np.array(st.lastb, np.float64), err=err)
     _oracle_cache[key] = out
     return out
