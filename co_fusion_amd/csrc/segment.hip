@@ -566,6 +566,9 @@ int cf_seg_buffer(cf_segmenter* s, int which, void** dptr, uint64_t* bytes)
     case 9: p = s->depth_range; b = 4; break;
     case 10: p = s->low_map; b = K; break;
     case 11: p = s->last_flip ? s->Q1 : s->Q0; b = K * L * 4; break;
+    case 12: p = s->centres; b = K * 5 * 4; break;
+    case 13: p = s->slic_sums; b = K * 6 * 8; break;
+    case 14: p = s->resample; b = K * 4; break;
     default: s->ctx->set_error("cf_seg_buffer: no such buffer"); return CF_EINVAL;
     }
     *dptr = p;

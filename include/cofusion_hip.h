@@ -614,7 +614,14 @@ int cf_seg_labels(cf_segmenter *s, void **dptr, uint64_t *bytes);
  *   10 low_map     u8 [K], the map behind the component analysis and the gates
  *   11 the marginals of the last inference (cf_seg_infer, cf_seg_run_batch or cf_seg_crf), f32 [K][L]: the one of the two buffers the
  *      mean field's last step wrote
- *        5-11 are valid behind cf_seg_infer / cf_seg_run_batch until the segmenter's next call (6, 7 and 11 also behind cf_seg_crf). */
+ *        5-11 are valid behind cf_seg_infer / cf_seg_run_batch until the segmenter's next call (6, 7 and 11 also behind cf_seg_crf).
+ *   12 centres     f32 [K][5] (x y r g b): the centres of SLIC's fifth update, the ones its sixth (last) assignment pass used
+ *   13 slic_sums   u64 [K][6] (x y r g b count): the sums of the sixth assignment pass -- cf_seg_slic leaves them there, no update
+ *      consumes them; column 5 is the labels' pixel count per superpixel
+ *        12 and 13 are valid behind cf_seg_slic until the segmenter's next cf_seg_slic (no other call touches them).
+ *   14 resample    i32 [K]: the label at superpixel k's resample pixel (what an empty superpixel reads, Slic.h:192-206)
+ *        14 is valid behind cf_seg_sums, cf_seg_early and cf_seg_run_batch until the next of them (it follows the labels at that
+ *        call; the inference reads it and leaves it). */
 int cf_seg_buffer(cf_segmenter *s, int which, void **dptr, uint64_t *bytes);
 /* The label-mask branch (Segmentation.cpp:59-119; the reference's "pre-processed segmentation" input, Mask####.png) as kernels: a mask
  * with one value per object arrives with the frame (u8 [H*W], device memory), `mapping` binds mask values to model ids (0 = unmapped)
