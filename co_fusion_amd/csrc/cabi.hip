@@ -97,6 +97,8 @@ void cf_destroy(cf_ctx* ctx)
     if (ctx->d_redetect_bits) (void)hipFree(ctx->d_redetect_bits);
     if (ctx->d_redetect_counts) (void)hipFree(ctx->d_redetect_counts);
     if (ctx->h_redetect_counts) (void)hipHostFree(ctx->h_redetect_counts);
+    if (ctx->d_search) (void)hipFree(ctx->d_search);
+    if (ctx->h_search) (void)hipHostFree(ctx->h_search);
     for (hipEvent_t e : ctx->redetect_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->prof.events) {
         for (int i = 0; i < ctx->prof.capacity; i++) (void)hipEventDestroy(ctx->prof.events[i]);

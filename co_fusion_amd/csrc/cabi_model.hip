@@ -887,6 +887,135 @@ int cf_relabel(cf_ctx* ctx, uint8_t* label_dev, uint64_t n, int from, int to)
     return CF_OK;
 }
 
+// ---- re-detection search (see the header; kernels and the host solve in redetect_search.hip) ----
+static int search_buffers(cf_ctx* ctx)
+{
+    if (ctx->d_search) return CF_OK;
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_search), cf_ctx::kSearchBytes));
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_search), cf_ctx::kSearchBytes));
+    return CF_OK;
+}
+static bool search_frame_ok(const cf_redetect_frame* f)
+{
+    return f && f->depth && f->label && f->cols > 0 && f->rows > 0 && (long long)f->cols * f->rows <= 0x7fffffffLL;
+}
+// the tail of every search entry: read `bytes` from `offset` of the results back and wait; the launches lie between the two events
+static int search_fetch(cf_ctx* ctx, hipStream_t s, size_t offset, size_t bytes)
+{
+    LAUNCHCHK(ctx);
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[1], s));
+    HIPCHK(ctx, hipMemcpyAsync(reinterpret_cast<char*>(ctx->h_search) + offset, reinterpret_cast<char*>(ctx->d_search) + offset, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventElapsedTime(&ctx->redetect_last_ms, ctx->redetect_ev[0], ctx->redetect_ev[1]));
+    return CF_OK;
+}
+static unsigned* search_hist(unsigned long long* base) { return reinterpret_cast<unsigned*>(base + cf_ctx::kSearchWords); }
+static constexpr size_t kSearchStepWord = (size_t)kRedetectBatch * kMomentWords;   // where the step record starts
+
+int cf_redetect_frame_moments(cf_ctx* ctx, const cf_redetect_frame* f, const uint8_t* rgba_dev, int64_t moments[4], uint32_t hist[CF_REDETECT_BINS])
+{
+    if (!ctx || !search_frame_ok(f) || !rgba_dev || !moments || !hist) return CF_EINVAL;
+    if (int r = search_buffers(ctx)) return r;
+    hipStream_t s = ctx->cur();
+    RedetectFrame rf{f->depth, f->label, f->cols, f->rows, f->cam, f->new_label, f->depth_cutoff, f->depth_tol};
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[0], s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_search, 0, kMomentWords * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(search_hist(ctx->d_search), 0, kRedetectBins * 4, s));
+    launch_redetect_frame_moments(s, rf, rgba_dev, ctx->d_search, search_hist(ctx->d_search));
+    if (int r = search_fetch(ctx, s, 0, cf_ctx::kSearchWords * 8 + kRedetectBins * 4)) return r;
+    for (int k = 0; k < kMomentWords; k++) moments[k] = (int64_t)ctx->h_search[k];
+    memcpy(hist, search_hist(ctx->h_search), kRedetectBins * 4);
+    return CF_OK;
+}
+
+static int search_cand(cf_ctx* ctx, cf_model* m, float theta, RedetectCand* rc)
+{
+    if (!m || m->ctx != ctx) return CF_EINVAL;
+    uint32_t nb = 0;
+    if (int r = count_bound(m, &nb)) return r;
+    rc->surfels = m->buf[m->target]; rc->count = m->d_count; rc->count_bound = nb; rc->theta = theta;
+    return CF_OK;
+}
+
+int cf_redetect_model_moments(cf_ctx* ctx, const cf_redetect_candidate* cands, int n, const float dhat[3], int64_t* moments, uint32_t* hist)
+{
+    if (!ctx || !cands || !dhat || !moments || !hist || n <= 0 || n > kRedetectBatch) return CF_EINVAL;
+    if (int r = search_buffers(ctx)) return r;
+    RedetectCand rc[kRedetectBatch];
+    for (int k = 0; k < n; k++) {
+        if (int r = search_cand(ctx, cands[k].model, cands[k].conf_threshold, &rc[k])) return r;
+        inv44f(cands[k].pose, rc[k].t_inv);
+    }
+    hipStream_t s = ctx->cur();
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[0], s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_search, 0, (size_t)n * kMomentWords * 8, s));
+    HIPCHK(ctx, hipMemsetAsync(search_hist(ctx->d_search), 0, (size_t)n * kRedetectBins * 4, s));
+    launch_redetect_model_moments(s, rc, n, dhat, ctx->d_search, search_hist(ctx->d_search));
+    if (int r = search_fetch(ctx, s, 0, cf_ctx::kSearchWords * 8 + (size_t)n * kRedetectBins * 4)) return r;
+    for (int k = 0; k < n * kMomentWords; k++) moments[k] = (int64_t)ctx->h_search[k];
+    memcpy(hist, search_hist(ctx->h_search), (size_t)n * kRedetectBins * 4);
+    return CF_OK;
+}
+
+// one step's launch and read-back; the record is left in ctx->h_search + kSearchStepWord
+static int register_step(cf_ctx* ctx, RedetectCand& rc, const float T[16], const RedetectFrame& rf, const float centre[3])
+{
+    hipStream_t s = ctx->cur();
+    memcpy(rc.t_inv, T, sizeof(rc.t_inv));
+    if (ctx->redetect_timing) HIPCHK(ctx, hipEventRecord(ctx->redetect_ev[0], s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_search + kSearchStepWord, 0, 32 * 8, s));
+    launch_redetect_register_step(s, rc, rf, centre, ctx->d_search + kSearchStepWord);
+    return search_fetch(ctx, s, kSearchStepWord * 8, 32 * 8);
+}
+
+int cf_redetect_register_step(cf_ctx* ctx, cf_model* model, float conf_threshold, const float cam_from_model[16], const cf_redetect_frame* f,
+                              const float centre[3], int64_t sums[32])
+{
+    if (!ctx || !cam_from_model || !search_frame_ok(f) || !centre || !sums) return CF_EINVAL;
+    if (int r = search_buffers(ctx)) return r;
+    RedetectCand rc{};
+    if (int r = search_cand(ctx, model, conf_threshold, &rc)) return r;
+    RedetectFrame rf{f->depth, f->label, f->cols, f->rows, f->cam, f->new_label, f->depth_cutoff, f->depth_tol};
+    if (int r = register_step(ctx, rc, cam_from_model, rf, centre)) return r;
+    for (int k = 0; k < 32; k++) sums[k] = (int64_t)ctx->h_search[kSearchStepWord + k];
+    return CF_OK;
+}
+
+int cf_redetect_register(cf_ctx* ctx, cf_model* model, float conf_threshold, const float seed[16], const cf_redetect_frame* f, const float centre[3],
+                         int max_iterations, cf_redetect_registration* out)
+{
+    if (!ctx || !seed || !search_frame_ok(f) || !centre || !out || max_iterations < 1) return CF_EINVAL;
+    if (int r = search_buffers(ctx)) return r;
+    RedetectCand rc{};
+    if (int r = search_cand(ctx, model, conf_threshold, &rc)) return r;
+    RedetectFrame rf{f->depth, f->label, f->cols, f->rows, f->cam, f->new_label, f->depth_cutoff, f->depth_tol};
+    double R[9], t[3];
+    for (int i = 0; i < 3; i++) { R[3 * i] = seed[4 * i]; R[3 * i + 1] = seed[4 * i + 1]; R[3 * i + 2] = seed[4 * i + 2]; t[i] = seed[4 * i + 3]; }
+    const double c[3] = {centre[0], centre[1], centre[2]};
+    cf_redetect_registration res{};
+    res.ok = 1;
+    for (int it = 0; it < max_iterations; it++) {
+        float T[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
+                       (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.f, 0.f, 0.f, 1.f};
+        if (int r = register_step(ctx, rc, T, rf, centre)) return r;
+        const long long* sums = reinterpret_cast<const long long*>(ctx->h_search + kSearchStepWord);
+        const long long n = sums[28];
+        if (it == 0) res.first_inliers = (uint32_t)n;
+        res.last_inliers = (uint32_t)n;
+        res.rms = n > 0 ? (float)sqrt(ldexp((double)sums[27], -32) / (double)n) : 0.f;
+        if (n < 6 || 2 * n < (long long)res.first_inliers) { res.ok = 0; break; }
+        double tn, on;
+        if (!redetect_register_solve(sums, 1e-3, c, R, t, &tn, &on)) { res.ok = 0; break; }
+        res.iterations = it + 1;
+        if (tn < 1e-5 && on < 1e-5) break;
+    }
+    const float T[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
+                         (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.f, 0.f, 0.f, 1.f};
+    memcpy(res.cam_from_model, T, sizeof(T));
+    *out = res;
+    return CF_OK;
+}
+
 // Model::computeFusionWeight (Model.cpp:391-406) + Model::rodrigues2 (Model.cpp:817-865); host math.
 // The JacobiSVD re-orthonormalisation of rodrigues2 is the identity for rotation products.
 float cf_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier)

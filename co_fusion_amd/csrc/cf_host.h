@@ -75,6 +75,11 @@ struct cf_ctx {
     unsigned* d_redetect_bits = nullptr; unsigned redetect_words = 0;
     unsigned* d_redetect_counts = nullptr; unsigned* h_redetect_counts = nullptr;
     bool redetect_timing = false; hipEvent_t redetect_ev[2]{}; float redetect_last_ms = 0.f;   // cf_redetect_timing
+    // the re-detection search's results (created at first use): [kSearchWords] 64-bit words -- the candidates' moments, then one step
+    // record -- followed by the candidates' histograms; and their pinned read-back
+    static constexpr size_t kSearchWords = (size_t)cf::kRedetectBatch * cf::kMomentWords + 32;
+    static constexpr size_t kSearchBytes = kSearchWords * 8 + (size_t)cf::kRedetectBatch * cf::kRedetectBins * 4;
+    unsigned long long* d_search = nullptr; unsigned long long* h_search = nullptr;
     void set_error(const std::string& m);
 };
 inline cf_cam ctx_cam(const cf_ctx* ctx) { return cf_cam{ctx->cfg.fx, ctx->cfg.fy, ctx->cfg.cx, ctx->cfg.cy}; }

@@ -501,4 +501,18 @@ struct RedetectFrame {   // what the candidates are scored against
 void launch_redetect_score(hipStream_t s, const RedetectCand* cands, int n, const RedetectFrame& f, unsigned* bits, unsigned words, unsigned* counts);
 void launch_relabel(hipStream_t s, uint8_t* label /* 16-byte aligned */, unsigned long long n, unsigned from, unsigned to);
 
+// ---- re-detection search launchers (redetect_search.hip) ----
+constexpr int kRedetectBins = 512;   // colour histogram: the top three bits of R, G and B
+constexpr int kMomentWords = 4;      // i64 per moment record: count, sum x, sum y, sum z (positions on a 2^-16 m grid)
+// the pixels of f.new_label with a valid depth: moments [kMomentWords] and hist [kRedetectBins], both zero on entry (f.tol is not read)
+void launch_redetect_frame_moments(hipStream_t s, const RedetectFrame& f, const uint8_t* rgba, unsigned long long* moments, unsigned* hist);
+// n <= kRedetectBatch candidates (t_inv: the static hypothesis): moments [n][kMomentWords] of the stable surfels whose normal points
+// along dhat (the maps' normals point away from the camera), hist [n][kRedetectBins] of all stable surfels; zero on entry
+void launch_redetect_model_moments(hipStream_t s, const RedetectCand* cands, int n, const float dhat[3], unsigned long long* moments, unsigned* hist);
+// one Gauss-Newton step's sums of candidate c at the pose c.t_inv = T(camera <- model): out [32] (the word layout of the ICP sums), zero on entry
+void launch_redetect_register_step(hipStream_t s, const RedetectCand& c, const RedetectFrame& f, const float centre[3], unsigned long long* out);
+// host f64: (A + lambda tr(A) / 6 I) xi = b by Cholesky, R <- exp(omega) R, t <- exp(omega) (t - centre) + centre + tau; false when the
+// damped matrix is not positive definite (no inliers)
+bool redetect_register_solve(const long long sums[32], double lambda, const double centre[3], double R[9], double t[3], double* tau_norm, double* omega_norm);
+
 }  // namespace cf

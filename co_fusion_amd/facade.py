@@ -29,6 +29,14 @@ class RedetectCandidate(C.Structure):
                 ("agree_on_label", C.c_uint32), ("covered", C.c_uint32), ("fit", C.c_float), ("cover", C.c_float), ("eligible", C.c_int)]
 
 
+class RedetectSearchCandidate(C.Structure):
+    """cofusion_redetect_search_candidate (include/cofusion.h)"""
+    _fields_ = [("id", C.c_uint), ("colour", C.c_float), ("registered", C.c_int), ("converged", C.c_int), ("iterations", C.c_int),
+                ("first_inliers", C.c_uint32), ("last_inliers", C.c_uint32), ("rms", C.c_float), ("moved", C.c_float),
+                ("projected", C.c_uint32), ("occluded", C.c_uint32), ("seen_through", C.c_uint32), ("agree", C.c_uint32),
+                ("agree_on_label", C.c_uint32), ("covered", C.c_uint32), ("fit", C.c_float), ("cover", C.c_float), ("eligible", C.c_int)]
+
+
 class CoFusionError(RuntimeError):
     pass
 
@@ -510,6 +518,27 @@ class CoFusion:
         for c in cands:
             c["eligible"] = bool(c["eligible"])
         return dict(label_pixels=px.value, winner=w.value, candidates=cands)
+
+    def set_redetection_search(self, on=True, iterations=10, min_colour=-1.0, max_registered=2):
+        """The search behind the static hypothesis (cofusion_set_redetection_search, DESIGN.md 4.13 "Search"): in a frame whose new label
+        no kept model explains where it stood, the models whose colours resemble the label's (histogram intersection >= min_colour;
+        negative: the default) are registered onto the label's pixels, the `max_registered` most similar first, and judged at the
+        registered pose.  Needs set_redetection(True) first; off by default; world == 1 only."""
+        self._check(self.lib.cofusion_set_redetection_search(self.h, int(bool(on)), int(iterations), C.c_float(min_colour), int(max_registered)))
+
+    def redetect_search_last(self):
+        """the search of the last attempt: dict(winner (position or -1), attempts (frames that searched), candidates=[dict(id, colour,
+        registered, converged, iterations, first_inliers, last_inliers, rms, moved, the six counts, fit, cover, eligible)] in the order of
+        redetect_last -- empty when that attempt did not search)"""
+        cap = 16
+        out = (RedetectSearchCandidate * cap)()
+        n = C.c_int(); w = C.c_int(); a = C.c_int()
+        self._check(self.lib.cofusion_redetect_search_last(self.h, out, cap, C.byref(n), C.byref(w), C.byref(a)))
+        cands = [{k: getattr(out[q], k) for k, _ in RedetectSearchCandidate._fields_} for q in range(min(n.value, cap))]
+        for c in cands:
+            for k in ("registered", "converged", "eligible"):
+                c[k] = bool(c[k])
+        return dict(winner=w.value, attempts=a.value, candidates=cands)
 
     @property
     def num_inactive_models(self):

@@ -706,6 +706,8 @@ void CoFusion::setRedetection(bool on, float minFit, float minCover, float depth
     redetect.on = on; redetect.minFit = minFit; redetect.minCover = minCover; redetect.depthTol = depthTol; redetect.maxCandidates = maxCandidates;
     modelKeepMinSurfels = keepMinSurfels; modelKeepConfThreshold = keepConfThreshold;
     redetectSt = RedetectStats{}; redetectCands.clear(); redetectLabelPixels = 0; redetectWinner = -1;
+    if (!on) search.on = false;   // (the search lives behind the static pass)
+    searchCands.clear(); searchWinner = -1; searchAttempts = 0;
 }
 
 // The body the reference removed (CoFusion.cpp:599-602).  Hypothesis: the object has not moved in the world since it was deactivated.
@@ -726,6 +728,7 @@ ModelPointer CoFusion::redetectModels(unsigned char newLabel)
         }
     }
     redetectCands.clear(); redetectLabelPixels = 0; redetectWinner = -1;
+    searchCands.clear(); searchWinner = -1;
     if (cand.empty()) return nullptr;
     redetectSt.attempts++;
     const Mat4f& G = globalModel->getPose();
@@ -751,10 +754,13 @@ ModelPointer CoFusion::redetectModels(unsigned char newLabel)
         if (r.eligible && (redetectWinner < 0 || counts[k].agree_on_label > counts[(size_t)redetectWinner].agree_on_label)) redetectWinner = (int)k;
         redetectCands.push_back(r);
     }
-    if (redetectWinner < 0) return nullptr;
-    ModelPointer m = *cand[(size_t)redetectWinner];
-    inactiveModels.erase(cand[(size_t)redetectWinner]);
-    m->overridePose(hyp[(size_t)redetectWinner]);
+    int winner = redetectWinner;
+    // setRedetectionSearch: nobody stands where it stood -- has one of them come back somewhere else?  (A parked object never gets here.)
+    if (winner < 0 && search.on) winner = searchModels(in, hyp, f);
+    if (winner < 0) return nullptr;
+    ModelPointer m = *cand[(size_t)winner];
+    inactiveModels.erase(cand[(size_t)winner]);
+    m->overridePose(hyp[(size_t)winner]);
     m->resetUnseenCount();
     m->predictOnlyThisFrame = true;
     // the tracker starts over as a spawned model's does (spawnObjectModel); the end-of-frame prediction gives it its model maps
@@ -764,6 +770,107 @@ ModelPointer CoFusion::redetectModels(unsigned char newLabel)
     labelGenerator->remapNewValue((unsigned char)m->getID());
     redetectSt.reactivations++; redetectSt.lastId = (int)m->getID();
     return m;
+}
+
+void CoFusion::setRedetectionSearch(bool on, int iterations, float minColour, int maxRegistered)
+{
+    if (on && dist.active()) throw std::runtime_error("setRedetectionSearch: re-detection is a single-process option (world == 1): a model-parallel instance keeps a model's map on one rank only");
+    if (on && !redetect.on) throw std::runtime_error("setRedetectionSearch: needs setRedetection(true) first");
+    if (on && (iterations < 1 || iterations > 100)) throw std::runtime_error("setRedetectionSearch: 1..100 iterations");
+    if (on && (maxRegistered < 1 || maxRegistered > 16)) throw std::runtime_error("setRedetectionSearch: 1..16 registrations per frame");
+    search.on = on; search.iterations = iterations; search.minColour = minColour; search.maxRegistered = maxRegistered;
+    searchCands.clear(); searchWinner = -1; searchAttempts = 0;
+}
+
+// The search behind the static pass (DESIGN.md 4.13 "Search"): the candidates `in` (their static hypotheses `hyp`) against the frame f,
+// whose new label nobody explains where it stood.  Colour gate first -- histogram intersection of the kept map's colours with the
+// label's, pose independent --, then the most similar maxRegistered candidates are registered onto the label's pixels from the seed
+// "static orientation, front-facing centroid on the label's centroid" (cf_redetect_register: a host wait per iteration), re-scored at
+// the registered pose in one launch and judged by the static pass's rule.  Returns the winner's position (hyp[winner] is then the
+// registered pose) or -1.
+int CoFusion::searchModels(const std::vector<cf_redetect_candidate>& in, std::vector<Mat4f>& hyp, const cf_redetect_frame& f)
+{
+    const size_t n = in.size();
+    searchCands.assign(n, RedetectSearchCandidate{});
+    searchWinner = -1;
+    searchAttempts++;
+    for (size_t k = 0; k < n; k++) searchCands[k].id = redetectCands[k].id;
+    int64_t fm[4];
+    std::vector<uint32_t> fh(CF_REDETECT_BINS);
+    check(ctx, cf_redetect_frame_moments(ctx, &f, curRgba, fm, fh.data()), "cf_redetect_frame_moments");
+    if (fm[0] <= 0) return -1;
+    double fbar[3];
+    for (int a = 0; a < 3; a++) fbar[a] = std::ldexp((double)fm[1 + a], -16) / (double)fm[0];
+    const double fn = std::sqrt((fbar[0] * fbar[0] + fbar[1] * fbar[1]) + fbar[2] * fbar[2]);
+    if (!(fn > 0.0)) return -1;
+    const float dhat[3] = {(float)(fbar[0] / fn), (float)(fbar[1] / fn), (float)(fbar[2] / fn)};
+    const float centre[3] = {(float)fbar[0], (float)fbar[1], (float)fbar[2]};
+    std::vector<int64_t> mm(n * 4);
+    std::vector<uint32_t> mh(n * CF_REDETECT_BINS);
+    check(ctx, cf_redetect_model_moments(ctx, in.data(), (int)n, dhat, mm.data(), mh.data()), "cf_redetect_model_moments");
+    std::vector<size_t> order;
+    for (size_t k = 0; k < n; k++) {
+        uint64_t nm = 0;
+        for (int b = 0; b < CF_REDETECT_BINS; b++) nm += mh[k * CF_REDETECT_BINS + b];
+        double sim = 0.0;
+        if (nm)
+            for (int b = 0; b < CF_REDETECT_BINS; b++) sim += std::min((double)mh[k * CF_REDETECT_BINS + b] / (double)nm, (double)fh[(size_t)b] / (double)fm[0]);
+        searchCands[k].colour = (float)sim;
+        if (nm && mm[k * 4] > 0 && searchCands[k].colour >= search.minColour) order.push_back(k);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return searchCands[a].colour > searchCands[b].colour; });
+    if (order.size() > (size_t)search.maxRegistered) order.resize((size_t)search.maxRegistered);
+    std::vector<cf_redetect_candidate> again;
+    std::vector<size_t> which;
+    std::vector<Mat4f> poses;
+    for (size_t k : order) {
+        RedetectSearchCandidate& r = searchCands[k];
+        const Mat4f T0 = hyp[k].inverse();   // camera <- model under the static hypothesis: its orientation is the seed's
+        double mbar[3];
+        for (int a = 0; a < 3; a++) mbar[a] = std::ldexp((double)mm[k * 4 + 1 + a], -16) / (double)mm[k * 4];
+        Mat4f seed = T0;
+        for (int i = 0; i < 3; i++) {
+            double s = (double)T0.m[4 * i] * mbar[0];
+            s = s + (double)T0.m[4 * i + 1] * mbar[1];
+            s = s + (double)T0.m[4 * i + 2] * mbar[2];
+            seed.m[4 * i + 3] = (float)(fbar[i] - s);
+        }
+        cf_redetect_registration reg{};
+        check(ctx, cf_redetect_register(ctx, in[k].model, in[k].conf_threshold, seed.m, &f, centre, search.iterations, &reg), "cf_redetect_register");
+        r.registered = true; r.converged = reg.ok != 0; r.iterations = reg.iterations;
+        r.firstInliers = reg.first_inliers; r.lastInliers = reg.last_inliers; r.rms = reg.rms;
+        Mat4f T{}; memcpy(T.m, reg.cam_from_model, sizeof(T.m));
+        double d2 = 0.0;
+        for (int i = 0; i < 3; i++) {   // how far the front-facing centroid went from where the static hypothesis has it
+            double a = 0.0, b = 0.0;
+            for (int j = 0; j < 3; j++) { a += (double)T.m[4 * i + j] * mbar[j]; b += (double)T0.m[4 * i + j] * mbar[j]; }
+            const double d = (a + (double)T.m[4 * i + 3]) - (b + (double)T0.m[4 * i + 3]);
+            d2 += d * d;
+        }
+        r.moved = (float)std::sqrt(d2);
+        if (!r.converged) continue;
+        cf_redetect_candidate c = in[k];
+        const Mat4f pose = T.inverse();
+        memcpy(c.pose, pose.m, sizeof(c.pose));
+        again.push_back(c); which.push_back(k); poses.push_back(pose);
+    }
+    if (again.empty()) return -1;
+    std::vector<cf_redetect_counts> counts(again.size());
+    uint32_t px = 0;
+    check(ctx, cf_redetect_score(ctx, again.data(), (int)again.size(), &f, counts.data(), &px), "cf_redetect_score");
+    for (size_t q = 0; q < again.size(); q++) {
+        RedetectSearchCandidate& r = searchCands[which[q]];
+        r.counts = counts[q];
+        const uint32_t seen = counts[q].agree + counts[q].seen_through;
+        r.fit = seen ? (float)counts[q].agree_on_label / (float)seen : 0.f;
+        r.cover = px ? (float)counts[q].covered / (float)px : 0.f;
+        r.eligible = seen != 0 && px != 0 && r.fit >= redetect.minFit && r.cover >= redetect.minCover;
+        if (r.eligible && (searchWinner < 0 || counts[q].agree_on_label > searchCands[(size_t)searchWinner].counts.agree_on_label)) {
+            searchWinner = (int)which[q];
+            hyp[which[q]] = poses[q];
+        }
+    }
+    return searchWinner;
 }
 
 void CoFusion::predict(bool lastOfFrame)

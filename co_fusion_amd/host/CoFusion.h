@@ -441,6 +441,27 @@ class CoFusion {
         if (winner) *winner = redetectWinner;
         return redetectCands;
     }
+    // The search behind it (DESIGN.md 4.13 "Search"), for an object that came back SOMEWHERE ELSE.  Needs setRedetection on; off by
+    // default, and with it off every frame is what it was.  Runs only in a frame whose static pass found nobody eligible: candidates
+    // whose colour histogram intersects the label's by at least `minColour` are ranked by that similarity; the first `maxRegistered`
+    // are registered onto the label's pixels (cf_redetect_register, at most `iterations` steps and host waits each), re-scored at the
+    // registered pose and judged by minFit / minCover as above; the winner is reactivated at the registered pose.  Envelope: any
+    // translation that keeps the object in view, turns up to about 10 degrees (degrading towards 20).  Single process only.
+    void setRedetectionSearch(bool on, int iterations = 10, float minColour = kRedetectMinColour, int maxRegistered = 2);
+    static constexpr float kRedetectMinColour = 0.175f;   // between the weakest returning object (0.67) and the strongest stranger (0.046) of the facade scenes, DESIGN.md 4.13
+    struct RedetectSearchCandidate {
+        unsigned id = 0; float colour = 0.f; bool registered = false, converged = false; int iterations = 0;
+        uint32_t firstInliers = 0, lastInliers = 0; float rms = 0.f, moved = 0.f;   // moved: front-facing centroid, registered against static pose (m)
+        cf_redetect_counts counts{}; float fit = 0.f, cover = 0.f; bool eligible = false;   // the score at the registered pose
+    };
+    // the candidates of the last attempt's search in the order of redetectLast (empty when that attempt did not search), the winner's
+    // position (-1: none), and the number of frames that searched
+    const std::vector<RedetectSearchCandidate>& redetectSearchLast(int* winner = nullptr, int* attempts = nullptr) const
+    {
+        if (winner) *winner = searchWinner;
+        if (attempts) *attempts = searchAttempts;
+        return searchCands;
+    }
     size_t numInactiveModels() const { return inactiveModels.size(); }
     // The motion-CRF chain's tracking-independent half beside the tracking launches (Segmentation::startEarly).  On by default; off
     // leaves the whole chain behind the tracker -- the same results bit for bit, for A/B measurements and parity tests.
@@ -496,6 +517,10 @@ class CoFusion {
     std::vector<RedetectCandidate> redetectCands;
     uint32_t redetectLabelPixels = 0;
     int redetectWinner = -1;
+    int searchModels(const std::vector<cf_redetect_candidate>& in, std::vector<Mat4f>& hyp, const cf_redetect_frame& f);
+    struct { bool on = false; int iterations = 10; float minColour = kRedetectMinColour; int maxRegistered = 2; } search;
+    std::vector<RedetectSearchCandidate> searchCands;
+    int searchWinner = -1, searchAttempts = 0;
     void moveNewModelToList();
     ModelList::iterator inactivateModel(ModelList::iterator it);
     unsigned char getNextModelID(bool assign = false);

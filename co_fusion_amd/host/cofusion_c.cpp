@@ -157,6 +157,27 @@ int cofusion_redetect_last(cofusion_handle* h, cofusion_redetect_candidate* out,
     }
     return 0;
 }
+int cofusion_set_redetection_search(cofusion_handle* h, int on, int iterations, float min_colour, int max_registered)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    GUARD(h->cf->setRedetectionSearch(on != 0, iterations > 0 ? iterations : 10, min_colour >= 0 ? min_colour : CoFusion::kRedetectMinColour,
+                                      max_registered > 0 ? max_registered : 2));
+    return 0;
+}
+int cofusion_redetect_search_last(cofusion_handle* h, cofusion_redetect_search_candidate* out, int capacity, int* n, int* winner, int* attempts)
+{
+    if (!h || !n) { g_err = "cofusion_redetect_search_last: bad arguments"; return -1; }
+    const std::vector<CoFusion::RedetectSearchCandidate>& c = h->cf->redetectSearchLast(winner, attempts);
+    *n = (int)c.size();
+    for (int k = 0; out && k < capacity && k < (int)c.size(); k++) {
+        const CoFusion::RedetectSearchCandidate& r = c[(size_t)k];
+        const cf_redetect_counts& q = r.counts;
+        out[k] = cofusion_redetect_search_candidate{r.id, r.colour, r.registered ? 1 : 0, r.converged ? 1 : 0, r.iterations, r.firstInliers, r.lastInliers,
+                                                    r.rms, r.moved, q.projected, q.occluded, q.seen_through, q.agree, q.agree_on_label, q.covered,
+                                                    r.fit, r.cover, r.eligible ? 1 : 0};
+    }
+    return 0;
+}
 int cofusion_num_inactive_models(cofusion_handle* h) { return h ? (int)h->cf->numInactiveModels() : -1; }
 int cofusion_reloc_stats(cofusion_handle* h, int* keyframes, int* last_closest, int* recoveries, int* database_full)
 {

@@ -29,6 +29,7 @@ SYMBOLS = [
     "cf_model_fuse", "cf_model_clean", "cf_models_frame_passes", "cf_models_preindex", "cf_model_download_map", "cf_model_upload_map", "cf_model_buffer",
     "cf_set_extent_culling", "cf_model_extents_unknown",
     "cf_redetect_score", "cf_redetect_timing", "cf_relabel",
+    "cf_redetect_frame_moments", "cf_redetect_model_moments", "cf_redetect_register_step", "cf_redetect_register",
     "cf_fusion_weight", "cf_seg_create", "cf_seg_destroy", "cf_seg_slic", "cf_seg_crf", "cf_seg_sums", "cf_seg_infer", "cf_seg_early", "cf_seg_run_batch", "cf_seg_fetch", "cf_seg_publish_poses", "cf_seg_fetch_poses",
     "cf_seg_labels", "cf_seg_buffer", "cf_seg_create_masks", "cf_seg_masks", "cf_seg_masks_batch", "cf_seg_new_mask_value",
     "cf_depth_pyramid", "cf_set_icp_launch", "cf_set_icp_arith", "cf_get_icp_arith", "cf_set_gn_mode", "cf_profile_enable", "cf_profile_read", "cf_odom_bench_icp", "cf_odom_level0_visited", "cf_odom_last_launch_shape",
@@ -74,6 +75,7 @@ HOST_SYMBOLS = [
     "cofusion_render", "cofusion_render_device", "cofusion_set_export_views", "cofusion_set_export_async", "cofusion_export_flush", "cofusion_export_stats", "cofusion_set_relocalisation", "cofusion_reloc_stats", "cofusion_deform_background", "cofusion_set_loop_closure", "cofusion_loop_stats", "cofusion_set_local_loop_closure", "cofusion_local_loop_stats",
     "cofusion_set_relative_constraints", "cofusion_add_relative_constraints", "cofusion_relative_constraints", "cofusion_relative_stats", "cofusion_local_closure_download",
     "cofusion_set_redetection", "cofusion_redetect_stats", "cofusion_redetect_last", "cofusion_num_inactive_models",
+    "cofusion_set_redetection_search", "cofusion_redetect_search_last",
     "cofusion_klg_player_open", "cofusion_klg_player_next", "cofusion_klg_player_process", "cofusion_klg_player_rewind", "cofusion_klg_player_set_limits", "cofusion_klg_player_close",
     "cofusion_jpeg_front", "cofusion_jpeg_finish_host", "cofusion_klg_prefetch_open", "cofusion_klg_prefetch_next", "cofusion_klg_prefetch_rewind", "cofusion_klg_prefetch_close",
     "cofusion_image_reader_open", "cofusion_image_reader_next", "cofusion_image_reader_rewind", "cofusion_image_reader_close",

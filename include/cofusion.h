@@ -216,6 +216,32 @@ typedef struct {
 /* the candidates of the last attempt in list order (at most `capacity` are written, *n is their number), the pixels its new label had and
  * the position of the accepted candidate (-1: none); out, label_pixels, winner nullable */
 int cofusion_redetect_last(cofusion_handle *h, cofusion_redetect_candidate *out, int capacity, int *n, uint32_t *label_pixels, int *winner);
+/* The search behind the static hypothesis (DESIGN.md 4.13 "Search"): an object that comes back SOMEWHERE ELSE.  Needs
+ * cofusion_set_redetection on (an error otherwise); off by default and then without any effect.  It runs only in a frame whose static
+ * pass found nobody eligible -- a parked object is handled exactly as before.  The kept models whose colour histogram (512 bins: the top
+ * three bits of R, G, B of their stable surfels) intersects that of the new label's pixels by at least min_colour (default 0.175, measured: DESIGN.md 4.13) are ranked by that
+ * similarity; the first max_registered (1..16, default 2) are registered onto the label's pixels -- point-to-plane, twist about the
+ * label's centroid, Tikhonov damped, at most `iterations` (default 10) steps with one host wait each, seeded with the static orientation
+ * and the centroids aligned (cf_redetect_register, cofusion_hip.h) --, scored again at the registered pose and judged by min_fit /
+ * min_cover as above; the winner is reactivated at the registered pose.  Envelope: any translation that keeps the object in view, turns
+ * of up to about 10 degrees while unseen (degrading towards 20).  iterations / max_registered <= 0 and min_colour < 0 select the
+ * defaults.  Refused for world > 1. */
+int cofusion_set_redetection_search(cofusion_handle *h, int on, int iterations, float min_colour, int max_registered);
+typedef struct {
+    unsigned id;
+    float colour;                 /* histogram intersection with the label's pixels, 0..1 */
+    int registered, converged;    /* passed the colour gate and was within max_registered; its registration did not fail */
+    int iterations;
+    uint32_t first_inliers, last_inliers;
+    float rms;                    /* of the point-to-plane residuals of the last step (m) */
+    float moved;                  /* its front-facing centroid: registered against static pose (m) */
+    uint32_t projected, occluded, seen_through, agree, agree_on_label, covered;   /* the score at the registered pose */
+    float fit, cover;
+    int eligible;
+} cofusion_redetect_search_candidate;
+/* the search of the last attempt, candidates in the order of cofusion_redetect_last (*n = 0 when that attempt did not search); winner:
+ * the position of the reactivated candidate (-1: none); attempts: frames that searched so far; out, winner, attempts nullable */
+int cofusion_redetect_search_last(cofusion_handle *h, cofusion_redetect_search_candidate *out, int capacity, int *n, int *winner, int *attempts);
 int cofusion_num_inactive_models(cofusion_handle *h);
 /* per model (list order, 0 = background): id, surfel count, pose T(model <- camera), confidence threshold */
 int cofusion_model_info(cofusion_handle *h, int index, unsigned *id, unsigned *count, float pose[16], float *conf_threshold);

@@ -519,6 +519,44 @@ int cf_redetect_score(cf_ctx *ctx, const cf_redetect_candidate *candidates, int 
 int cf_redetect_timing(cf_ctx *ctx, int on, float *last_ms);
 /* label_dev[i] == from -> to for i < n, 16 bytes per lane (label_dev: device, 16-byte aligned; from, to: 0..255); enqueued only */
 int cf_relabel(cf_ctx *ctx, uint8_t *label_dev, uint64_t n, int from, int to);
+/* Re-detection search (CoFusion::setRedetectionSearch, DESIGN.md 4.13 "Search"; kernels in csrc/redetect_search.hip, the numpy statement
+ * in tests/redetect_search_ref.py): for an object that came back somewhere else.  Every device result is an integer -- a count, or a sum
+ * of values rounded once to a fixed-point grid -- and so independent of launch shape and atomic order.  Each entry enqueues on the
+ * context's stream and waits (the results travel through pinned memory); cf_redetect_timing covers their launches too.
+ *
+ * cf_redetect_frame_moments: over the pixels with label == new_label and 0 < depth <= depth_cutoff (depth_tol is not read):
+ *   moments[0] their number, moments[1..3] the sum of rint(clamp(c, +-64) * 2^16) over the coordinates c of their vertices (createVMap's
+ *   arithmetic: (d * (u - cx)) * (1 / fx), ...), hist[512] the histogram of (R >> 5) << 6 | (G >> 5) << 3 | (B >> 5) of rgba (device, u8 x 4). */
+#define CF_REDETECT_BINS 512
+int cf_redetect_frame_moments(cf_ctx *ctx, const cf_redetect_frame *frame, const uint8_t *rgba_dev, int64_t moments[4], uint32_t hist[CF_REDETECT_BINS]);
+/* cf_redetect_model_moments: n <= 16 candidates in ONE launch (candidates[k].pose: the static hypothesis, as cf_redetect_score takes it).
+ * Over the surfels with confidence >= conf_threshold: hist[k] the histogram of their decoded colours; over those of them whose normal,
+ * rotated into the camera, has a POSITIVE dot product with dhat, the unit vector towards the label's centroid (the maps' normals point
+ * away from the camera that saw them, as createNMap's do: such a surfel faces the camera): moments[k][0] their
+ * number, moments[k][1..3] the sum of their MODEL-frame positions on the same grid. */
+int cf_redetect_model_moments(cf_ctx *ctx, const cf_redetect_candidate *candidates, int n, const float dhat[3], int64_t *moments /* [n][4] */,
+                              uint32_t *hist /* [n][CF_REDETECT_BINS] */);
+/* cf_redetect_register_step: one candidate at one pose, cam_from_model = row-major T(camera <- model) -- the INVERSE of the convention of
+ * cf_redetect_candidate::pose: the registration's state is the transform it applies.  A surfel with confidence >= conf_threshold is an
+ * inlier when p = R p_m + t projects (as the score projects it) onto a pixel q with label[q] == new_label and 0 < depth[q] <=
+ * depth_cutoff, |v - p| <= depth_tol for the frame's vertex v at q, and dot(n, p) > 0 for n = R n_m (it faces the camera).  Row J = [n, (p - centre) x n],
+ * residual r = n . (v - p), entries clamped to +-4; sums[0..26]: the upper triangle of [J | r]^T [J | r] row by row without its last
+ * entry, sums[27] = sum r^2, sums[28] the inliers, each product rounded once to 2^-32 (the layout and grid of the ICP sums). */
+int cf_redetect_register_step(cf_ctx *ctx, cf_model *model, float conf_threshold, const float cam_from_model[16], const cf_redetect_frame *frame,
+                              const float centre[3], int64_t sums[32]);
+/* cf_redetect_register: the loop over that step, host f64 from the exact sums: (A + 1e-3 tr(A) / 6 I) xi = b by Cholesky, xi = (tau,
+ * omega); R <- exp(omega) R, t <- exp(omega) (t - centre) + centre + tau (the twist is about `centre`, the label's centroid).  Ends when
+ * |tau| < 1e-5 m and |omega| < 1e-5 rad or after max_iterations steps; FAILS (ok = 0) when a step has fewer than 6 inliers or fewer than
+ * half of the first step's, or no positive definite system.  One host wait per step.  rms: sqrt(sum r^2 / inliers) of the last step
+ * evaluated; cam_from_model: the pose after the last update (the seed when the first step fails). */
+typedef struct {
+    int ok, iterations;                       /* steps whose update was applied */
+    uint32_t first_inliers, last_inliers;
+    float rms;
+    float cam_from_model[16];
+} cf_redetect_registration;
+int cf_redetect_register(cf_ctx *ctx, cf_model *model, float conf_threshold, const float seed_cam_from_model[16], const cf_redetect_frame *frame,
+                         const float centre[3], int max_iterations, cf_redetect_registration *out);
 /* Model::computeFusionWeight (Model.cpp:391-406); pure host math */
 float cf_fusion_weight(const float pose[16], const float lastPose[16], float weightMultiplier);
 

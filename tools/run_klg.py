@@ -7,7 +7,7 @@ does head-less, GUI/MainController.cpp):
                             [--export-labels] [--export-normals] [--export-viewport] [--export-async [--export-workers N]]
                             [--player [--workers N]]
                             [--mask-dir DIR [--mask-prefix Mask --index-width 4]]
-                            [--redetect [--redetect-fit F --redetect-cover C --redetect-tol T]]
+                            [--redetect [--redetect-fit F --redetect-cover C --redetect-tol T]] [--redetect-search]
 
 Writes out/poses-<id>.txt, out/cloud-<id>.ply (and out/Segmentation<tick>.png, out/Labels<tick>.png, out/Normals<tick>.png,
 out/Viewport<tick>.png: the reference's -el / -en / -ev views of every frame) and prints frames/s.  --export-async encodes those PNGs on
@@ -70,6 +70,8 @@ def main():
                                                               "--close-loops)")
     ap.add_argument("--redetect", action="store_true", help="an object that is labelled again resumes its kept inactive model (old id and map) "
                                                             "where that explains the frame, instead of a new model")
+    ap.add_argument("--redetect-search", action="store_true", help="implies --redetect: an object that comes back somewhere else is looked for by "
+                    "registration -- colour gate, then point-to-plane onto the new label's pixels (DESIGN.md 4.13, Search)")
     ap.add_argument("--redetect-fit", type=float, default=-1.0, help="least agree_on_label / (agree + seen_through) of a candidate (default 0.5)")
     ap.add_argument("--redetect-cover", type=float, default=-1.0, help="least share of the new label's pixels a candidate must explain (default 0.044)")
     ap.add_argument("--redetect-tol", type=float, default=-1.0, help="depth agreement in metres (default 0.10, the tracker's gate)")
@@ -117,10 +119,13 @@ def main():
         cf.set_local_loop_closure(True, sample_rate=a.local_sample_rate)
     if a.relative_constraints:
         cf.set_relative_constraints(True)
+    a.redetect = a.redetect or a.redetect_search
     if a.redetect:
         if a.static:
             raise SystemExit("--redetect needs the multi-model mode (no --static)")
         cf.set_redetection(True, min_fit=a.redetect_fit, min_cover=a.redetect_cover, depth_tol=a.redetect_tol)   # (negative: the defaults)
+        if a.redetect_search:
+            cf.set_redetection_search(True)
     if a.export_segmentation and not a.static:
         cf.set_export_segmentation(prefix)
     if a.export_labels or a.export_normals or a.export_viewport:
@@ -195,6 +200,8 @@ def main():
         print(f"relative constraints: {cf.relative_stats()}")
     if a.redetect:
         print(f"re-detection: {cf.redetect_stats()}, {cf.num_inactive_models} inactive model(s) kept")
+        if a.redetect_search:
+            print(f"re-detection search: {cf.redetect_search_last()['attempts']} frame(s) searched")
     if a.export_async:
         s = cf.export_stats()
         print(f"asynchronous exports: {s['images']} files, {s['bytes']} bytes, {s['stalls']} submits waited for a slot")
