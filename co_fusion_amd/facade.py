@@ -216,6 +216,37 @@ class CoFusion:
             raise CoFusionError(self.lib.cofusion_last_error().decode())
         return n
 
+    def save_mesh(self, prefix, voxel=0.0):
+        """CoFusion::saveMesh: <prefix>mesh-<id>.ply per model, a triangle mesh of its confident surfels extracted on the device
+        (voxel 0: the model's mean confident radius); returns the number of files"""
+        self.lib.cofusion_save_mesh.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
+        n = self.lib.cofusion_save_mesh(self.h, str(prefix).encode(), float(voxel))
+        if n < 0:
+            raise CoFusionError(self.lib.cofusion_last_error().decode())
+        return n
+
+    def model_mesh(self, index, voxel=0.0, with_transform=False):
+        """one model's mesh in the model's own frame: (vertices, triangles) -- records of co_fusion_amd.mesh.VERTEX (pos, nrm f32 x 3,
+        rgba u8 x 4) and u32 [T, 3].  index >= 0: the active models (0 = background); index < 0: the kept inactive model -1 - index.
+        with_transform: also the 4x4 Tp = globalPose * modelPose^-1 that save_mesh applies."""
+        from .mesh import VERTEX
+        f = self.lib.cofusion_model_mesh
+        f.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        nv, nt = C.c_uint32(), C.c_uint32()
+        tp = np.zeros((4, 4), np.float32)
+        self._check(f(self.h, int(index), float(voxel), C.byref(nv), C.byref(nt), None, 0, None, 0, tp.ctypes.data_as(C.c_void_p)))
+        v = np.zeros(nv.value, VERTEX)
+        t = np.zeros((nt.value, 3), np.uint32)
+        if nv.value:
+            self._check(f(self.h, int(index), float(voxel), C.byref(nv), C.byref(nt), v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p),
+                          len(t), None))
+        return (v, t, tp) if with_transform else (v, t)
+
+    def set_mesh_max_voxels(self, max_voxels):
+        """grid samples the mesher is created for (default 2^24, 64 bytes each); the default grid's voxel grows until the map fits"""
+        self.lib.cofusion_set_mesh_max_voxels.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(self.lib.cofusion_set_mesh_max_voxels(self.h, int(max_voxels)))
+
     def set_export_segmentation(self, prefix):
         """every segmented frame writes <prefix>Segmentation<tick>.png (labels, rejected superpixels as 0); '' switches it off"""
         self._check(self.lib.cofusion_set_export_segmentation(self.h, str(prefix or "").encode()))

@@ -642,6 +642,7 @@ CoFusion::~CoFusion()
     exportWriter.reset();   // writes what is in flight
     pool.reset();
     releaseRenderer();
+    releaseMesher();
     if (ferns) cf_ferns_destroy(ferns);
     if (deform) cf_deform_destroy(deform);
     releaseLocalLoop();

@@ -55,6 +55,8 @@ struct SegmentationResult {
 };
 
 class CoFusion;
+// binary little-endian PLY of an indexed mesh (Mesh.cpp): x y z nx ny nz red green blue | list uchar int vertex_indices
+bool writeMeshPly(const std::string& path, const cf_mesh_vertex* vertices, uint32_t nVertices, const uint32_t* triangles, uint32_t nTriangles);
 class EnqueuePool;
 
 // host wall-clock per phase of processFrame (diagnostics: where the host keeps the GPU waiting)
@@ -309,6 +311,19 @@ class CoFusion {
     // CoFusion::savePly / exportPoses (CoFusion.cpp:646-783); exportDir is a prefix ("out/"); return files written or -1
     int savePly(const std::string& exportDir);
     int exportPoses(const std::string& exportDir);
+    // Mesh export (Mesh.cpp over cf_mesh_*): <prefix>mesh-<id>.ply per owned active model, a triangle mesh of its
+    // confident surfels extracted on the device; voxel 0: the model's mean confident radius.  Returns files written or -1.
+    int saveMesh(const std::string& exportDir, float voxel = 0.f);
+    // one model's mesh in the model's own frame.  index >= 0: the active models in list order (0 = background); index < 0: the kept
+    // inactive model number -1 - index.  extractMesh runs both stages and keeps the result on the device (counts 0 for a model this rank
+    // does not own); keptMesh: the counts of what is kept, when it is the mesh of (index, voxel) at the current tick; downloadMesh
+    // copies it out.  meshTransform: Tp = globalPose * modelPose^-1, which saveMesh applies.
+    void extractMesh(int index, float voxel, uint32_t* nVertices, uint32_t* nTriangles);
+    bool keptMesh(int index, float voxel, uint32_t* nVertices, uint32_t* nTriangles) const;
+    void downloadMesh(cf_mesh_vertex* vertices, uint32_t* triangles);
+    Model* meshModel(int index);
+    Mat4f meshTransform(Model& model) const;
+    void setMeshMaxVoxels(uint64_t n);               // grid samples the mesher is created for (default 2^24, 64 bytes each)
     // exportSegmentation (CoFusion.cpp:235-240): when set, every segmented frame writes <prefix>Segmentation<tick>.png (8-bit labels)
     void setExportSegmentation(const std::string& prefix) { exportSegmentationPrefix = prefix; }
     // Scene rendering (Render.cpp over cf_render): every active model drawn into one view, depth-tested against the others, the
@@ -601,6 +616,11 @@ class CoFusion {
     void releaseRenderer();
     void exportViews(int frameTick);
     std::unique_ptr<ExportWriter> exportWriter;   // setExportAsync
+    // mesh export: created at first use (Mesh.cpp)
+    cf_mesher* mesher = nullptr;
+    uint64_t meshMaxVoxels = 1ull << 24;
+    bool meshKept = false; int meshIndex = 0; float meshVoxel = 0.f; int meshTick = 0; uint32_t meshVertices = 0, meshTriangles = 0;
+    void releaseMesher();
     bool useLanes = true;  // per-model auxiliary streams
     std::shared_ptr<EnqueuePool> pool;                      // Config::enqueueThreads helpers
     void modelPasses(Model& model, bool fuse, float weightMultiplier, bool lost);

@@ -503,6 +503,39 @@ int cofusion_save_ply(cofusion_handle* h, const char* prefix)
     try { const int n = h->cf->savePly(prefix ? prefix : ""); if (n < 0) g_err = "savePly: cannot write"; return n; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+int cofusion_save_mesh(cofusion_handle* h, const char* prefix, float voxel)
+{
+    if (!h) { g_err = "cofusion_save_mesh: no instance"; return -1; }
+    try { const int n = h->cf->saveMesh(prefix ? prefix : "", voxel); if (n < 0) g_err = "saveMesh: cannot write"; return n; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int cofusion_model_mesh(cofusion_handle* h, int index, float voxel, uint32_t* n_vertices, uint32_t* n_triangles, cf_mesh_vertex* vertices,
+                        uint32_t vertex_capacity, uint32_t* triangles, uint32_t triangle_capacity, float transform[16])
+{
+    if (!h || !n_vertices || !n_triangles) { g_err = "cofusion_model_mesh: bad arguments"; return -1; }
+    Model* m = h->cf->meshModel(index);
+    if (!m) { g_err = "model index out of range"; return -1; }
+    const bool copy = vertices || triangles;
+    // counts first: a call without arrays extracts and keeps the mesh; a call with arrays copies the kept one (or extracts, if none fits)
+    GUARD(if (!copy || !h->cf->keptMesh(index, voxel, n_vertices, n_triangles)) h->cf->extractMesh(index, voxel, n_vertices, n_triangles));
+    if (transform) { const Mat4f T = h->cf->meshTransform(*m); for (int i = 0; i < 16; i++) transform[i] = T.m[i]; }
+    if (!copy || (*n_vertices == 0 && *n_triangles == 0)) return 0;
+    if (!vertices || !triangles || vertex_capacity < *n_vertices || triangle_capacity < *n_triangles) { g_err = "cofusion_model_mesh: arrays too small"; return -1; }
+    GUARD(h->cf->downloadMesh(vertices, triangles));
+    return 0;
+}
+int cofusion_set_mesh_max_voxels(cofusion_handle* h, uint64_t max_voxels)
+{
+    if (!h) { g_err = "cofusion_set_mesh_max_voxels: no instance"; return -1; }
+    GUARD(h->cf->setMeshMaxVoxels(max_voxels));
+    return 0;
+}
+int cofusion_write_mesh_ply(const char* path, const cf_mesh_vertex* vertices, uint32_t n_vertices, const uint32_t* triangles, uint32_t n_triangles)
+{
+    if (!path) { g_err = "cofusion_write_mesh_ply: no path"; return -1; }
+    if (!writeMeshPly(path, vertices, n_vertices, triangles, n_triangles)) { g_err = std::string("cannot write ") + path; return -1; }
+    return 0;
+}
 int cofusion_export_poses(cofusion_handle* h, const char* prefix)
 {
     try { const int n = h->cf->exportPoses(prefix ? prefix : ""); if (n < 0) g_err = "exportPoses: cannot write"; return n; }

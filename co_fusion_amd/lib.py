@@ -48,6 +48,8 @@ SYMBOLS = [
     "cf_ferns_gate_async", "cf_ferns_gate_wait", "cf_ferns_constraints", "cf_ferns_find_frame", "cf_ferns_constraint_buffers", "cf_ferns_keyframe_buffers",
     "cf_local_loop_create", "cf_local_loop_destroy", "cf_local_loop_constraints_async", "cf_local_loop_wait", "cf_local_loop_constraint_buffers",
     "cf_local_loop_target_times",
+    "cf_mesh_create", "cf_mesh_destroy", "cf_mesh_default_grid", "cf_mesh_accumulate", "cf_mesh_extract", "cf_mesh_download", "cf_mesh_grid_download",
+    "cf_mesh_extract_grid", "cf_mesh_timing",
 ]
 
 
@@ -82,6 +84,7 @@ HOST_SYMBOLS = [
     "cofusion_image_player_open", "cofusion_image_player_next", "cofusion_image_player_process", "cofusion_image_player_rewind", "cofusion_image_player_set_limits",
     "cofusion_image_player_times", "cofusion_image_player_close",
     "cofusion_image_prefetch_open", "cofusion_image_prefetch_next", "cofusion_image_prefetch_rewind", "cofusion_image_prefetch_close",
+    "cofusion_save_mesh", "cofusion_model_mesh", "cofusion_set_mesh_max_voxels", "cofusion_write_mesh_ply",
     "cofusion_png_decode", "cofusion_png_finish_host", "cofusion_exr_decode", "cofusion_exr_finish_host", "cofusion_ppm_decode",
 ]
 _host = None

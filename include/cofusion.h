@@ -321,6 +321,23 @@ int cofusion_debug_phase_ms(double *out, int n, long *frames, int reset);
  * number of files written or a negative error */
 int cofusion_save_ply(cofusion_handle *h, const char *export_dir_prefix);
 int cofusion_export_poses(cofusion_handle *h, const char *export_dir_prefix);
+/* Mesh export (CoFusion::saveMesh over cf_mesh_*, include/cofusion_hip.h): writes <prefix>mesh-<id>.ply per owned
+ * active model -- binary little-endian, vertices x y z nx ny nz red green blue, faces list uchar int vertex_indices --, a triangle mesh
+ * of the model's confident surfels extracted on the device.  voxel 0: the model's mean confident radius.  Positions are mapped by
+ * Tp = globalPose * modelPose^-1 as in savePly, normals by Tp's rotation block; normals point outside (the side the surface was seen
+ * from).  Returns the number of files written or a negative error.  Off unless called; the first call creates the mesher (64 bytes per
+ * voxel of cofusion_set_mesh_max_voxels, default 2^24), which the instance keeps. */
+int cofusion_save_mesh(cofusion_handle *h, const char *export_dir_prefix, float voxel);
+/* one model's mesh in the MODEL's frame (before Tp).  index >= 0: the active models in list order (0 = background); index < 0: the kept
+ * inactive model number -1 - index (-1 is the first of cofusion_num_inactive_models).  Counts first: a call with vertices and triangles
+ * NULL extracts the mesh, keeps it on the device and returns the counts; a call with arrays (capacities in records / triangles) copies
+ * the kept mesh of the same index and voxel out, extracting first when none is kept or a frame was processed since.  transform
+ * (nullable): the Tp cofusion_save_mesh applies.  A model this rank does not own: counts 0. */
+int cofusion_model_mesh(cofusion_handle *h, int index, float voxel, uint32_t *n_vertices, uint32_t *n_triangles, cf_mesh_vertex *vertices,
+                        uint32_t vertex_capacity, uint32_t *triangles, uint32_t triangle_capacity, float transform[16]);
+int cofusion_set_mesh_max_voxels(cofusion_handle *h, uint64_t max_voxels);   /* 1 .. 2^28; drops a mesher of another size */
+/* the PLY writer alone (host code): n_vertices records and n_triangles x 3 indices to `path` */
+int cofusion_write_mesh_ply(const char *path, const cf_mesh_vertex *vertices, uint32_t n_vertices, const uint32_t *triangles, uint32_t n_triangles);
 /* exportSegmentation (CoFusion.cpp:235-240): every segmented frame writes <prefix>Segmentation<tick>.png; NULL / "" switches it off */
 int cofusion_set_export_segmentation(cofusion_handle *h, const char *export_dir_prefix);
 

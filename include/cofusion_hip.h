@@ -1121,6 +1121,57 @@ int cf_deform_download_out(cf_deform *d, void *out32);
  * factor and its rows); it rewrites Y with the same bytes.  Enqueued only. */
 int cf_deform_bench_relative_y(cf_deform *d);
 
+/* ------------------------------------------------ mesh export ---- */
+/* A triangle mesh of one surfel map, extracted on the device in two stages (csrc/mesh.hip; tests/mesh_ref.py states both in numpy
+ * and the device equals it bit for bit, order of the output included):
+ *   (a) every confident surfel (conf > conf_threshold, savePly's rule) adds a quantised weight and signed distance to the samples of
+ *       a dense grid inside its support, with 64-bit INTEGER atomics (sums that commute: no dependence on launch shape or arrival);
+ *   (b) marching tetrahedra on Kuhn's six tetrahedra per cell: shared vertices on 7 edge kinds per sample, ordered by (sample, kind);
+ *       triangles ordered by (cell, tetrahedron, triangle), wound so that the geometric normal points outside.
+ * Positive distance = outside = the side a surfel was observed from (stored normals point away from the camera; they are negated here
+ * as savePly negates them).  A cell emits only when its 8 corners are valid: unobserved space leaves an open boundary.  Triangles of
+ * zero area (a sample exactly on the surface) are kept: the topology comes first.  A voxel far below the surfel radius leaves holes
+ * once the support radius hits its cap of max_support_voxels.
+ * A cf_mesher owns the grid and the scan scratch for max_voxels samples (64 bytes each); vertices and triangles are allocated after the
+ * counting pass.  Every launch is enqueued on the context's stream behind the frame's lanes (as cf_render); the host waits only for
+ * the counts, the default grid's bounds and the downloads.  Nothing of the frame loop is touched. */
+#define CF_ERANGE (-5)              /* a grid over max_voxels, or a vertex / triangle count over 2^32 - 1 */
+typedef struct cf_mesher cf_mesher;
+typedef struct {
+    float origin[3];                /* sample (0, 0, 0) */
+    float voxel;                    /* > 0 */
+    int32_t nx, ny, nz;             /* corner samples per axis; sample (x, y, z) has the linear index (z * ny + y) * nx + x */
+} cf_mesh_grid;
+typedef struct {                    /* NULL where a call takes one: 3, 4, 100 */
+    float trunc_voxels;             /* tau = trunc_voxels * voxel */
+    float max_support_voxels;       /* rho = clamp(radius, 1.5 voxel, max_support_voxels * voxel) */
+    float conf_cap;                 /* w = min(conf, conf_cap) * (1 - t^2 / rho^2) */
+} cf_mesh_params;
+typedef struct { float x, y, z, nx, ny, nz; uint8_t r, g, b, a; } cf_mesh_vertex;   /* 28 bytes */
+#define CF_MESH_MAX_VOXELS (1u << 28)
+int cf_mesh_create(cf_ctx *ctx, uint64_t max_voxels, cf_mesher **out);   /* 1 .. CF_MESH_MAX_VOXELS */
+void cf_mesh_destroy(cf_mesher *m);
+/* the default placement: the exact box of the confident surfels padded by tau; voxel = 0: the mean confident radius (an exact integer
+ * sum of radii quantised to 2^-16); the voxel grows by a quarter at a time until the grid fits max_voxels.  No confident surfel: a grid
+ * of 0 x 0 x 0 samples, which the other calls accept and turn into an empty mesh.  One host wait (the bounds). */
+int cf_mesh_default_grid(cf_mesher *m, cf_model *model, float conf_threshold, float voxel, cf_mesh_grid *grid);
+/* stage (a): clears the grid, then adds the surfels of `model`, or, with model NULL, the `count` surfels at surfels_dev (device, 12 f32
+ * each).  CF_ERANGE when the grid has more samples than max_voxels.  Enqueued only. */
+int cf_mesh_accumulate(cf_mesher *m, cf_model *model, const float *surfels_dev, uint32_t count, float conf_threshold, const cf_mesh_grid *grid,
+                       const cf_mesh_params *params);
+/* stage (b) on the accumulated grid: a sample is valid iff its weight sum is at least max(rint(w_min * 2^12), 1); its distance is
+ * (float)((double)sum(wq dq) / (double)sum(wq)).  Waits for the two counts. */
+int cf_mesh_extract(cf_mesher *m, float w_min, uint32_t *n_vertices, uint32_t *n_triangles);
+/* host arrays of the last extraction: n_vertices records, n_triangles x 3 indices; either may be NULL */
+int cf_mesh_download(cf_mesher *m, cf_mesh_vertex *vertices, uint32_t *triangles);
+/* test access: the integer accumulators of the last cf_mesh_accumulate, int64 [5][nz * ny * nx]: sum wq dq, sum wq, sum wq {r, g, b} */
+int cf_mesh_grid_download(cf_mesher *m, int64_t *acc_host);
+/* test access: stage (b) on a caller's field (host arrays: sdf f32 [n], valid u8 [n], rgb f32 [n][3] or NULL for black) */
+int cf_mesh_extract_grid(cf_mesher *m, const cf_mesh_grid *grid, const float *sdf_host, const uint8_t *valid_host, const float *rgb_host,
+                         uint32_t *n_vertices, uint32_t *n_triangles);
+/* benchmark access: milliseconds of the last cf_mesh_accumulate and of the last extraction, by device events (waits for them) */
+int cf_mesh_timing(cf_mesher *m, float *accumulate_ms, float *extract_ms);
+
 #ifdef __cplusplus
 }
 #endif

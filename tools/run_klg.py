@@ -52,6 +52,10 @@ def main():
     ap.add_argument("--export-viewport", action="store_true", help="Viewport<n>.png: every model in colour (-ev)")
     ap.add_argument("--export-async", action="store_true", help="the per-frame PNG exports through the device encoder and writer threads")
     ap.add_argument("--export-workers", type=int, default=2, help="writer threads of --export-async (1..8)")
+    ap.add_argument("--export-mesh", action="store_true", help="mesh-<id>.ply per model at the end of the run: a triangle mesh of the confident "
+                                                               "surfels, extracted on the device (DESIGN.md 4.15)")
+    ap.add_argument("--mesh-voxel", type=float, default=0.0, help="voxel size of --export-mesh in metres (default 0: each model's mean confident "
+                                                                  "surfel radius; far below the radius the mesh gets holes)")
     ap.add_argument("--max-surfels", type=int, default=3072 * 3072)
     ap.add_argument("--relocalise", action="store_true", help="failure detection (-rl) with the fern keyframe database: a lost camera recovers")
     ap.add_argument("--fern-threshold", type=float, default=0.3095, help="a frame becomes a keyframe when it differs more than this from every keyframe")
@@ -206,6 +210,8 @@ def main():
         s = cf.export_stats()
         print(f"asynchronous exports: {s['images']} files, {s['bytes']} bytes, {s['stalls']} submits waited for a slot")
     print(f"exported {cf.export_poses(prefix)} pose file(s), {cf.save_ply(prefix)} PLY cloud(s) to {prefix}")
+    if a.export_mesh:
+        print(f"exported {cf.save_mesh(prefix, a.mesh_voxel)} PLY mesh(es) to {prefix}")
     cf.close()
 
 
