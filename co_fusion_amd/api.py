@@ -65,6 +65,16 @@ class So3System(C.Structure):
                 ("sync", C.c_uint64 * 418)]
 
 
+class RgbSystem(C.Structure):
+    """cf_rgb_system: one system of cf_rgb_records_step (the level's device images, the range of a culled tracker, the record buffer and
+    the accumulator words before and after the residual pass, the RGB sums, the state / twin / hot block of the solve under mode 2)"""
+    _fields_ = [("cand", C.c_void_p), ("next_depth", C.c_void_p), ("last_depth", C.c_void_p), ("last_image", C.c_void_p), ("next_image", C.c_void_p),
+                ("cloud", C.c_void_p), ("dIdx", C.c_void_p), ("dIdy", C.c_void_p), ("no_counts", C.c_int32), ("ranged", C.c_int32),
+                ("res_range", C.c_uint32 * 2), ("res_blocks", C.c_int32), ("records", C.c_void_p), ("slot_counts", C.c_void_p),
+                ("count_seed", C.c_int64 * 64), ("sigma_seed", C.c_int64 * 64), ("count_total", C.c_int64), ("sigma_total", C.c_int64),
+                ("rgb_sums", C.c_int64 * 32), ("state", GnState), ("twin", GnState), ("hot", C.c_uint32 * 48)]
+
+
 class Profile(C.Structure):
     _fields_ = [("icp_ms_total", C.c_double), ("icp_launches", C.c_uint64), ("icp_bytes", C.c_uint64),
                 ("surfel_ms_total", C.c_double), ("surfel_calls", C.c_uint64), ("surfel_bytes", C.c_uint64)]
@@ -296,6 +306,15 @@ class Context:
         them (copied); returns the array with the device state, the hot block and the sync block of every system"""
         arr = systems if isinstance(systems, C.Array) else (So3System * len(systems))(*systems)
         self._check(self.lib.cf_so3_prealign_step(self.h, len(arr), arr, int(bool(do_so3)), int(first_level)))
+        return arr
+
+    def rgb_records_step(self, systems, cols, rows, max_depth_delta, sobel_scale, fx, fy, next_level=2, last_of_level=False):
+        """cf_rgb_records_step: the compact residual pass and the RGB step over its record slots as the schedule launches them under the
+        context's gn mode (1 or 2) and launch shape.  systems: a ctypes array of 1..16 RgbSystem (updated in place; `records` and
+        `slot_counts` point at host arrays the caller keeps alive) or a sequence of them (copied); returns the array"""
+        arr = systems if isinstance(systems, C.Array) else (RgbSystem * len(systems))(*systems)
+        self._check(self.lib.cf_rgb_records_step(self.h, len(arr), arr, int(cols), int(rows), C.c_float(max_depth_delta), C.c_float(sobel_scale),
+                                                 C.c_float(fx), C.c_float(fy), int(next_level), int(bool(last_of_level))))
         return arr
 
     def set_icp_launch(self, threads, ppt):

@@ -50,11 +50,8 @@ int cf_odom_create(cf_ctx* ctx, cf_odom** out)
         if (int r = each_level_buffer(od, i, n, [&](auto*& p, size_t count) { return dmalloc(ctx, &p, count); })) return r;
     }
     if (int r = dmalloc(ctx, &od->icp_acc, (size_t)kGroups * 32)) return r;
-    {   // 64 groups of grouped atomics, or (cf_set_gn_mode 2) one row of totals per workgroup of the RGB step: a workgroup per 2 record slots
-        const size_t slots0 = (n0 + 255) / 256, quads0 = (slots0 + 1) / 2;   // (slots of >= 256 pixels: cf_set_icp_launch allows 64-thread workgroups)
-        od->rgb_acc_words = (quads0 > (size_t)kGroups ? quads0 : (size_t)kGroups) * 32;
-        if (int r = dmalloc(ctx, &od->rgb_acc, od->rgb_acc_words)) return r;
-    }
+    od->rgb_acc_words = rgb_acc_rows(n0) * 32;
+    if (int r = dmalloc(ctx, &od->rgb_acc, od->rgb_acc_words)) return r;
     if (int r = dmalloc(ctx, &od->occ, ((size_t)(W >> 2) * (H >> 2) + 3) / 4 * 4)) return r;
     if (int r = dmalloc(ctx, &od->aabb, 8)) return r;
     if (int r = dmalloc(ctx, &od->res_range, 8)) return r;

@@ -101,11 +101,16 @@ void gn_state_from_dev(const OdomDev* h, cf_gn_state* g)  // every word back, th
     g->lastRGBError = h->lastRGBError; g->level_done = h->level_done; g->solves = h->solves; memcpy(g->residual, h->residual, 8);
     memcpy(g->cull_z, h->cull_z, 8); memcpy(g->pose_inv, h->pose_inv, sizeof(g->pose_inv)); g->stats = h->stats;
 }
-struct GnStepBuffers {   // temporaries of one cf_gn_solve_step / cf_so3_prealign_step call
+struct GnStepBuffers {   // temporaries of one cf_gn_solve_step / cf_so3_prealign_step / cf_rgb_records_step call
     hipStream_t stream = nullptr;
     OdomDev* d_states = nullptr; unsigned long long* d_acc = nullptr; OdomDev* h_twins = nullptr;
+    cf_dataterm* d_recs = nullptr; unsigned* d_range = nullptr; So3Sync* d_sync = nullptr;   // (cf_rgb_records_step)
     // (an entry that fails half way returns with copies and the launch still enqueued: nothing they touch is released before the stream is idle)
-    ~GnStepBuffers() { (void)hipStreamSynchronize(stream); (void)hipFree(d_states); (void)hipFree(d_acc); if (h_twins) (void)hipHostFree(h_twins); }
+    ~GnStepBuffers()
+    {
+        (void)hipStreamSynchronize(stream); (void)hipFree(d_states); (void)hipFree(d_acc); if (h_twins) (void)hipHostFree(h_twins);
+        (void)hipFree(d_recs); (void)hipFree(d_range); (void)hipFree(d_sync);
+    }
 };
 }  // namespace
 
@@ -309,6 +314,108 @@ int cf_gn_solve_step(cf_ctx* ctx, int n, cf_gn_system* systems, int next_level, 
         gn_state_from_dev(&h[(size_t)k], &systems[k].state);
         gn_state_from_dev(&buf.h_twins[k], &systems[k].twin);
         memcpy(systems[k].hot, &h[(size_t)k].hot, sizeof(GnHot));
+    }
+    return CF_OK;
+}
+
+// The record-slot path of the photometric term on its own, two launches as the schedule issues them for an rgb_only call: (a) the compact
+// residual pass (launch_rgb_records_residual: the {ICP || residual} launch without its ICP half), (b) the RGB step over the slots it left
+// (launch_rgb_slot_step: rgb_slot_step_kernel under cf_set_gn_mode 1, rgb_step_solve_kernel -- whose last workgroup solves -- under 2), on
+// temporary device states, accumulators, record buffers and sync blocks filled from the caller's words.
+int cf_rgb_records_step(cf_ctx* ctx, int n, cf_rgb_system* systems, int cols, int rows, float max_depth_delta, float sobel_scale, float fx, float fy,
+                        int next_level, int last_of_level)
+{
+    if (!ctx || !systems || n < 1 || n > kMaxBatch || cols <= 0 || rows <= 0 || (cols % 4) || next_level < -1 || next_level > 2) return CF_EINVAL;
+    const size_t N = (size_t)cols * rows;
+    if (N > (size_t)ctx->cfg.width * ctx->cfg.height || N > (1u << 22)) return CF_EINVAL;   // (22-bit pixel index in the records)
+    const int mode = ctx->gn_mode;
+    if (mode == 0 || ctx->icp_arith == CF_ICP_ARITH_REFERENCE) { ctx->set_error("cf_rgb_records_step: the record slots exist under cf_set_gn_mode 1 and 2 of the fixed-point arithmetic only"); return CF_EINVAL; }
+    if (mode == 2 && ctx->xcd_round_robin != 1) { ctx->set_error("cf_rgb_records_step: cf_set_gn_mode 2 needs workgroups dealt round-robin over 8 XCDs"); return CF_EINVAL; }
+    for (int k = 0; k < n; k++) {
+        const cf_rgb_system& y = systems[k];
+        if (!y.cand || !y.next_depth || !y.last_depth || !y.last_image || !y.next_image || !y.cloud || !y.dIdx || !y.dIdy || !y.records || !y.slot_counts) return CF_EINVAL;
+    }
+    static_assert(sizeof(systems->hot) == sizeof(GnHot) && sizeof(systems->count_seed) == 8 * kGroups, "cf_rgb_system mirrors the hot block and the accumulator groups");
+    constexpr size_t kAccWords = (size_t)kGroups * 32;
+    const size_t rgb_words = rgb_acc_rows(N) * 32, acc_words = kAccWords + rgb_words;
+    const int slot_px = ctx->icp_launch.threads * 4, n_slots = (int)((N + slot_px - 1) / slot_px);
+    std::vector<OdomDev> h((size_t)n);   // (declared in front of buf: destroyed behind its synchronisation)
+    std::vector<unsigned long long> seeds((size_t)n * kAccWords), acc_a((size_t)n * kAccWords), acc_b((size_t)n * kAccWords);
+    std::vector<unsigned> ranges((size_t)n * 2);
+    GnStepBuffers buf;
+    buf.stream = ctx->stream;
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_states), sizeof(OdomDev) * n));
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_acc), 8 * acc_words * n));
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_recs), sizeof(cf_dataterm) * N * n));   // (a tracker's corres image: the records alias it)
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_range), sizeof(unsigned) * 2 * n));
+    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&buf.d_sync), sizeof(So3Sync) * n));
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&buf.h_twins), sizeof(OdomDev) * n, hipHostMallocCoherent));  // the solve stores into them
+    // the sums start from zero under mode 1 (grouped atomics add to them); under mode 2 every row read is a row stored by the same launch:
+    // a pattern where the rows start
+    HIPCHK(ctx, hipMemsetAsync(buf.d_acc, 0, 8 * acc_words * n, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(buf.d_recs, 0, sizeof(cf_dataterm) * N * n, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(buf.d_sync, 0, sizeof(So3Sync) * n, ctx->stream));   // (zero between launches)
+    RgbArgs ra{};
+    ra.cols = cols; ra.rows = rows; ra.il = cf_cam{fx, fy, 0, 0}; ra.sobelScale = sobel_scale; ra.maxDepthDelta = max_depth_delta;
+    ra.compact = 1; ra.slot_px = slot_px;
+    for (int k = 0; k < n; k++) {
+        cf_rgb_system& y = systems[k];
+        OdomDev* s = &h[(size_t)k];
+        memset(s, 0, sizeof(*s));
+        gn_state_to_dev(y.state, s);
+        s->icp_acc = buf.d_acc + acc_words * k; s->rgb_acc = s->icp_acc + kAccWords;
+        s->sobelScale = sobel_scale; s->maxDepthDeltaRGB = max_depth_delta;
+        s->host_twin = &buf.h_twins[k];   // (what the solve of mode 2 publishes to when the schedule ends)
+        refresh_hot(s);
+        memset(&buf.h_twins[k], 0, sizeof(OdomDev));
+        gn_state_to_dev(y.twin, &buf.h_twins[k]);
+        if (mode == 2) HIPCHK(ctx, hipMemsetAsync(s->rgb_acc, 0xA5, 8 * rgb_words, ctx->stream));
+        unsigned long long* seed = &seeds[(size_t)k * kAccWords];
+        for (int g = 0; g < kGroups; g++) { seed[(size_t)g * 32 + 29] = (unsigned long long)y.count_seed[g]; seed[(size_t)g * 32 + 30] = (unsigned long long)y.sigma_seed[g]; }
+        HIPCHK(ctx, hipMemcpyAsync(s->icp_acc, seed, 8 * kAccWords, hipMemcpyHostToDevice, ctx->stream));
+        OdomDev level = *s;   // the level's view of the tracker for rgb_model_args: its images, its record buffer, its size
+        level.width = cols; level.height = rows;
+        level.cand[0] = y.cand; level.nextDepth[0] = y.next_depth; level.lastDepth[0] = y.last_depth; level.lastImage[0] = y.last_image;
+        level.nextImage[0] = y.next_image; level.cloud[0] = y.cloud; level.dIdx[0] = y.dIdx; level.dIdy[0] = y.dIdy;
+        level.corres[0] = buf.d_recs + N * k;
+        level.res_range = y.ranged ? buf.d_range + 2 * k : nullptr;
+        ra.m[k] = rgb_model_args(&level, buf.d_states + k, 0);
+        ra.m[k].no_counts = y.no_counts ? 1 : 0;
+        ra.m[k].res_blocks = y.ranged ? y.res_blocks : 0;
+        ranges[(size_t)2 * k] = y.res_range[0]; ranges[(size_t)2 * k + 1] = y.res_range[1];
+        HIPCHK(ctx, hipMemcpyAsync(ra.m[k].recs, y.records, 8 * N, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ra.m[k].slot_counts, y.slot_counts, sizeof(unsigned) * n_slots, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(buf.d_range, ranges.data(), sizeof(unsigned) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(buf.d_states, h.data(), sizeof(OdomDev) * n, hipMemcpyHostToDevice, ctx->stream));
+    launch_rgb_records_residual(ctx->stream, ctx->icp_launch, ra, n, 0);                                   // (a)
+    LAUNCHCHK(ctx);
+    for (int k = 0; k < n; k++) {
+        HIPCHK(ctx, hipMemcpyAsync(systems[k].records, ra.m[k].recs, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(systems[k].slot_counts, ra.m[k].slot_counts, sizeof(unsigned) * n_slots, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&acc_a[(size_t)k * kAccWords], ra.m[k].icp_acc, 8 * kAccWords, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    launch_rgb_slot_step(ctx->stream, ra, buf.d_sync, n, mode, ctx->icp_launch.gram ? -1 : CF_FIX_ICP, next_level, last_of_level ? 1 : 0);   // (b)
+    LAUNCHCHK(ctx);
+    if (mode == 2) HIPCHK(ctx, hipMemcpyAsync(h.data(), buf.d_states, sizeof(OdomDev) * n, hipMemcpyDeviceToHost, ctx->stream));
+    else for (int k = 0; k < n; k++)
+        HIPCHK(ctx, hipMemcpyAsync(&acc_b[(size_t)k * kAccWords], ra.m[k].rgb_acc, 8 * kAccWords, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) {
+        cf_rgb_system& y = systems[k];
+        unsigned long long c = 0, g2 = 0;
+        for (int g = 0; g < kGroups; g++) { c += acc_a[(size_t)k * kAccWords + (size_t)g * 32 + 29]; g2 += acc_a[(size_t)k * kAccWords + (size_t)g * 32 + 30]; }
+        y.count_total = (int64_t)c; y.sigma_total = (int64_t)g2;
+        for (int w = 0; w < 32; w++) {
+            unsigned long long t = 0;
+            for (int g = 0; g < kGroups && mode != 2; g++) t += acc_b[(size_t)k * kAccWords + (size_t)g * 32 + w];
+            y.rgb_sums[w] = (int64_t)t;   // (mode 2: the solve has consumed and cleared them)
+        }
+        if (mode == 2) {
+            gn_state_from_dev(&h[(size_t)k], &y.state);
+            gn_state_from_dev(&buf.h_twins[k], &y.twin);
+            memcpy(y.hot, &h[(size_t)k].hot, sizeof(GnHot));
+        } else memcpy(y.hot, &h[(size_t)k].hot, sizeof(GnHot));   // (no solve: the block the two launches read)
     }
     return CF_OK;
 }

@@ -351,6 +351,17 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
                      OdomDev* const* h_states = nullptr /* [n] pinned host copies the last solve publishes to */,
                      const RgbPrepBatch* prep = nullptr /* n <= kPrepBatch models' RGB preparation (levels filled: rgb_prep_levels), run in the
                                                            first launch beside the SO3 pre-alignment */);
+// the RGB step over the record slots as that schedule launches it under mode 1 / 2 (rgb_slot_step_kernel / rgb_step_solve_kernel), and the
+// compact residual pass of an rgb_only call -- the {ICP || residual} launch without its ICP half -- on their own (cf_rgb_records_step)
+void launch_rgb_slot_step(hipStream_t s, const RgbArgs& ra, So3Sync* so3_syncs /* [n], mode 2 */, int n, int mode, int icp_fix, int next_level, int last_of_level);
+void launch_rgb_records_residual(hipStream_t s, IcpLaunch cfg, const RgbArgs& ra, int n, int level);
+// rows of 32 words a tracker's RGB accumulator needs for frames of n0 pixels: 64 groups of grouped atomics, or (cf_set_gn_mode 2) one row of
+// totals per workgroup of the RGB step: a workgroup per 2 record slots (slots of >= 256 pixels: cf_set_icp_launch allows 64-thread workgroups)
+inline size_t rgb_acc_rows(size_t n0)
+{
+    const size_t slots0 = (n0 + 255) / 256, quads0 = (slots0 + 1) / 2;
+    return quads0 > (size_t)kGroups ? quads0 : (size_t)kGroups;
+}
 // the first launch of that schedule on its own (cf_so3_prealign_step): so3_prealign_kernel as launch_gn_track launches it
 void launch_so3_prealign(hipStream_t s, const TrackerStates& states, So3Sync* so3_syncs /* [n] */, int n, bool so3, int first_level,
                          const RgbPrepBatch* prep /* nullable */);

@@ -883,6 +883,25 @@ void launch_so3_prealign(hipStream_t s, const TrackerStates& states, So3Sync* so
     so3_prealign_kernel<<<gx * n + prep_bx * n, 256, 0, s>>>(states, so3_syncs, so3 ? 1 : 0, first_level, gx, gx * n, prep ? *prep : none, prep_bx);
 }
 
+// The RGB step over the record slots of ra's level, the grid of either slot mode: 1 -- a workgroup per slot x trackers; 2 -- a workgroup per
+// two slots, the tracker's on ONE XCD, the last of them solves (rgb_step_solve_kernel).  For the schedule and for cf_rgb_records_step.
+void launch_rgb_slot_step(hipStream_t s, const RgbArgs& ra, So3Sync* so3_syncs, int n, int mode, int icp_fix, int next_level, int last_of_level)
+{
+    const int N = ra.cols * ra.rows, n_slots = (N + ra.slot_px - 1) / ra.slot_px;
+    if (mode == 2) {
+        const int n_quads = (n_slots + 1) / 2;
+        rgb_step_solve_kernel<<<8 * n_quads * ((n + 7) / 8), 256, 0, s>>>(ra, so3_syncs, n_slots, n_quads, make_idiv(n_quads > 1 ? n_quads : 2), n,
+                                                                         icp_fix, next_level, last_of_level);
+    } else rgb_slot_step_kernel<<<dim3(n_slots, n), 256, 0, s>>>(ra, n_slots);
+}
+// The compact residual pass of an rgb_only call on its own (cf_rgb_records_step): the {ICP || residual} launch without its ICP half
+void launch_rgb_records_residual(hipStream_t s, IcpLaunch cfg, const RgbArgs& ra_in, int n, int level)
+{
+    RgbArgs ra = ra_in; ra.compact = 1; ra.slot_px = cfg.threads * 4;
+    IcpArgs a{}; a.cols = ra.cols; a.rows = ra.rows;
+    launch_icp_rgbres(s, cfg, a, ra, false, true, n, level, nullptr, nullptr);
+}
+
 bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, So3Sync* so3_syncs, const GnHook* hook, const IcpArgs icp_args[3],
                      const RgbArgs rgb_args[3], int n, int width, int height, bool so3, bool pyramid, bool fast_odom, bool rgb, bool icp, int mode,
                      ProfSink* prof, OdomDev* const* h_states, const RgbPrepBatch* prep)
@@ -949,16 +968,14 @@ bool launch_gn_track(hipStream_t s, IcpLaunch cfg, const TrackerStates& states, 
                     if (hook->split[m] && hook->fn(hook->user, 0, gn.icp_acc[m], 32, (void*)s) != 0) hook_failed = true;
             }
             if (rgb && mode == 2) {   // the RGB step's last workgroup of every tracker solves
-                const int n_slots = (N + ra.slot_px - 1) / ra.slot_px, n_quads = (n_slots + 1) / 2;
-                rgb_step_solve_kernel<<<8 * n_quads * ((n + 7) / 8), 256, 0, s>>>(ra, so3_syncs, n_slots, n_quads, make_idiv(n_quads > 1 ? n_quads : 2), n,
-                                                                                 cfg.gram ? -1 : kFixICP, next_level, last_of_level ? 1 : 0);
+                launch_rgb_slot_step(s, ra, so3_syncs, n, 2, cfg.gram ? -1 : kFixICP, next_level, last_of_level ? 1 : 0);
                 continue;
             }
             if (rgb) {
                 if (slots) {
                     const int n_slots = (N + ra.slot_px - 1) / ra.slot_px;
                     if (err_with_step) rgb_slot_step_err_kernel<<<dim3(n_slots + (N + 255) / 256, n), 256, 0, s>>>(ra, n_slots, with_cdiv(icp_args[i]));
-                    else rgb_slot_step_kernel<<<dim3(n_slots, n), 256, 0, s>>>(ra, n_slots);
+                    else launch_rgb_slot_step(s, ra, so3_syncs, n, 1, 0, next_level, last_of_level ? 1 : 0);
                 }
                 else rgb_step_kernel<<<dim3((N + 255) / 256, n), 256, 0, s>>>(ra);
             }

@@ -304,6 +304,39 @@ typedef struct {
  * krkInv / kt are prepared for.  Synchronous.  n or first_level out of range, a null pointer (the images when do_so3), a width that is
  * no multiple of 16 or a height that is no multiple of 4: CF_EINVAL, nothing enqueued. */
 int cf_so3_prealign_step(cf_ctx *ctx, int n, cf_so3_system *systems, int do_so3, int first_level);
+/* The record-slot path of the photometric term on its own (test-only, off the hot path): the two launches the schedule issues per
+ * iteration of an rgb_only call under cf_set_gn_mode 1 / 2 -- (a) the compact residual pass, four pixels per thread, which packs the
+ * valid correspondences of every workgroup into that workgroup's record slot (slot = 4 x cf_set_icp_launch threads pixels; record
+ * x = pixel k of the next image, y = pixel g of the last image | (diff + 256) << 22) and adds count and sum (int)(diff^2) to words
+ * 29 / 30 of the ICP accumulator; (b) the RGB step over the slots: rgb_slot_step_kernel (mode 1) or rgb_step_solve_kernel (mode 2,
+ * whose last workgroup runs the solve) -- on temporary device states, accumulators, record buffers and sync blocks. */
+typedef struct {
+    /* in: the level's images on the device, cols x rows */
+    const uint8_t *cand;              /* candidate mask of the frame preparation */
+    const float *next_depth, *last_depth;
+    const uint8_t *last_image, *next_image;
+    const float *cloud;               /* 3 floats per pixel of the last image */
+    const int16_t *dIdx, *dIdy;
+    int32_t no_counts;                /* the residual pass leaves words 29 / 30 alone (RgbModelArgs::no_counts) */
+    int32_t ranged;                   /* 0: every slot; 1: the slots of res_range only (a culled tracker) */
+    uint32_t res_range[2];            /* ~(first 256-pixel chunk with a candidate), last such chunk + 1 (0: none), as the preparation leaves them */
+    int32_t res_blocks;               /* residual workgroups of this system when ranged (<= 0 or more than the level's slots: one per slot) */
+    uint64_t *records;                /* host [cols * rows]: in, what the record buffer holds before (a) (x in the low word); out, after (a) */
+    uint32_t *slot_counts;            /* host [slots of the level]: in / out likewise */
+    int64_t count_seed[64], sigma_seed[64];   /* in: words 29 / 30 of the 64 accumulator groups before (a) */
+    int64_t count_total, sigma_total; /* out: the 64-group totals of words 29 / 30 after (a) */
+    int64_t rgb_sums[32];             /* out, mode 1: the 64-group totals of the RGB accumulator after (b); mode 2: zero (the solve clears the sums) */
+    cf_gn_state state;                /* in: the tracker state the launches read (rgb, rgbOnly, level_done, krkInv, kt; mode 2: all the solve reads);
+                                       * out, mode 2: after the solve, as cf_gn_solve_step returns it */
+    cf_gn_state twin;                 /* mode 2: the pinned host copy before / after, as cf_gn_system::twin */
+    uint32_t hot[48];                 /* out: the derived hot block (mode 1: as the launches read it) */
+} cf_rgb_system;
+/* `n` systems (1 <= n <= 16) in one call.  cols, rows, max_depth_delta, sobel_scale and the level's fx, fy travel once per launch (the
+ * trackers of a lock-step batch share a level); next_level / last_of_level: of the solve under mode 2, as cf_gn_solve_step.
+ * Synchronous.  n out of range, cols % 4 != 0, cols * rows above the context's size, a null pointer, cf_set_gn_mode 0 or the
+ * reference-order arithmetic (no record slots), mode 2 without round-robin workgroup placement: CF_EINVAL, nothing enqueued. */
+int cf_rgb_records_step(cf_ctx *ctx, int n, cf_rgb_system *systems, int cols, int rows, float max_depth_delta, float sobel_scale,
+                        float fx, float fy, int next_level, int last_of_level);
 /* pixels the level-0 {ICP reduction || RGB residual} launch of the last fetched tracking call visited for this tracker: the 64-pixel
  * runs inside its final screen box and the record slots between its first and last RGB candidate (the whole image for a tracker
  * that is not culled) -- the physical byte count of a roofline figure, as opposed to SURVEY 8(d)'s every-pixel-to-every-tracker */
