@@ -70,7 +70,7 @@ struct cf_model {
     void drop_preindex() { preindex_od = nullptr; preindex_time = -1; }             // every entry that rewrites the surfels or the index maps calls it
     float* rays = nullptr;  // per-pixel view rays of the splat fragment stage, float4 [H*W]
     float inv_fx = 0, inv_fy = 0;
-    // EXTENTS (surfel.hip) of the index maps: a ring of three pixel rectangles in device memory, the number of the next batched index pass
+    // EXTENTS (surf_index_dev.h) of the index maps: a ring of three pixel rectangles in device memory, the number of the next batched index pass
     // modulo 3, and "the maps may hold anything outside the ring's rectangles": true from creation, after every writer other than a
     // culled batched pass, and after a batched chain that did not get to its end
     unsigned* d_ext = nullptr;        // [3][4]
@@ -110,6 +110,71 @@ struct ExtentGuard {
 };
 
 using cf::inv44f;   // (cf_kernels.h: shared with the device)
+
+// ---- the pass arguments of ONE model, every statement once: the per-model entry points launch them as batches of one (of an item made
+// from their own arguments), cf_models_preindex / cf_models_frame_passes as the batches of a frame ----
+// Model::predictIndices of surfels [0, nb) under a host pose, or (pose == nullptr) under the inverse pose the tracker left in device memory.
+// clean_depth: the pass in front of the clean stage also packs what that stage reads per texel -- with this frame's filtered depth -- into
+// one 32-byte record (clean_kernel stages a 4x4 neighbourhood per surfel: one array and 16-byte pieces instead of three arrays).
+// No extent ring: the batched chains add theirs (next_extent).
+static IndexPassArgs index_pass_args(cf_model* m, const float* pose, const float* t_inv_dev, uint32_t nb, float maxDepth, int time, int timeDelta,
+                                     const float* clean_depth = nullptr)
+{
+    IndexPassArgs p{};
+    p.surfels = m->buf[m->target]; p.count = m->d_count; p.id_begin = 0; p.id_end = nb; p.maxDepth = maxDepth; p.time = time; p.timeDelta = timeDelta;
+    p.keys = m->keys; p.index = m->index; p.vertConf = m->vertConf; p.colorTime = m->colorTime; p.normRad = m->normRad; p.t_inv_dev = t_inv_dev;
+    if (pose) inv44f(pose, p.t_inv);
+    if (clean_depth) { p.clean_rec = m->clean_rec; p.clean_depth = clean_depth; }
+    return p;
+}
+// Model::fuse (Model.cpp:408-563): the association ...
+static SurfelFuseArgs fuse_args(const cf_model_pass& it)
+{
+    cf_model* m = it.model; const cf_ctx* ctx = m->ctx;
+    SurfelFuseArgs a;
+    a.index = m->index; a.vertConf = m->vertConf; a.normRad = m->normRad; a.rgba = it.rgba; a.depth_raw = it.depth_raw; a.depth_filt = it.depth_filtered;
+    a.mask = it.mask; a.tcx = m->tcx; a.tcy = m->tcy; memcpy(a.pose, it.pose, sizeof(a.pose)); a.cam = ctx_cam(ctx); a.inv_fx = m->inv_fx;
+    a.inv_fy = m->inv_fy; a.cols = ctx->cfg.width; a.rows = ctx->cfg.height; a.time = it.time; a.weighting = it.weighting; a.maskID = it.mask_id;
+    a.maxDepth = it.fuse_max_depth; a.records = m->records; a.new_flags = m->new_flags; a.owner = m->owner; a.flags_clean = m->new_flags_clean ? 1 : 0;
+    return a;
+}
+// ... the new unstable vertices appended in column-major draw order (transform feedback of data.geom); zero_flags: the compaction leaves the
+// flags it read cleared, the next association starts from zeros without a fill launch (the caller notes it: new_flags_clean) ...
+static ScanPassArgs fresh_compaction_args(cf_model* m) { return ScanPassArgs{m->records, m->new_flags, (long long)m->ctx->cfg.width * m->ctx->cfg.height, m->block_sums, m->d_nfresh, 0, m->fresh, nullptr, 1}; }
+// ... and update.vert over all surfels into the other buffer (the caller swaps: Model.cpp:559)
+static UpdatePassArgs update_pass_args(cf_model* m, uint32_t nb, int time) { return UpdatePassArgs{m->buf[m->target], m->d_count, nb, m->owner, m->records, time, m->buf[1 - m->target]}; }
+// Model::clean (Model.cpp:565-697) stages up to `bound` surfels -- the nb the model enters with and a new one for every pixel of the frame's
+// parity -- beside the map; CF_ENOMEM, with the error text in the name of the entry point, when they do not fit
+static int clean_staging_bound(cf_model* m, uint32_t nb, const char* who, unsigned* bound)
+{
+    const int W = m->ctx->cfg.width, H = m->ctx->cfg.height;
+    *bound = nb + (unsigned)((W / 2) * (H / 2));
+    if (*bound <= m->max_surfels + (unsigned)(W * H / 4 + 64)) return CF_OK;
+    m->ctx->set_error(std::string(who) + ": a model's surfel buffer cannot hold the clean stage's staging area (max_surfels too small)");
+    return CF_ENOMEM;
+}
+// with_rec: the index pass in front of the stage packed the texel records (index_pass_args: clean_depth)
+static CleanPassArgs clean_pass_args(const cf_model_pass& it, float outlierCoeff, int timeDelta, unsigned bound, bool with_rec)
+{
+    cf_model* m = it.model; const cf_ctx* ctx = m->ctx;
+    CleanPassArgs c;
+    c.index = m->index; c.vertConf = m->vertConf; c.colorTime = m->colorTime; c.depth_filt = it.depth_filtered; c.mask = it.mask;
+    c.rec = with_rec ? m->clean_rec : nullptr; inv44f(it.pose, c.t_inv); c.cam = ctx_cam(ctx); c.cols = ctx->cfg.width; c.rows = ctx->cfg.height;
+    c.time = it.time; c.confThreshold = it.conf_threshold; c.outlierCoeff = outlierCoeff; c.timeDelta = timeDelta; c.maskID = it.mask_id;
+    c.surfels = m->buf[m->target]; c.count = m->d_count; c.fresh = m->fresh; c.n_fresh = m->d_nfresh; c.total_bound = bound; c.staged = m->staged; c.flags = m->flags;
+    return c;
+}
+// ... and the compaction of what it kept into the other buffer: the kept total IS the new count, mirrored in pinned host memory (h_counts[0])
+static ScanPassArgs kept_compaction_args(cf_model* m, unsigned bound) { return ScanPassArgs{m->staged, m->flags, (long long)bound, m->block_sums, m->d_count, 0, m->buf[1 - m->target], m->h_counts}; }
+// ModelProjection::combinedPredict of surfels [0, nb) into the ACTIVE prediction targets (the callers of the other modes replace them)
+static SplatPassArgs splat_args(cf_model* m, const float pose[16], uint32_t nb, float maxDepth, float confThreshold, int time, int maxTime, int timeDelta)
+{
+    SplatPassArgs a{};
+    a.surfels = m->buf[m->target]; a.count = m->d_count; a.count_bound = nb; inv44f(pose, a.t_inv); a.maxDepth = maxDepth;
+    a.confThreshold = confThreshold; a.time = time; a.maxTime = maxTime; a.timeDelta = timeDelta; a.rays = m->rays; a.keys = m->keys;
+    a.image = m->splat_image; a.vertexConf = m->splat_vertex; a.normalRad = m->splat_normal; a.time16 = m->splat_time;
+    return a;
+}
 
 extern "C" {
 
@@ -259,11 +324,13 @@ int cf_model_initialise(cf_model* m, const uint8_t* rgba, const float* depth_raw
     // raw feedback
     launch_feedback(s, rgba, depth_raw, W, H, cam, m->inv_fx, m->inv_fy, m->tcx, m->tcy, time, maxDepth, m->fb_rec, m->new_flags);
     HIPCHK(ctx, hipMemsetAsync(m->fb_raw, 0, sizeof(float) * 12 * N, s));
-    launch_scan_scatter(s, m->fb_rec, m->new_flags, N, m->block_sums, m->d_count, 0, m->fb_raw);
+    const ScanPassArgs raw{m->fb_rec, m->new_flags, N, m->block_sums, m->d_count, 0, m->fb_raw, nullptr};
+    launch_scan_scatter_batch(s, &raw, 1);
     // filtered feedback (zero-filled past its own count, like the reference's zero-initialised VBO)
     launch_feedback(s, rgba, depth_filt, W, H, cam, m->inv_fx, m->inv_fy, m->tcx, m->tcy, time, maxDepth, m->fb_rec, m->new_flags);
     HIPCHK(ctx, hipMemsetAsync(m->fb_filt, 0, sizeof(float) * 12 * N, s));
-    launch_scan_scatter(s, m->fb_rec, m->new_flags, N, m->block_sums, m->d_tmp2, 0, m->fb_filt);
+    const ScanPassArgs filt{m->fb_rec, m->new_flags, N, m->block_sums, m->d_tmp2, 0, m->fb_filt, nullptr};
+    launch_scan_scatter_batch(s, &filt, 1);
     m->new_flags_clean = false;   // (the feedback passes wrote every flag)
     launch_init(s, m->fb_raw, m->fb_filt, m->d_count, N, m->buf[m->target]);
     LAUNCHCHK(ctx);
@@ -278,12 +345,11 @@ int cf_model_predict_indices(cf_model* m, const float pose[16], int time, float 
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
     m->extents_unknown();   // (an unculled pass: the index maps' footprint is not in the ring)
     cf_ctx* ctx = m->ctx;
-    float t_inv[16];
-    inv44f(pose, t_inv);
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
-    launch_predict_indices(ctx->cur(), m->buf[m->target], m->d_count, nb, t_inv, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height,
-                           maxDepth, time, timeDelta, m->keys, m->index, m->vertConf, m->colorTime, m->normRad);
+    const IndexPassArgs a = index_pass_args(m, pose, nullptr, nb, maxDepth, time, timeDelta);
+    launch_index_keys_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
+    launch_index_resolve_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -300,13 +366,12 @@ int cf_model_index_keys(cf_model* m, const float pose[16], int time, float maxDe
     m->extents_unknown();   // (keys_dev may be the model's own z-keys: cf_model_predict_indices_sharded)
     cf_ctx* ctx = m->ctx;
     const int W = ctx->cfg.width, H = ctx->cfg.height;
-    float t_inv[16];
-    inv44f(pose, t_inv);
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
     HIPCHK(ctx, hipMemsetAsync(keys_dev, 0xFF, sizeof(uint64_t) * (size_t)W * H, ctx->cur()));
-    launch_index_keys(ctx->cur(), m->buf[m->target], m->d_count, surfel_begin, surfel_end < nb ? surfel_end : nb, t_inv, ctx_cam(ctx), W, H, maxDepth,
-                      time, timeDelta, reinterpret_cast<unsigned long long*>(keys_dev));
+    IndexPassArgs a = index_pass_args(m, pose, nullptr, surfel_end < nb ? surfel_end : nb, maxDepth, time, timeDelta);
+    a.id_begin = surfel_begin; a.keys = reinterpret_cast<unsigned long long*>(keys_dev);
+    launch_index_keys_batch(ctx->cur(), &a, 1, ctx_cam(ctx), W, H);
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -316,10 +381,9 @@ int cf_model_index_resolve(cf_model* m, const float pose[16], uint64_t* keys_dev
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
     m->extents_unknown();
     cf_ctx* ctx = m->ctx;
-    float t_inv[16];
-    inv44f(pose, t_inv);
-    launch_index_resolve(ctx->cur(), m->buf[m->target], t_inv, ctx->cfg.width, ctx->cfg.height, reinterpret_cast<unsigned long long*>(keys_dev),
-                         m->index, m->vertConf, m->colorTime, m->normRad);
+    IndexPassArgs a = index_pass_args(m, pose, nullptr, 0, 0.f, 0, 0);   // (the resolve reads the keys, the surfels and the pose only)
+    a.keys = reinterpret_cast<unsigned long long*>(keys_dev);
+    launch_index_resolve_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -349,24 +413,13 @@ int cf_model_combined_predict(cf_model* m, const float pose[16], float maxDepth,
 {
     if (!m || !pose) return CF_EINVAL;
     cf_ctx* ctx = m->ctx;
-    float t_inv[16];
-    inv44f(pose, t_inv);
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
-    launch_combined_predict(ctx->cur(), m->buf[m->target], m->d_count, nb, t_inv, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height,
-                            maxDepth, confThreshold, time, maxTime, timeDelta, m->rays, m->keys, m->splat_image, m->splat_vertex, m->splat_normal,
-                            m->splat_time);
+    const SplatPassArgs a = splat_args(m, pose, nb, maxDepth, confThreshold, time, maxTime, timeDelta);
+    launch_combined_predict_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
     LAUNCHCHK(ctx);
     m->ratio_valid = false;  // a new prediction: any prefetched fill-in ratio is stale
     return CF_OK;
-}
-
-static SplatPassArgs splat_args(cf_model* m, const float pose[16], uint32_t nb, float maxDepth, float confThreshold, int time, int maxTime, int timeDelta)
-{
-    SplatPassArgs a{};
-    a.surfels = m->buf[m->target]; a.count = m->d_count; a.count_bound = nb; inv44f(pose, a.t_inv); a.maxDepth = maxDepth;
-    a.confThreshold = confThreshold; a.time = time; a.maxTime = maxTime; a.timeDelta = timeDelta; a.rays = m->rays; a.keys = m->keys;
-    return a;
 }
 
 // ModelProjection::combinedPredict(..., INACTIVE) as CoFusion.cpp:390 calls it (time = 0, so no surfel is too old; maxTime = tick -
@@ -389,7 +442,7 @@ int cf_model_predict_inactive(cf_model* m, const float pose[16], float maxDepth,
     a.image = m->old_image; a.vertexConf = m->old_vertex; a.normalRad = m->old_normal; a.time16 = m->old_time;
     a.fill.out2 = m->old_covered;
     HIPCHK(ctx, hipMemsetAsync(m->old_covered, 0, sizeof(unsigned), ctx->cur()));
-    launch_predict_counted(ctx->cur(), a, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
+    launch_combined_predict_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height, kSplatCount);
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -403,8 +456,8 @@ int cf_model_synthesize_depth(cf_model* m, const float pose[16], float maxDepth,
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
     SplatPassArgs a = splat_args(m, pose, nb, maxDepth, confThreshold, time, maxTime, timeDelta);
-    a.vertexConf = depth_out_dev;
-    launch_synthesize_depth(ctx->cur(), a, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height);
+    a.image = nullptr; a.vertexConf = depth_out_dev; a.normalRad = nullptr; a.time16 = nullptr;   // (one output: the f32 depth plane)
+    launch_combined_predict_batch(ctx->cur(), &a, 1, ctx_cam(ctx), ctx->cfg.width, ctx->cfg.height, kSplatDepth);
     LAUNCHCHK(ctx);
     return CF_OK;
 }
@@ -465,24 +518,19 @@ int cf_model_fuse(cf_model* m, const float pose[16], int time, const uint8_t* rg
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
     m->extents_unknown();
     cf_ctx* ctx = m->ctx; hipStream_t s = ctx->cur();
-    const int W = ctx->cfg.width, H = ctx->cfg.height; const long long N = (long long)W * H;
-    SurfelFuseArgs a;
-    a.index = m->index; a.vertConf = m->vertConf; a.normRad = m->normRad; a.rgba = rgba; a.depth_raw = depth_raw; a.depth_filt = depth_filt;
-    a.mask = mask; a.tcx = m->tcx; a.tcy = m->tcy; memcpy(a.pose, pose, sizeof(a.pose)); a.cam = ctx_cam(ctx); a.inv_fx = m->inv_fx;
-    a.inv_fy = m->inv_fy; a.cols = W; a.rows = H; a.time = time; a.weighting = weighting; a.maskID = maskID; a.maxDepth = maxDepth;
-    a.records = m->records; a.new_flags = m->new_flags; a.owner = m->owner; a.flags_clean = m->new_flags_clean ? 1 : 0;
-    launch_associate(s, a);
-    // append the new unstable vertices in column-major draw order (transform feedback of data.geom); the flags are left cleared
-    {
-        ScanPassArgs sp{m->records, m->new_flags, N, m->block_sums, m->d_nfresh, 0, m->fresh, nullptr};
-        sp.zero_flags = 1;
-        launch_scan_scatter_batch(s, &sp, 1);
-        m->new_flags_clean = true;
-    }
-    // update.vert over all surfels into the other buffer, then swap (Model.cpp:559)
+    // (the separate launches, never the side-by-side pair of the frame chain)
+    cf_model_pass it{};
+    it.model = m; it.pose = pose; it.rgba = rgba; it.mask = mask; it.depth_raw = depth_raw; it.depth_filtered = depth_filt; it.time = time;
+    it.fuse_max_depth = maxDepth; it.weighting = weighting; it.mask_id = maskID;
+    const SurfelFuseArgs a = fuse_args(it);
+    launch_associate_batch(s, &a, 1);
+    const ScanPassArgs sp = fresh_compaction_args(m);
+    launch_scan_scatter_batch(s, &sp, 1);
+    m->new_flags_clean = true;
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
-    launch_update(s, m->buf[m->target], m->d_count, nb, m->owner, m->records, time, m->buf[1 - m->target]);
+    const UpdatePassArgs ua = update_pass_args(m, nb, time);
+    launch_update_batch(s, &ua, 1);
     m->target = 1 - m->target;
     LAUNCHCHK(ctx);
     return CF_OK;
@@ -496,17 +544,17 @@ int cf_model_clean(cf_model* m, const float pose[16], int time, float confThresh
     m->drop_preindex();   // (the index map / surfels cf_models_preindex saw are about to change)
     m->extents_unknown();
     cf_ctx* ctx = m->ctx; hipStream_t s = ctx->cur();
-    const int W = ctx->cfg.width, H = ctx->cfg.height;
     uint32_t nb = 0;
     if (int r = count_bound(m, &nb)) return r;
-    const unsigned bound = nb + (unsigned)((W / 2) * (H / 2));
-    if (bound > m->max_surfels + (unsigned)(W * H / 4 + 64)) return CF_ENOMEM;
-    SurfelCleanArgs a;
-    a.index = m->index; a.vertConf = m->vertConf; a.colorTime = m->colorTime; a.depth_filt = depth_filt; a.mask = mask; a.rec = nullptr;
-    inv44f(pose, a.t_inv); a.cam = ctx_cam(ctx); a.cols = W; a.rows = H; a.time = time; a.confThreshold = confThreshold;
-    a.outlierCoeff = outlierCoeff; a.timeDelta = timeDelta; a.maskID = maskID;
-    launch_clean(s, m->buf[m->target], m->d_count, m->fresh, m->d_nfresh, bound, a, m->staged, m->flags);
-    launch_scan_scatter(s, m->staged, m->flags, bound, m->block_sums, m->d_count, 0, m->buf[1 - m->target], m->h_counts);  // the kept total IS the new count
+    unsigned bound = 0;
+    if (int r = clean_staging_bound(m, nb, "cf_model_clean", &bound)) return r;
+    // (no packed texel records: the index pass in front of this call was not told to stage them)
+    cf_model_pass it{};
+    it.model = m; it.pose = pose; it.mask = mask; it.depth_filtered = depth_filt; it.time = time; it.mask_id = maskID; it.conf_threshold = confThreshold;
+    const CleanPassArgs a = clean_pass_args(it, outlierCoeff, timeDelta, bound, false);
+    launch_clean_batch(s, &a, 1);
+    const ScanPassArgs sp = kept_compaction_args(m, bound);
+    launch_scan_scatter_batch(s, &sp, 1);
     m->target = 1 - m->target;
     LAUNCHCHK(ctx);
     const uint32_t upper = bound < m->max_surfels ? bound : m->max_surfels;
@@ -533,12 +581,10 @@ int cf_models_preindex(cf_ctx* ctx, const cf_model_preindex* items, int n, float
         cf_model* m = items[k].model; const cf_odom* od = items[k].odom;
         uint32_t nb = 0;
         if (int r = count_bound(m, &nb)) return r;
+        // (the inverse of the tracked pose, left in the tracker's state by the last solve of its schedule)
         const float* pinv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(od->d_state) + offsetof(cf::OdomDev, pose_inv));
-        IndexPassArgs& p = a[k];
-        p.surfels = m->buf[m->target]; p.count = m->d_count; p.id_begin = 0; p.id_end = nb; p.maxDepth = depth_cutoff; p.time = items[k].time;
-        p.timeDelta = time_delta; p.keys = m->keys; p.index = m->index; p.vertConf = m->vertConf; p.colorTime = m->colorTime; p.normRad = m->normRad;
-        p.t_inv_dev = pinv;   // (the inverse of the tracked pose, left in the tracker's state by the last solve of its schedule)
-        if (int r = next_extent(m, cull, nb, s, &p.ext, &p.ext_slot)) return r;
+        a[k] = index_pass_args(m, nullptr, pinv, nb, depth_cutoff, items[k].time, time_delta);
+        if (int r = next_extent(m, cull, nb, s, &a[k].ext, &a[k].ext_slot)) return r;
     }
     launch_index_keys_batch(s, a.data(), n, ctx_cam(ctx), W, H);
     launch_index_resolve_batch(s, a.data(), n, ctx_cam(ctx), W, H);
@@ -568,7 +614,7 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
 {
     if (!ctx || !items || n <= 0) return CF_EINVAL;
     hipStream_t s = ctx->cur();
-    const int W = ctx->cfg.width, H = ctx->cfg.height; const long long N = (long long)W * H;
+    const int W = ctx->cfg.width, H = ctx->cfg.height;
     const cf_cam cam = ctx_cam(ctx);
     std::vector<int> fusing;
     for (int k = 0; k < n; k++) {
@@ -581,12 +627,9 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
     // the model enters the chain with (the update pass rewrites the surfels in place, new ones wait in `fresh`).
     for (int k : fusing) {
         cf_model* m = items[k].model;
-        uint32_t nb = 0;
+        uint32_t nb = 0; unsigned bound = 0;
         if (int r = count_bound(m, &nb)) return r;
-        if (nb + (unsigned)((W / 2) * (H / 2)) > m->max_surfels + (unsigned)(W * H / 4 + 64)) {
-            ctx->set_error("cf_models_frame_passes: a model's surfel buffer cannot hold the clean stage's staging area (max_surfels too small)");
-            return CF_ENOMEM;
-        }
+        if (int r = clean_staging_bound(m, nb, "cf_models_frame_passes", &bound)) return r;
     }
     for (int k = 0; k < n; k++) { uint32_t nb = 0; if (int r = count_bound(items[k].model, &nb)) return r; }
     ExtentGuard guard;   // (from here on a return that is not the last one leaves the models' extents unknown)
@@ -609,22 +652,9 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
             const cf_model_pass& it = items[which[q]]; cf_model* m = it.model;
             uint32_t nb = 0;
             if (int r = count_bound(m, &nb)) return r;
-            IndexPassArgs& p = a[q];
-            p.surfels = m->buf[m->target]; p.count = m->d_count; p.id_begin = 0; p.id_end = nb; inv44f(it.pose, p.t_inv); p.maxDepth = depth_cutoff;
-            p.time = it.time; p.timeDelta = time_delta; p.keys = m->keys; p.index = m->index; p.vertConf = m->vertConf; p.colorTime = m->colorTime;
-            p.normRad = m->normRad;
-            // the pass in front of the clean stage also packs what that stage reads per texel -- with this frame's filtered depth -- into
-            // one 32-byte record (clean_kernel stages a 4x4 neighbourhood per surfel: one array and 16-byte pieces instead of three arrays)
-            if (feeds_clean && clean_rec_on) { p.clean_rec = m->clean_rec; p.clean_depth = it.depth_filtered; }
-            if (int r = next_extent(m, cull, nb, s, &p.ext, &p.ext_slot)) return r;   // (every index pass of the chain is enqueued once its arguments exist)
+            a[q] = index_pass_args(m, it.pose, nullptr, nb, depth_cutoff, it.time, time_delta, feeds_clean && clean_rec_on ? it.depth_filtered : nullptr);
+            if (int r = next_extent(m, cull, nb, s, &a[q].ext, &a[q].ext_slot)) return r;   // (every index pass of the chain is enqueued once its arguments exist)
         }
-        return CF_OK;
-    };
-    auto index_pass = [&](const std::vector<int>& which) -> int {
-        std::vector<IndexPassArgs> a;
-        if (int r = index_args_of(which, false, a)) return r;
-        launch_index_keys_batch(s, a.data(), (int)a.size(), cam, W, H);
-        launch_index_resolve_batch(s, a.data(), (int)a.size(), cam, W, H);
         return CF_OK;
     };
     if (!fusing.empty()) {
@@ -636,7 +666,10 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
                 if (int r = count_bound(items[k].model, &nb)) return r;
                 if (!preindexed_with(items[k].model, items[k].pose, items[k].time, depth_cutoff, time_delta, nb)) todo.push_back(k);
             }
-            if (!todo.empty()) { if (int r = index_pass(todo)) return r; }
+            std::vector<IndexPassArgs> a;
+            if (int r = index_args_of(todo, false, a)) return r;
+            launch_index_keys_batch(s, a.data(), (int)a.size(), cam, W, H);
+            launch_index_resolve_batch(s, a.data(), (int)a.size(), cam, W, H);
         }
         // Model::fuse (Model.cpp:408-563)
         std::vector<SurfelFuseArgs> fa(nf);
@@ -644,17 +677,12 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         std::vector<UpdatePassArgs> ua(nf);
         for (int q = 0; q < nf; q++) {
             const cf_model_pass& it = items[fusing[q]]; cf_model* m = it.model;
-            SurfelFuseArgs& a = fa[q];
-            a.index = m->index; a.vertConf = m->vertConf; a.normRad = m->normRad; a.rgba = it.rgba; a.depth_raw = it.depth_raw; a.depth_filt = it.depth_filtered;
-            a.mask = it.mask; a.tcx = m->tcx; a.tcy = m->tcy; memcpy(a.pose, it.pose, sizeof(a.pose)); a.cam = cam; a.inv_fx = m->inv_fx;
-            a.inv_fy = m->inv_fy; a.cols = W; a.rows = H; a.time = it.time; a.weighting = it.weighting; a.maskID = it.mask_id; a.maxDepth = it.fuse_max_depth;
-            a.records = m->records; a.new_flags = m->new_flags; a.owner = m->owner; a.flags_clean = m->new_flags_clean ? 1 : 0;
-            sa[q] = ScanPassArgs{m->records, m->new_flags, N, m->block_sums, m->d_nfresh, 0, m->fresh, nullptr};
-            sa[q].zero_flags = 1;   // (the compaction leaves the flags it read cleared: the next frame's association starts from zeros without a fill launch)
+            fa[q] = fuse_args(it);
+            sa[q] = fresh_compaction_args(m);
             m->new_flags_clean = true;
             uint32_t nb = 0;
             if (int r = count_bound(m, &nb)) return r;
-            ua[q] = UpdatePassArgs{m->buf[m->target], m->d_count, nb, m->owner, m->records, it.time, m->buf[1 - m->target]};
+            ua[q] = update_pass_args(m, nb, it.time);
         }
         launch_associate_batch(s, fa.data(), nf);
         // the new unstable vertices in column-major draw order (transform feedback of data.geom) || update.vert over all surfels into the
@@ -674,22 +702,13 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         }
         // Model::clean (Model.cpp:565-697)
         std::vector<CleanPassArgs> ca(nf);
-        std::vector<uint32_t> upper(nf);
         for (int q = 0; q < nf; q++) {
             const cf_model_pass& it = items[fusing[q]]; cf_model* m = it.model;
-            uint32_t nb = 0;
+            uint32_t nb = 0; unsigned bound = 0;
             if (int r = count_bound(m, &nb)) return r;
-            const unsigned bound = nb + (unsigned)((W / 2) * (H / 2));
-            if (bound > m->max_surfels + (unsigned)(W * H / 4 + 64)) return CF_ENOMEM;
-            CleanPassArgs& c = ca[q];
-            c.h.index = m->index; c.h.vertConf = m->vertConf; c.h.colorTime = m->colorTime; c.h.depth_filt = it.depth_filtered; c.h.mask = it.mask;
-            c.h.rec = clean_rec_on ? m->clean_rec : nullptr;
-            inv44f(it.pose, c.h.t_inv); c.h.cam = cam; c.h.cols = W; c.h.rows = H; c.h.time = it.time; c.h.confThreshold = it.conf_threshold;
-            c.h.outlierCoeff = outlier_coeff; c.h.timeDelta = time_delta; c.h.maskID = it.mask_id;
-            c.surfels = m->buf[m->target]; c.count = m->d_count; c.fresh = m->fresh; c.n_fresh = m->d_nfresh; c.total_bound = bound; c.staged = m->staged;
-            c.flags = m->flags;
-            sa[q] = ScanPassArgs{m->staged, m->flags, (long long)bound, m->block_sums, m->d_count, 0, m->buf[1 - m->target], m->h_counts};  // the kept total IS the new count
-            upper[q] = bound < m->max_surfels ? bound : m->max_surfels;
+            if (int r = clean_staging_bound(m, nb, "cf_models_frame_passes", &bound)) return r;   // (checked in front of the chain: cannot fail here)
+            ca[q] = clean_pass_args(it, outlier_coeff, time_delta, bound, clean_rec_on);
+            sa[q] = kept_compaction_args(m, bound);
         }
         launch_clean_batch(s, ca.data(), nf);
         launch_scan_scatter_batch(s, sa.data(), nf);
@@ -700,7 +719,7 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         for (int q = 0; q < nf; q++) {
             cf_model* m = items[fusing[q]].model;
             m->target = 1 - m->target;
-            m->count_host = upper[q]; m->count_pending = true; m->count_wait = nullptr;   // (nullptr until the event below is recorded)
+            m->count_host = ca[q].total_bound < m->max_surfels ? ca[q].total_bound : m->max_surfels; m->count_pending = true; m->count_wait = nullptr;   // (nullptr until the event below is recorded)
         }
     }
     // combinedPredict(maxDepthProcessed, time, time, timeDelta) of every model (CoFusion.cpp:533-545)
@@ -710,9 +729,7 @@ int cf_models_frame_passes(cf_ctx* ctx, const cf_model_pass* items, int n, float
         uint32_t nb = m->count_host;   // (exact, or the upper bound the clean stage has just set)
         if (!(m->count_pending && !m->count_wait)) { if (int r = count_bound(m, &nb)) return r; }
         SplatPassArgs& p = pa[k];
-        p.surfels = m->buf[m->target]; p.count = m->d_count; p.count_bound = nb; inv44f(it.pose, p.t_inv); p.maxDepth = depth_cutoff;
-        p.confThreshold = it.conf_threshold; p.time = it.time; p.maxTime = it.time; p.timeDelta = time_delta; p.rays = m->rays; p.keys = m->keys;
-        p.image = m->splat_image; p.vertexConf = m->splat_vertex; p.normalRad = m->splat_normal; p.time16 = m->splat_time;
+        p = splat_args(m, it.pose, nb, depth_cutoff, it.conf_threshold, it.time, it.time, time_delta);
         m->ratio_valid = false;  // a new prediction: any prefetched fill-in ratio is stale
         if (it.fill_in)          // Model::performFillIn and the count of cf_model_prefetch_fill_ratio inside the resolve launch (SplatFillArgs)
             p.fill = SplatFillArgs{it.depth_filtered, it.rgba, m->inv_fx, m->inv_fy, it.passthrough_geom ? 1 : 0, it.passthrough_rgb ? 1 : 0,

@@ -45,7 +45,7 @@ struct cf_ctx {
     cf::OdomDev* h_state_pool = nullptr;  // pinned
     bool slot_used[kStateSlots]{};
     hipEvent_t batch_event = nullptr;     // cf_models_frame_passes: ONE event behind a batch's compactions marks all its models' counts
-    bool extent_cull = true;              // cf_set_extent_culling: the batched surfel passes skip the texels outside the models' extents (surfel.hip, EXTENTS)
+    bool extent_cull = true;              // cf_set_extent_culling: the batched surfel passes skip the texels outside the models' extents (surf_index_dev.h, EXTENTS)
     // auxiliary streams for independent per-model work of one frame (cf_fork / cf_join)
     static constexpr int kLanes = 8;
     hipStream_t lanes[kLanes]{};

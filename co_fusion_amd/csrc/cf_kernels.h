@@ -378,9 +378,9 @@ bool probe_xcd_round_robin(hipStream_t s);   // does hardware workgroup b run on
 float sqrt_gate_lt(float T);  // smallest x with sqrtf(x) >= T
 float sqrt_gate_le(float T);  // largest x with sqrtf(x) <= T
 
-// ---- surfel launchers (surfel.hip) ----
-// Every pass exists as a LOCK-STEP BATCH: one launch covers the models of a frame (or of several sequences' frames), kSurfBatch at a
-// time -- the workgroups of the launch are dealt to the models (surfel.hip: BatchHdr).  The single-model launchers are batches of one.
+// ---- surfel launchers (surfel.hip and its stage headers surf_*_dev.h) ----
+// Every pass of the chain is a LOCK-STEP BATCH: one launch covers the models of a frame (or of several sequences' frames), kSurfBatch at a
+// time -- the workgroups of the launch are dealt to the models (surf_batch_dev.h: BatchHdr).  One model is a batch of one.
 constexpr int kSurfBatch = 16;   // models per launch (their arguments travel in the 4 KB kernel-argument segment)
 struct IndexPassArgs {   // Model::predictIndices of one model: rasterise surfels [id_begin, id_end) into the z-keys, resolve
     const float* surfels; const unsigned* count; unsigned id_begin, id_end; float t_inv[16]; float maxDepth; int time, timeDelta;
@@ -388,8 +388,8 @@ struct IndexPassArgs {   // Model::predictIndices of one model: rasterise surfel
     const float* t_inv_dev;   // nullable: the inverse pose in device memory (OdomDev::pose_inv) instead of t_inv -- an index pass enqueued
                               // before the host has seen the tracked pose (cf_models_preindex)
     float* clean_rec;         // nullable: [rows * cols][8] -- what the clean pass stages per texel, packed by the resolve pass that feeds it:
-    const float* clean_depth; // vertConf.xyzw | colorTime.z, colorTime.w, index, this filtered depth (SurfelCleanArgs::rec)
-    unsigned* ext;            // nullable: the model's ring of three index-map rectangles [3][4] (surfel.hip, EXTENTS): the rasteriser extends slot
+    const float* clean_depth; // vertConf.xyzw | colorTime.z, colorTime.w, index, this filtered depth (CleanPassArgs::rec)
+    unsigned* ext;            // nullable: the model's ring of three index-map rectangles [3][4] (surf_index_dev.h, EXTENTS): the rasteriser extends slot
     int ext_slot;             // (ext_slot & 3), the resolve skips the waves outside it and the slot before it -- unless bit 2 says that the maps may
                               // hold anything -- and zeroes the slot after it.  nullptr: every texel, no ring
 };
@@ -411,8 +411,6 @@ __host__ __device__ inline void inv44f(const float a[16], float o[16])
     }
     o[12] = 0; o[13] = 0; o[14] = 0; o[15] = 1;
 }
-// the tracked poses of n trackers (their device states, as the last solve left them), inverted into out[k][16]: what the index pass of a
-// model needs of its pose, without the host
 // Model::performFillIn and the count of CoFusion::requiresFillIn inside the resolve launch of the prediction they read (all zeros: not
 // asked for).  The thread that has just formed a texel of the prediction evaluates the fill-in on it (fill_in_px, the statements of
 // fill_in_kernel) and, at the sample positions of fill_ratio_kernel, counts it; of the workgroups that hold sample positions the one
@@ -442,15 +440,12 @@ struct SurfelFuseArgs {
     float* records; unsigned* new_flags; unsigned* owner;
     int flags_clean = 0;  // 1: new_flags is known to hold zeros (left so by the last compaction): launch_associate_batch does not clear it
 };
-struct SurfelCleanArgs {
+struct CleanPassArgs {   // Model::clean of one model
     const unsigned* index; const float* vertConf; const float* colorTime;
     const float* depth_filt; const uint8_t* mask;
     const float* rec;   // nullable: the packed records of the index pass in front of this call (IndexPassArgs::clean_rec, written with depth_filt)
     float t_inv[16]; cf_cam cam; int cols, rows, time; float confThreshold, outlierCoeff; int timeDelta, maskID;
-};
-struct CleanPassArgs {   // Model::clean of one model
-    SurfelCleanArgs h; const float* surfels; const unsigned* count; const float* fresh; const unsigned* n_fresh; unsigned total_bound;
-    float* staged; unsigned* flags;
+    const float* surfels; const unsigned* count; const float* fresh; const unsigned* n_fresh; unsigned total_bound; float* staged; unsigned* flags;
 };
 struct ScanPassArgs {    // one ordered compaction (transform feedback): the flagged 48 B records of rec [n] to out, their number (+ add) to *total
     const float* rec; const unsigned* flags; long long n; unsigned* block_sums; unsigned* total; unsigned add_to_total; float* out; unsigned* total_host;
@@ -460,40 +455,24 @@ void launch_index_keys_batch(hipStream_t s, const IndexPassArgs* items, int n, c
 bool launch_update_compaction_index_keys(hipStream_t s, const UpdatePassArgs* up, const ScanPassArgs* sc, const IndexPassArgs* ix, int n, cf_cam cam, int cols,
                                          int rows);   // the three stages as two launches (surfel.hip); false = not enqueued, use the separate launches
 void launch_index_resolve_batch(hipStream_t s, const IndexPassArgs* items, int n, cf_cam cam, int cols, int rows);
-void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, int n, cf_cam cam, int cols, int rows);
-// the same pass of one model into the targets of `a`, adding the number of covered texels (time > 0) to the device word a.fill.out2
-// (zero before the launch; a.fill.depth_filt == nullptr) / ModelProjection::synthesizeDepth: a.vertexConf is an f32 plane [rows * cols]
-void launch_predict_counted(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows);
-void launch_synthesize_depth(hipStream_t s, const SplatPassArgs& a, cf_cam cam, int cols, int rows);
+// the splat pass.  kSplatFull: combinedPredict.  kSplatCount: the same pass into the targets of the arguments, adding the number of covered
+// texels (time > 0) to the device word a.fill.out2 (zero before the launch; no fill-in: a.fill.depth_filt == nullptr).  kSplatDepth:
+// ModelProjection::synthesizeDepth -- a.vertexConf is the f32 depth plane [rows * cols], the other targets are not written
+enum { kSplatFull = 0, kSplatCount = 1, kSplatDepth = 2 };
+void launch_combined_predict_batch(hipStream_t s, const SplatPassArgs* items, int n, cf_cam cam, int cols, int rows, int mode = kSplatFull);
 void launch_associate_batch(hipStream_t s, const SurfelFuseArgs* items, int n);   // zeroes the new_flags of every model that is not flags_clean first
 void launch_update_batch(hipStream_t s, const UpdatePassArgs* items, int n);
 void launch_clean_batch(hipStream_t s, const CleanPassArgs* items, int n);
 void launch_scan_scatter_batch(hipStream_t s, const ScanPassArgs* items, int n);
+// per frame or per model, no batch form:
 void launch_bilateral(hipStream_t s, const float* depth, int cols, int rows, float maxD, float* out);
-void launch_scan_scatter(hipStream_t s, const float* rec, const unsigned* flags, long long n, unsigned* block_sums, unsigned* total,
-                         unsigned add_to_total, float* out, unsigned* total_host = nullptr /* pinned mirror of *total */);
 void launch_feedback(hipStream_t s, const uint8_t* rgba, const float* depth, int cols, int rows, cf_cam cam, float inv_fx, float inv_fy,
                      const float* tcx, const float* tcy, int time, float maxDepth, float* rec, unsigned* flags);
 void launch_init(hipStream_t s, const float* raw, const float* filt, const unsigned* raw_count, long long max_n, float* out);
-void launch_index_keys(hipStream_t s, const float* surfels, const unsigned* count, unsigned id_begin, unsigned id_end, const float t_inv[16],
-                       cf_cam cam, int cols, int rows, float maxDepth, int time, int timeDelta, unsigned long long* keys);
-void launch_index_resolve(hipStream_t s, const float* surfels, const float t_inv[16], int cols, int rows, unsigned long long* keys,
-                          unsigned* index, float* vertConf, float* colorTime, float* normRad);
-void launch_predict_indices(hipStream_t s, const float* surfels, const unsigned* count, unsigned count_bound, const float t_inv[16], cf_cam cam,
-                            int cols, int rows, float maxDepth, int time, int timeDelta, unsigned long long* keys, unsigned* index,
-                            float* vertConf, float* colorTime, float* normRad);
 void launch_splat_rays(hipStream_t s, cf_cam cam, int cols, int rows, float* rays /* [rows*cols*4] */);
-void launch_combined_predict(hipStream_t s, const float* surfels, const unsigned* count, unsigned count_bound, const float t_inv[16], cf_cam cam,
-                             int cols, int rows, float maxDepth, float confThreshold, int time, int maxTime, int timeDelta,
-                             const float* rays, unsigned long long* keys, uint8_t* image, float* vertexConf, float* normalRad, uint16_t* time16);
 void launch_fill_in(hipStream_t s, const float* pv, const float* pn, const uint8_t* pimg, const float* depth, const uint8_t* rgba, int cols,
                     int rows, cf_cam cam, float inv_fx, float inv_fy, int pass_geom, int pass_rgb, float* ov, float* on, uint8_t* oi);
 void launch_fill_ratio(hipStream_t s, const uint8_t* pimg, int cols, int rows, unsigned* out2, unsigned* out2_host = nullptr /* pinned */);
-void launch_associate(hipStream_t s, const SurfelFuseArgs& h);
-void launch_update(hipStream_t s, const float* in, const unsigned* count, unsigned count_bound, unsigned* owner, const float* records, int time,
-                   float* out);
-void launch_clean(hipStream_t s, const float* surfels, const unsigned* count, const float* fresh, const unsigned* n_fresh, unsigned total_bound,
-                  const SurfelCleanArgs& h, float* staged, unsigned* flags);
 void launch_set_count(hipStream_t s, unsigned* out, unsigned v);
 
 // ---- re-detection launchers (redetect.hip) ----

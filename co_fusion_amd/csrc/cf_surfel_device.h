@@ -1,4 +1,4 @@
-// cf_surfel_device.h -- device helpers shared by the surfel kernels (surfel.hip).
+// cf_surfel_device.h -- device helpers shared by the surfel kernels (surfel.hip and its stage headers surf_*_dev.h).
 //
 // These restate the GLSL helper files of the reference (Core/Shaders/surfels.glsl,
 // color_encoding.glsl, geometry.glsl) and pin what OpenGL leaves to the driver, exactly as the
@@ -98,7 +98,7 @@ __device__ __forceinline__ f3 xform_dir(const Mat4& T, f3 p)
 }
 
 // index_map.vert:38-63 without its time window: a surfel position into the camera of t_inv, onto its pixel q.  Shared by the index pass
-// (surfel.hip: index_project) and the re-detection score (redetect.hip), which must land every surfel on the same pixel.
+// (surf_index_dev.h: index_project) and the re-detection score (redetect.hip), which must land every surfel on the same pixel.
 __device__ __forceinline__ bool surfel_project(const float4 pc, const Mat4& t_inv, cf_cam cam, int cols, int rows, float maxDepth, f3& ph, int& q)
 {
     ph = xform_point(t_inv, f3{pc.x, pc.y, pc.z});

@@ -2,7 +2,7 @@
 //
 // What the reference's viewer draws (Core/Model/Model.cpp:274-314 with draw_global_surface.{vert,geom,frag}, objects placed by
 // view * globalPose * modelPose^-1, GUI/MainController.cpp:570-600), restated as three compute passes in the style of the splat
-// prediction (surfel.hip):
+// prediction (surf_splat_dev.h):
 //   render_rays_kernel     the per-pixel view rays of the call's intrinsics (they depend on the view only)
 //   render_raster_kernel   all items' surfels in one launch, four lanes per surfel, 64-bit (depth bits << 32 | draw index) atomicMin
 //                          keys; a footprint of more than kBigArea pixels is appended to an overflow list instead, in tiles of kTile

@@ -23,7 +23,7 @@ from orc import P, f32, u8
 from co_fusion_amd import synth
 
 K_SURF_BATCH = 16          # kSurfBatch, csrc/cf_kernels.h
-SCAN_ITEMS = 2048          # kScanItems, csrc/surfel.hip
+SCAN_ITEMS = 2048          # kScanItems, csrc/surf_scan_dev.h
 DEPTH_CUTOFF = 20.0        # maxDepthProcessed: the cutoff of both index passes and of the prediction
 FILTER_CUTOFF = 5.0
 CONF = 10.0

@@ -1,4 +1,4 @@
-"""Extent culling of the batched index passes (cf_set_extent_culling; csrc/surfel.hip, EXTENTS): the index-map resolve launches of
+"""Extent culling of the batched index passes (cf_set_extent_culling; csrc/surf_index_dev.h, EXTENTS): the index-map resolve launches of
 cf_models_preindex / cf_models_frame_passes skip the 64-texel runs outside the rectangle a model's maps were rasterised into in this pass
 and in the one before it.  The promise is that every buffer holds the same bytes as without it after every launch.
 

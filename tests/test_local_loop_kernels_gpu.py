@@ -1,5 +1,5 @@
 """GPU suite: the splat passes of local loop closure (cf_model_predict_inactive, cf_model_synthesize_depth in csrc/cabi_model.hip; the
-resolve modes of csrc/surfel.hip) at 256x160 against the CPU oracle on the crafted maps of tests/local_loop_cases.py.
+resolve modes of csrc/surf_splat_dev.h) at 256x160 against the CPU oracle on the crafted maps of tests/local_loop_cases.py.
 
 Inactive prediction: bit for bit orc_combined_predict(time = 0, maxTime, timeDelta); the ACTIVE buffers byte-identical before and after;
 the covered count exact; twice, identical bytes.  Depth synthesis: splat.vert + depth_splat.frag accept what the colour splat accepts

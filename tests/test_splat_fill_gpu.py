@@ -1,5 +1,5 @@
 """GPU parity of the fill-in and the fill ratio that cf_models_frame_passes evaluates inside its last launch for the items that ask
-for it (cf_model_pass::fill_in; csrc/surfel.hip: splat_resolve_kernel with SplatFillArgs -> fill_in_px, fill_ratio_sample, the
+for it (cf_model_pass::fill_in; csrc/surf_splat_dev.h: splat_resolve_kernel with SplatFillArgs -> fill_in_px, fill_ratio_sample, the
 completion ticket) against twin models driven through the separate calls: the chain's statements per model, then
 cf_model_prefetch_fill_ratio + cf_model_perform_fill_in (fill_ratio_kernel, fill_in_kernel).  Bit for bit, NaN equal to NaN:
 the splat buffers 4..7, the fill maps 8..10, the two counts in device memory, and the host's answers (cf_model_requires_fill_in reads
